@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/r02
 export TMPDIR=/tmp
 run_bench() {  # name, args...
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $OUT/$name.log 2>&1
+  timeout -k 10 400 python bench.py --full "$@" > $OUT/$name.log 2>&1
   local rc=$?
   tail -n 1 $OUT/$name.log > $OUT/$name.json
   echo "bench $name rc=$rc"
@@ -16,7 +16,7 @@ run_bench() {  # name, args...
 prof() {  # name, args...
   local name=$1; shift
   cd /tmp
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- python3 $REPO/bench.py "$@" > $OUT/prof_$name.log 2>&1
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- python3 $REPO/bench.py --full "$@" > $OUT/prof_$name.log 2>&1
   local rc=$?
   cd $REPO
   echo "rocprof $name rc=$rc"

@@ -101,6 +101,18 @@ class DOptimalBatch:
         arr = (C.c_int * self.K)(*[1 if a else 0 for a in active])
         return arr, [i for i in range(self.K) if active[i]]
 
+    def _rows(self, **tensors):
+        """The K x n operands (other than func_grad's X, whose row stride is passed) cross the C-ABI with row stride n:
+        refuse any that is laid out otherwise instead of letting the kernels misread it."""
+        for name, T in tensors.items():
+            if T is None:
+                continue
+            if not (isinstance(T, torch.Tensor) and T.is_cuda and T.dtype == torch.float64
+                    and tuple(T.shape) == (self.K, self.n) and T.stride(1) == 1 and (self.K == 1 or T.stride(0) == self.n)):
+                raise ValueError("DOptimalBatch: %s must be a K x n float64 device tensor with row stride n (got shape %s, "
+                                 "strides %s)" % (name, tuple(getattr(T, "shape", ())),
+                                                  T.stride() if isinstance(T, torch.Tensor) else None))
+
     @staticmethod
     def _raise(status, idx, what, assert_msg):
         for i in idx:
@@ -117,6 +129,7 @@ class DOptimalBatch:
         st = (C.c_int * self.K)()
         G = None
         if flag != 0:
+            self._rows(out=out)
             G = out if out is not None else torch.empty(self.K, self.n, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             self._lib.accbpg_dopt_batch_set_stream(self._h, _stream())
@@ -161,6 +174,7 @@ class DOptimalBatch:
     def prox(self, Y, G, Ls, eps, active=None, out=None):
         """Row i: BurgEntropySimplex(eps).div_prox_map(Y[i], G[i], Ls[i]) (Y None: prox_map).  Only the rows of the
         active instances are written (`out`: an existing K x n tensor to write them into)."""
+        self._rows(Y=Y, G=G, out=out)
         mask, idx = self._mask(active)
         Lc = (C.c_double * self.K)(*[float(v) for v in Ls])
         st = (C.c_int * self.K)()
@@ -176,6 +190,7 @@ class DOptimalBatch:
 
     def ls_terms(self, G, X, Y, Z=None, Z1=None, active=None):
         """K x 3 NumPy array: (<g, x-y>, D(x,y), D(z,z1)) per instance."""
+        self._rows(G=G, X=X, Y=Y, Z=Z, Z1=Z1)
         mask, idx = self._mask(active)
         out = (C.c_double * (3 * self.K))()
         st = (C.c_int * self.K)()
@@ -189,6 +204,7 @@ class DOptimalBatch:
 
     def axpby(self, a, X, b, Z, active=None, out=None):
         """Row i: a[i]*X[i] + b[i]*Z[i] with NumPy's rounding; only the rows of the active instances are written."""
+        self._rows(X=X, Z=Z, out=out)
         mask, _ = self._mask(active)
         av = (C.c_double * self.K)(*[float(v) for v in a])
         bv = (C.c_double * self.K)(*[float(v) for v in b])

@@ -11,7 +11,7 @@ extern "C" int accbpg_dopt_batch_destroy(accbpg_dopt_batch* b) {
     if (!b) return ACCBPG_OK;
     for (accbpg_dopt* h : b->inst) accbpg_dopt_destroy(h);
     hipFree(b->table); hipFree(b->chol_table[0]); hipFree(b->chol_table[1]); hipFree(b->ops_all); hipFree(b->red_all);
-    hipFree(b->dscal_all); hipFree(b->vflags); hipFree(b->vout); hipFree(b->vpart); hipFree(b->vgg);
+    hipFree(b->dscal_all); hipFree(b->vflags); hipFree(b->vout); hipFree(b->vpart); hipFree(b->vgg); hipFree(b->vws);
     if (b->hpin) hipHostFree(b->hpin);
     if (b->vpin) hipHostFree(b->vpin);
     delete b;
@@ -44,8 +44,12 @@ static int batch_init(accbpg_dopt_batch* b, const double* const* V_host, int K, 
     if (h0->chol_tiles_ok && h0->chol_tiles_grid > 0)
         b->chunk = std::max(1, std::min(b->chunk, h0->chol_slots / h0->chol_tiles_grid));
     // one launch per kernel family needs: the interior big-tile path, the one-launch Cholesky for every instance at
-    // once, identical plans (same shape and alignment give identical plans)
-    bool fast = h0->big && h0->use_glds && (m % 256 == 0) && (n % 128 == 0) && h0->chol_tiles_ok && K <= BATCH_MAX;
+    // once, identical plans (same shape and alignment give identical plans), and rows short enough for ONE Gram
+    // launch: a plan that cuts the rows into column blocks (gram_chunks > 1: one launch per block, every segment
+    // through a slab, the fix-up adding the blocks up) has no batched counterpart, so such instances are
+    // evaluated one by one
+    bool fast = h0->big && h0->use_glds && (m % 256 == 0) && (n % 128 == 0) && h0->chol_tiles_ok && K <= BATCH_MAX &&
+                h0->gram_chunks == 1;
     for (accbpg_dopt* h : b->inst) fast = fast && h->vec_ok && h->big && h->chol_tiles_ok;
     b->fast = fast;
     if (!fast) return ACCBPG_OK;

@@ -221,6 +221,7 @@ struct accbpg_dopt_batch {
     double* vout = nullptr;                 // K * 4 doubles: reduction results
     double* vpart = nullptr;                // K * 4 * 1024 doubles: reduction partials
     double* vgg = nullptr;                  // K * n doubles: gg of the prox when it does not fit in registers
+    double* vws = nullptr;                  // workspace of the single-instance prox (long vectors, one instance at a time)
     double* vpin = nullptr;                 // pinned mirror (K * 8 doubles)
     // the evaluation in flight between _begin and _end
     accbpg::BatchAct pend_act;

@@ -917,6 +917,23 @@ extern "C" int accbpg_dopt_batch_burg_simplex_div_prox(accbpg_dopt_batch* b, con
     }
     if (act.n == 0) return ACCBPG_OK;
     hipStream_t s = b->stream;
+    if (n > (int64_t)PB * 32) {
+        // Long vectors: the single-instance prox spreads one instance over several workgroups with an order of
+        // summation of its own (burg_prox_multi_kernel), which the one-workgroup-per-instance kernel below does not
+        // reproduce.  Run the single-instance prox itself, instance by instance, so that a batch stays bit for bit
+        // equal to its instances evaluated on their own.
+        if (!b->vws) ACC_HIP(hipMalloc(&b->vws, sizeof(double) * (size_t)vec_ws_doubles(n)));
+        for (int a = 0; a < act.n; ++a) {
+            const int i = act.idx[a];
+            int info[2] = {0, 0};
+            const int rc = accbpg_burg_simplex_div_prox(y_dev ? y_dev + (size_t)i * ld : nullptr, g_dev + (size_t)i * ld,
+                                                        L_host[i], eps, n, x_out_dev + (size_t)i * ld, b->vws, info, s);
+            if (rc == ACCBPG_ERR_ASSERT) status_host[i] = ACCBPG_ERR_ASSERT;   // y.min() > 0, functions.py:270
+            else if (rc != ACCBPG_OK) return rc;
+            if (info_host) { info_host[2 * i] = info[0]; info_host[2 * i + 1] = info[1]; }
+        }
+        return ACCBPG_OK;
+    }
     if (n <= (int64_t)PB * 2)
         burg_prox_batch_kernel<2><<<act.n, PB, 0, s>>>(act, y_dev, g_dev, ld, Ls, eps, n, x_out_dev, nullptr, b->vflags);
     else if (n <= (int64_t)PB * 8)

@@ -9,18 +9,21 @@ kernel, and D_opt_FW / D_opt_FW_away, behind the reference's own names and signa
 All arithmetic runs in hand-written gfx950 HIP kernels (accbpg_and_fw_amd/csrc) through a
 ctypes C-ABI (include/accbpg_hip.h); there is no CPU fallback.
 """
-from .functions import (RSmoothFunction, DOptimalObj, PoissonRegression, LegendreFunction, BurgEntropy,
-                        BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex)
+from .functions import (RSmoothFunction, DOptimalObj, PoissonRegression, KLdivRegression, LegendreFunction,
+                        BurgEntropy, BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, ShannonEntropy,
+                        ShannonEntropyL1, ShannonEntropySimplex)
 from .algorithms import BPG, ABPG, ABPG_gain, ABPG_expo, ABDA, solve_theta
 from .algorithms_fw import FW_alg_div_step
 from .functions_lmo import lmo_simplex
 from .D_opt_alg import D_opt_FW, D_opt_FW_away
-from .applications import D_opt_design, D_opt_libsvm, D_opt_KYinit, Poisson_regrL1, Poisson_regrL2
+from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, Poisson_regrL1, Poisson_regrL2,
+                           KL_nonneg_regr)
 from .utils import load_libsvm_file
 from .batched import DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, solve_batch, solve_instances
 
 __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunction", "BurgEntropy",
            "BurgEntropyL1", "BurgEntropyL2", "BurgEntropySimplex", "Poisson_regrL1", "Poisson_regrL2",
+           "KLdivRegression", "ShannonEntropy", "ShannonEntropyL1", "ShannonEntropySimplex", "KL_nonneg_regr",
            "BPG", "ABPG", "ABPG_gain", "ABPG_expo", "ABDA", "solve_theta", "FW_alg_div_step", "lmo_simplex",
            "D_opt_FW", "D_opt_FW_away", "D_opt_design", "D_opt_libsvm", "D_opt_KYinit", "load_libsvm_file"]
 __version__ = "0.1.0"

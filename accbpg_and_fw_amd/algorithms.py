@@ -18,14 +18,19 @@ import time
 import numpy as np
 import torch
 
-from .functions import BurgEntropy, from_dev, ls_terms, to_dev, vec_axpby, vec_div_scalar, vec_dot_diff
+from .functions import (BurgEntropy, ShannonEntropy, from_dev, ls_terms, shannon_ls_terms, to_dev, vec_axpby,
+                        vec_div_scalar, vec_dot_diff)
 
 
 def _divergences(h, g, x, y, z, z_prev):
-    """(<g, x-y>, D(x,y), D(z,z_prev)); one fused launch when h is this package's Burg kernel."""
+    """(<g, x-y>, D(x,y), D(z,z_prev)); one fused launch when h is this package's Burg or Shannon kernel
+    (g None: no inner product, z None: no second divergence)."""
     if isinstance(h, BurgEntropy):
         return ls_terms(g, x, y, z, z_prev)
-    return vec_dot_diff(g, x, y), h.divergence(x, y), h.divergence(z, z_prev)
+    if isinstance(h, ShannonEntropy):
+        return shannon_ls_terms(g, x, y, z, z_prev, h.delta)
+    lin = vec_dot_diff(g, x, y) if g is not None else 0.0
+    return lin, h.divergence(x, y), (h.divergence(z, z_prev) if z is not None else 0.0)
 
 
 def _lin(f):

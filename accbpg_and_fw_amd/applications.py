@@ -3,8 +3,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, PoissonRegression,
-                        vec_argminmax)
+from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, KLdivRegression,
+                        PoissonRegression, ShannonEntropyL1, vec_argminmax)
 from .utils import load_libsvm_file
 
 
@@ -102,3 +102,18 @@ def Poisson_regrL2(m, n, noise=0.01, lamda=0, randseed=-1, normalizeA=True):
     Returns f, h, L = ||b||_1, x0 = (1/n)*ones."""
     A, b = _poisson_instance(m, n, noise, randseed, normalizeA)
     return PoissonRegression(A, b), BurgEntropyL2(lamda), b.sum(), (1.0 / n) * np.ones(n)
+
+
+def KL_nonneg_regr(m, n, noise=0.01, lamdaL1=0, randseed=-1, normalizeA=True):
+    """minimize_{x >= 0} D_KL(Ax, b) + lamdaL1*||x||_1  (accbpg/applications.py:175-206): legacy global RNG drawn
+    in the order A, x, noise, on the host like the reference's.  Returns f = KLdivRegression, h = ShannonEntropyL1,
+    L = max column sum of A, x0 = 0.5*ones."""
+    if randseed > 0:
+        np.random.seed(randseed)
+    A = np.random.rand(m, n)
+    if normalizeA:
+        A = A / A.sum(axis=0)
+    x = np.random.rand(n)
+    b = np.dot(A, x) + noise * (np.random.rand(m) - 0.5)
+    assert b.min() > 0, "need b > 0 for nonnegative regression."
+    return KLdivRegression(A, b), ShannonEntropyL1(lamdaL1), max(A.sum(axis=0)), 0.5 * np.ones(n)

@@ -262,6 +262,9 @@ int pipe_probe(int iters, int mode, double* ms_out, hipStream_t s);
 
 // vec_kernels.hip
 int64_t vec_ws_doubles(int64_t n);
+// per-(thread, device) scratch of the handle-free entry points: pinned host (32 doubles), device flags (8 ints),
+// device result scalars (16 doubles)
+int vec_scratch(double** pin, int** flags, double** out);
 
 // fw_kernels.hip
 int vt_nsplit(int64_t m, int64_t n, int num_cu);

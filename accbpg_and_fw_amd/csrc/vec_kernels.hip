@@ -651,6 +651,12 @@ static int ensure_scratch() {
     return ACCBPG_OK;
 }
 
+int vec_scratch(double** pin, int** flags, double** out) {
+    ACC_TRY(ensure_scratch());
+    *pin = g_pin; *flags = g_flags; *out = g_out;
+    return ACCBPG_OK;
+}
+
 static bool g_prox_multi_off = false;    // set when the multi-workgroup prox had to give up a wait (then: one workgroup)
 
 int64_t vec_ws_doubles(int64_t n) { return n + 4 * RMAXBLK + 64; }

@@ -464,8 +464,13 @@ class PoissonRegression(RSmoothFunction):
     (borrowed); ``self.A``, ``self.b``, ``self.m``, ``self.n`` stay readable as in the reference.
     Each func_grad is two passes over A: A x with the KL terms fused into its epilogue, then A^T r."""
 
+    _create, _destroy = "accbpg_poisson_create", "accbpg_poisson_destroy"
+    _set_stream, _func_grad, _get_ax = "accbpg_poisson_set_stream", "accbpg_poisson_func_grad", "accbpg_poisson_get_ax"
+    _size_msg = "PoissonRegression: x.size not equal to n."
+    _match_msg = "A and b sizes not matching"
+
     def __init__(self, A, b):
-        assert A.shape[0] == b.shape[0], "A and b sizes not matching"
+        assert A.shape[0] == b.shape[0], self._match_msg
         self.A = A
         self.b = b
         self.m = A.shape[0]
@@ -475,9 +480,9 @@ class PoissonRegression(RSmoothFunction):
         lib = _lib.load()
         h = C.c_void_p()
         with torch.cuda.device(self._A.device):
-            rc = lib.accbpg_poisson_create(_ptr(self._A), self.m, self.n, self._A.stride(0), _ptr(self._b),
-                                           _stream(), C.byref(h))
-        _lib.check(rc, "accbpg_poisson_create")
+            rc = getattr(lib, self._create)(_ptr(self._A), self.m, self.n, self._A.stride(0), _ptr(self._b),
+                                            _stream(), C.byref(h))
+        _lib.check(rc, self._create)
         self._h = h
         self._lib = lib
 
@@ -485,7 +490,7 @@ class PoissonRegression(RSmoothFunction):
         h = getattr(self, "_h", None)
         if h:
             try:
-                self._lib.accbpg_poisson_destroy(h)
+                getattr(self._lib, self._destroy)(h)
             except Exception:
                 pass
             self._h = None
@@ -498,14 +503,14 @@ class PoissonRegression(RSmoothFunction):
 
     def func_grad(self, x, flag=2):
         size = x.numel() if isinstance(x, torch.Tensor) else x.size
-        assert size == self.n, "PoissonRegression: x.size not equal to n."
+        assert size == self.n, self._size_msg
         xd, was_np = to_dev(x)
         g = torch.empty(self.n, dtype=torch.float64, device=self._A.device) if flag != 0 else None
         fval = C.c_double(0.0)
         with torch.cuda.device(self._A.device):
-            self._lib.accbpg_poisson_set_stream(self._h, _stream())
-            rc = self._lib.accbpg_poisson_func_grad(self._h, _ptr(xd), int(flag), C.byref(fval), _ptr(g))
-        _lib.check(rc, "accbpg_poisson_func_grad")
+            getattr(self._lib, self._set_stream)(self._h, _stream())
+            rc = getattr(self._lib, self._func_grad)(self._h, _ptr(xd), int(flag), C.byref(fval), _ptr(g))
+        _lib.check(rc, self._func_grad)
         if flag == 0:
             return fval.value
         if flag == 1:
@@ -516,9 +521,20 @@ class PoissonRegression(RSmoothFunction):
         """A x of the last evaluation (length m) as a NumPy vector."""
         out = torch.empty(self.m, dtype=torch.float64, device=self._A.device)
         with torch.cuda.device(self._A.device):
-            rc = self._lib.accbpg_poisson_get_ax(self._h, _ptr(out))
-        _lib.check(rc, "accbpg_poisson_get_ax")
+            rc = getattr(self._lib, self._get_ax)(self._h, _ptr(out))
+        _lib.check(rc, self._get_ax)
         return out.cpu().numpy()
+
+
+class KLdivRegression(PoissonRegression):
+    """f(x) = D_KL(Ax, b) for the nonnegative regression A x = b  (accbpg/functions.py:123-158).
+
+    Same storage, device-tensor behaviour and two passes over A as PoissonRegression; only the per-row epilogue of
+    the A x pass differs: r = log(Ax/b), t = Ax*log(Ax/b) - Ax + b, and g = A^T r."""
+    _create, _destroy = "accbpg_kldiv_create", "accbpg_kldiv_destroy"
+    _set_stream, _func_grad, _get_ax = "accbpg_kldiv_set_stream", "accbpg_kldiv_func_grad", "accbpg_kldiv_get_ax"
+    _size_msg = "NonnegRegression: x.size not equal to n."
+    _match_msg = "A and b size not matching"
 
 
 # ------------------------------------------------------------------ h
@@ -670,6 +686,91 @@ class BurgEntropySimplex(BurgEntropy):
         return self._prox(y, g, L)
 
 
+class ShannonEntropy(LegendreFunction):
+    """h(x) = sum x_i log x_i for x >= 0, h(0) = 0  (accbpg/functions.py:398-438).  ``delta`` guards the
+    logarithms of the divergence at exact zeros."""
+    _kind = 0       # variant of accbpg_shannon_div_prox
+    lamda = 0
+
+    def __init__(self, delta=1e-20):
+        self.delta = delta
+
+    def __call__(self, x):
+        # off the solver path (no solver calls h(x)); evaluated with torch on the device
+        xd, _ = to_dev(x)
+        assert float(xd.min()) >= 0, "ShannonEntropy takes nonnegative arguments."
+        xx = torch.clamp(xd, min=self.delta)
+        return float((xx * torch.log(xx)).sum())
+
+    def gradient(self, x):
+        xd, was_np = to_dev(x)
+        assert float(xd.min()) >= 0, "ShannonEntropy takes nonnegative arguments."
+        return from_dev(1.0 + torch.log(torch.clamp(xd, min=self.delta)), was_np)
+
+    def divergence(self, x, y):
+        assert x.shape == y.shape, "Vectors x and y are of different shapes."
+        xd, _ = to_dev(x)
+        yd, _ = to_dev(y)
+        n = xd.numel()
+        out = C.c_double(0.0)
+        with torch.cuda.device(xd.device):
+            ws = _Workspace.get(n, xd.device)
+            rc = _lib.load().accbpg_shannon_divergence(_ptr(xd), _ptr(yd), n, float(self.delta), C.byref(out),
+                                                       _ptr(ws), _stream())
+        _lib.check(rc, "accbpg_shannon_divergence", "Some entries are negative.")
+        return np.float64(out.value)                            # a NumPy scalar, as the reference's sum is (:421)
+
+    def _prox(self, y, g, L, msg):
+        gd, was_np = to_dev(g)
+        yd = None
+        if y is not None:
+            yd, _ = to_dev(y)
+        n = gd.numel()
+        out = torch.empty_like(gd)
+        with torch.cuda.device(gd.device):
+            ws = _Workspace.get(n, gd.device) if self._kind == 2 else None
+            rc = _lib.load().accbpg_shannon_div_prox(self._kind, _ptr(yd), _ptr(gd), float(L), float(self.lamda), n,
+                                                     _ptr(out), _ptr(ws), _stream())
+        _lib.check(rc, "accbpg_shannon_div_prox", msg)
+        return from_dev(out, was_np)
+
+    def prox_map(self, g, L):
+        assert L > 0, "ShannonEntropy prox_map require L > 0."
+        return self._prox(None, g, L, None)
+
+    def div_prox_map(self, y, g, L):
+        assert y.shape == g.shape, "Vectors y and g are of different sizes."
+        assert L > 0, "Some entries of y are negavie."
+        return self._prox(y, g, L, "Some entries of y are negavie.")    # y.min() >= 0 on the device (:437)
+
+
+class ShannonEntropyL1(ShannonEntropy):
+    """Shannon entropy for min_{x >= 0} f(x) + lamda*||x||_1  (accbpg/functions.py:441-466): the prox maps
+    take lamda + g."""
+    _kind = 1
+
+    def __init__(self, lamda=0, delta=1e-20):
+        ShannonEntropy.__init__(self, delta)
+        self.lamda = lamda
+
+    def extra_Psi(self, x):
+        if self.lamda == 0:
+            return 0.0
+        xd, _ = to_dev(x)
+        return self.lamda * vec_min_sum(xd)[1]
+
+
+class ShannonEntropySimplex(ShannonEntropy):
+    """Shannon entropy with the unit-simplex constraint (accbpg/functions.py:469-490): the prox maps of
+    ShannonEntropy divided by their sum."""
+    _kind = 2
+
+    def div_prox_map(self, y, g, L):
+        assert y.shape == g.shape, "Vectors y and g are of different shapes."
+        assert L > 0, "prox_map needs positive arguments."
+        return self._prox(y, g, L, "prox_map needs positive arguments.")   # y.min() > 0 on the device (:488)
+
+
 # ------------------------------------------------------------------ vector helpers for the solver loops
 def vec_axpby(a, x, b, z):
     """a*x + b*z with NumPy's rounding (two products, one sum)."""
@@ -711,6 +812,17 @@ def ls_terms(g, x, y, z=None, z1=None):
     # NumPy scalars, as the reference's sums are (accbpg/functions.py:253): D(x+,y) / D(z+,z) with D(z+,z) == 0 --
     # an iterate that has stopped moving -- is then inf or nan with a warning, as in the reference, not an exception
     # (the stopping rule dzz < epsilon right behind it ends the run, accbpg/algorithms.py:155,174)
+    return np.float64(out[0]), np.float64(out[1]), np.float64(out[2])
+
+
+def shannon_ls_terms(g, x, y, z=None, z1=None, delta=1e-20):
+    """(<g,x-y>, D(x,y), D(z,z1)) of the Shannon entropy in one streaming pass and one readback (g None: 0)."""
+    out = (C.c_double * 3)(0.0, 0.0, 0.0)
+    with torch.cuda.device(x.device):
+        ws = _Workspace.get(x.numel(), x.device)
+        rc = _lib.load().accbpg_shannon_ls_terms(_ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(),
+                                                 float(delta), out, _ptr(ws), _stream())
+    _lib.check(rc, "accbpg_shannon_ls_terms", "Some entries are negative.")
     return np.float64(out[0]), np.float64(out[1]), np.float64(out[2])
 
 

@@ -300,6 +300,43 @@ int accbpg_poisson_func_grad(accbpg_poisson* h, const double* x_dev, int flag, d
 /* out_dev <- Ax of the last func_grad (length m). */
 int accbpg_poisson_get_ax(accbpg_poisson* h, double* out_dev);
 
+/* ---- KL-divergence nonnegative regression with Shannon-entropy kernels ----------------------------------- */
+
+typedef struct accbpg_kldiv accbpg_kldiv;
+
+/* f(x) = D_KL(Ax, b): replaces KLdivRegression.__init__ (accbpg/functions.py:123-134).  Same layout and
+ * ownership rules as accbpg_poisson_create: A row-major m x n with leading dimension lda >= n (any base
+ * alignment), b length m; both owned by the caller. */
+int accbpg_kldiv_create(const double* A_dev, int64_t m, int64_t n, int64_t lda, const double* b_dev,
+                        void* stream, accbpg_kldiv** out);
+int accbpg_kldiv_destroy(accbpg_kldiv* h);
+int accbpg_kldiv_set_stream(accbpg_kldiv* h, void* stream);
+
+/* KLdivRegression.func_grad (accbpg/functions.py:141-158): flag 0 -> *f_host = sum(Ax*log(Ax/b) - Ax + b);
+ * flag 1 -> g_dev = A^T log(Ax/b); flag 2 -> both.  Synchronises the stream when a value is returned. */
+int accbpg_kldiv_func_grad(accbpg_kldiv* h, const double* x_dev, int flag, double* f_host, double* g_dev);
+
+/* out_dev <- Ax of the last func_grad (length m). */
+int accbpg_kldiv_get_ax(accbpg_kldiv* h, double* out_dev);
+
+/* Shannon-entropy prox maps.  kind 0: ShannonEntropy, y_dev == NULL -> exp(-g/L - 1) (accbpg/functions.py:423-429),
+ * y_dev != NULL -> y*exp(-g/L) (:431-438, asserts y >= 0); kind 1: ShannonEntropyL1, the same with lamda + g
+ * (:456-466); kind 2: ShannonEntropySimplex, the kind-0 result divided by its sum (:475-490, the div form asserts
+ * y > 0; ws_dev: accbpg_vec_workspace_doubles(n) doubles).  A failed assertion or L <= 0 returns ACCBPG_ERR_ASSERT. */
+int accbpg_shannon_div_prox(int kind, const double* y_dev, const double* g_dev, double L, double lamda, int64_t n,
+                            double* x_out_dev, double* ws_dev, void* stream);
+
+/* out_host[0..2] <- { <g, x - y>, D(x, y), D(z, z1) } with D(x,y) = sum(x*log((x+delta)/(y+delta))) + (sum(y) -
+ * sum(x)) (ShannonEntropy.divergence, accbpg/functions.py:415-421), each of the three sums reduced on its own fixed
+ * tree.  g_dev NULL skips the first term (0), z_dev = z1_dev = NULL the last.  Negative entries of x, y, z, z1
+ * return ACCBPG_ERR_ASSERT (:418).  One readback; ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_shannon_ls_terms(const double* g_dev, const double* x_dev, const double* y_dev, const double* z_dev,
+                            const double* z1_dev, int64_t n, double delta, double* out_host, double* ws_dev,
+                            void* stream);
+/* *out_host <- D(x, y) alone (accbpg_shannon_ls_terms without g, z, z1). */
+int accbpg_shannon_divergence(const double* x_dev, const double* y_dev, int64_t n, double delta, double* out_host,
+                              double* ws_dev, void* stream);
+
 /* Closed-form Burg-entropy prox maps on x > 0.  kind 0: BurgEntropy.prox_map L/g (accbpg/functions.py:255-262);
  * kind 1: BurgEntropyL1.prox_map L/(lamda+g) (:290-298); kind 2: BurgEntropyL2.prox_map (:316-323).  With
  * y_dev != NULL the argument is g - L*(-1/y) first, i.e. BurgEntropy.div_prox_map (:264-271).

@@ -11,13 +11,15 @@ ctypes C-ABI (include/accbpg_hip.h); there is no CPU fallback.
 """
 from .functions import (RSmoothFunction, DOptimalObj, PoissonRegression, KLdivRegression, LegendreFunction,
                         BurgEntropy, BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, ShannonEntropy,
-                        ShannonEntropyL1, ShannonEntropySimplex)
+                        ShannonEntropyL1, ShannonEntropySimplex, FrobeniusSymLoss, SumOf2nd4thPowers,
+                        SumOf2nd4thPowersPositiveOrthant, SquaredL2Norm)
 from .algorithms import BPG, ABPG, ABPG_gain, ABPG_expo, ABDA, solve_theta
-from .algorithms_fw import FW_alg_div_step
-from .functions_lmo import lmo_simplex
+from .algorithms_fw import FW_alg_div_step, FW_alg_descent_step
+from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball
 from .D_opt_alg import D_opt_FW, D_opt_FW_away
 from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, Poisson_regrL1, Poisson_regrL2,
-                           KL_nonneg_regr)
+                           KL_nonneg_regr, FrobeniusSymLossExL2Ball, FrobeniusSymLossExLInfBall,
+                           FrobeniusSymLossResMeasEx)
 from .utils import load_libsvm_file
 from .batched import DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, solve_batch, solve_instances
 
@@ -25,5 +27,8 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "BurgEntropyL1", "BurgEntropyL2", "BurgEntropySimplex", "Poisson_regrL1", "Poisson_regrL2",
            "KLdivRegression", "ShannonEntropy", "ShannonEntropyL1", "ShannonEntropySimplex", "KL_nonneg_regr",
            "BPG", "ABPG", "ABPG_gain", "ABPG_expo", "ABDA", "solve_theta", "FW_alg_div_step", "lmo_simplex",
-           "D_opt_FW", "D_opt_FW_away", "D_opt_design", "D_opt_libsvm", "D_opt_KYinit", "load_libsvm_file"]
+           "D_opt_FW", "D_opt_FW_away", "D_opt_design", "D_opt_libsvm", "D_opt_KYinit", "load_libsvm_file",
+           "FrobeniusSymLoss", "SumOf2nd4thPowers", "SumOf2nd4thPowersPositiveOrthant", "SquaredL2Norm",
+           "FW_alg_descent_step", "lmo_l2_ball", "lmo_linf_ball", "FrobeniusSymLossExL2Ball",
+           "FrobeniusSymLossExLInfBall", "FrobeniusSymLossResMeasEx"]
 __version__ = "0.1.0"

@@ -99,6 +99,17 @@ _SIGS = {
     "accbpg_shannon_div_prox": (C.c_int, [C.c_int, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P]),
     "accbpg_shannon_ls_terms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double), _P, _P]),
     "accbpg_shannon_divergence": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double), _P, _P]),
+    "accbpg_symnmf_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_double, _P, C.POINTER(_P)]),
+    "accbpg_symnmf_destroy": (C.c_int, [_P]),
+    "accbpg_symnmf_set_stream": (C.c_int, [_P, _P]),
+    "accbpg_symnmf_func_grad": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_double), _P]),
+    "accbpg_symnmf_plan": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "accbpg_quartic_prox_stage": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int64, _P,
+                                            C.POINTER(C.c_double), _P, _P]),
+    "accbpg_quartic_ls_terms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), _P, _P]),
+    "accbpg_lmo_l2_ball": (C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_double, C.c_int64, _P,
+                                     C.POINTER(C.c_double), _P, _P]),
+    "accbpg_lmo_linf_ball": (C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_int64, _P, _P]),
     "accbpg_burg_reg_div_prox": (C.c_int, [C.c_int, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P]),
     "accbpg_vec_dot": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_double), _P, _P]),
     "accbpg_dopt_profile_enable": (C.c_int, [_P, C.c_int]),

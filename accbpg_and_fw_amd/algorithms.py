@@ -18,17 +18,19 @@ import time
 import numpy as np
 import torch
 
-from .functions import (BurgEntropy, ShannonEntropy, from_dev, ls_terms, shannon_ls_terms, to_dev, vec_axpby,
-                        vec_div_scalar, vec_dot_diff)
+from .functions import (BurgEntropy, ShannonEntropy, SumOf2nd4thPowers, from_dev, ls_terms, shannon_ls_terms,
+                        to_dev, vec_axpby, vec_div_scalar, vec_dot_diff)
 
 
 def _divergences(h, g, x, y, z, z_prev):
-    """(<g, x-y>, D(x,y), D(z,z_prev)); one fused launch when h is this package's Burg or Shannon kernel
-    (g None: no inner product, z None: no second divergence)."""
+    """(<g, x-y>, D(x,y), D(z,z_prev)); one fused launch when h is this package's Burg, Shannon or quartic kernel
+    (g None: no inner product, z None: no second divergence).  Inner products of n x r iterates are flat."""
     if isinstance(h, BurgEntropy):
         return ls_terms(g, x, y, z, z_prev)
     if isinstance(h, ShannonEntropy):
         return shannon_ls_terms(g, x, y, z, z_prev, h.delta)
+    if isinstance(h, SumOf2nd4thPowers):
+        return h.ls_terms(g, x, y, z, z_prev)
     lin = vec_dot_diff(g, x, y) if g is not None else 0.0
     return lin, h.divergence(x, y), (h.divergence(z, z_prev) if z is not None else 0.0)
 

@@ -1,6 +1,8 @@
 """Frank-Wolfe with a step length taken from the Bregman divergence to the LMO vertex, on device
-vectors (behaviour of accbpg/algorithms_fw.py:6-75; used with ``lmo_simplex`` on the D-optimal
-objective as in frank_wolfe_wtih_rs/ex_Dopt_design.py:17-18).
+vectors or n x r matrices (behaviour of accbpg/algorithms_fw.py:6-75; used with ``lmo_simplex`` on the
+D-optimal objective as in frank_wolfe_wtih_rs/ex_Dopt_design.py:17-18, and with the ball LMOs on the
+SymNMF objective as in parameters_free_fw/ipynb/ex_SymNMF.ipynb), and Frank-Wolfe with the classical
+step 2/(k+2) (accbpg/algorithms_fw.py:210-247).
 
 Written like the other solvers of this package: a step generator that the public function drains,
 preallocated traces cut to the iterations that ran, and one fused launch for the slope <g, s - x> and
@@ -14,7 +16,7 @@ import time
 import numpy as np
 
 from .algorithms import _divergences, _drain
-from .functions import from_dev, to_dev, vec_axpby
+from .functions import from_dev, to_dev, vec_axpby, vec_dot
 
 _SLOPE_FLOOR = 1e-6     # stand-in for a vanishing divergence, and the band of slopes treated as zero
 
@@ -93,3 +95,48 @@ def FW_alg_div_step_steps(f, h, L, x0, maxitrs, gamma, lmo, epsilon=1e-14, lines
         yield k
 
     return from_dev(point, as_numpy), F[:done], Ls[:done], T[:done]
+
+
+def FW_alg_descent_step(f, h, x0, maxitrs, lmo, epsilon=1e-14, verbose=True, verbskip=1):
+    """Returns (x, F, T, G) with G all zeros, as the reference does.  Iteration k >= 1 moves x by 2/(k+2) towards
+    s = lmo(grad f(x)) and stops on |F[k] - F[k-1]| < epsilon or ||grad f(x)|| < epsilon.  With maxitrs = 1 the
+    reference fails (UnboundLocalError on k); this returns the single evaluation at x0."""
+    return _drain(FW_alg_descent_step_steps(f, h, x0, maxitrs, lmo, epsilon, verbose, verbskip))
+
+
+def FW_alg_descent_step_steps(f, h, x0, maxitrs, lmo, epsilon=1e-14, verbose=True, verbskip=1):
+    """Generator form: yields k after each iteration, returns FW_alg_descent_step's tuple."""
+    if verbose:
+        print("\nFW descent step size algorithm")
+        print("     k      F(x)         alpha_k       time")
+
+    t_start = time.time()
+    F = np.zeros(maxitrs)
+    G = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+
+    point, as_numpy = to_dev(x0)
+    point = point.clone()
+    value, grad = f.func_grad(point)
+    F[0] = value + h.extra_Psi(point)
+    T[0] = time.time() - t_start
+
+    k = 0
+    for k in range(1, maxitrs):
+        vertex = lmo(grad)
+        towards = vec_axpby(1.0, vertex, -1.0, point)                          # d = s - x
+        alpha = 2 / (k + 2)
+        point = vec_axpby(1.0, point, alpha, towards)                          # x + alpha*d
+
+        value, grad = f.func_grad(point)
+        F[k] = value + h.extra_Psi(point)
+        T[k] = time.time() - t_start
+
+        if verbose and (k % verbskip == 0 or k == 1):
+            print(f"{k:6d}  {F[k]:10.3e}  {alpha:10.3e}  {T[k]:6.1f}")
+
+        if abs(F[k] - F[k - 1]) < epsilon or math.sqrt(vec_dot(grad, grad)) < epsilon:
+            break
+        yield k
+
+    return from_dev(point, as_numpy), F[:k + 1], T[:k + 1], G[:k + 1]

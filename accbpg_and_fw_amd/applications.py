@@ -1,10 +1,11 @@
-"""Problem factory for the D-optimal design benchmark (accbpg/applications.py:36-56)."""
+"""Problem factories (accbpg/applications.py): D-optimal design, Poisson and KL regression, and symmetric NMF."""
 from __future__ import annotations
 
 import numpy as np
 
-from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, KLdivRegression,
-                        PoissonRegression, ShannonEntropyL1, vec_argminmax)
+from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, FrobeniusSymLoss,
+                        KLdivRegression, PoissonRegression, ShannonEntropyL1, SquaredL2Norm, SumOf2nd4thPowers,
+                        SumOf2nd4thPowersPositiveOrthant, vec_argminmax)
 from .utils import load_libsvm_file
 
 
@@ -117,3 +118,98 @@ def KL_nonneg_regr(m, n, noise=0.01, lamdaL1=0, randseed=-1, normalizeA=True):
     b = np.dot(A, x) + noise * (np.random.rand(m) - 0.5)
     assert b.min() > 0, "need b > 0 for nonnegative regression."
     return KLdivRegression(A, b), ShannonEntropyL1(lamdaL1), max(A.sum(axis=0)), 0.5 * np.ones(n)
+
+
+def _symnmf_l2_instance(n, r, ball_center, radius=1.0, on_boundary=True):
+    """(M, X0) of FrobeniusSymLossExL2Ball on the host: the legacy global RNG drawn in the reference's order
+    (accbpg/applications.py:330-352), with its assertions."""
+    rows = n
+    X = np.random.randn(n, r)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    if on_boundary:
+        X *= radius
+    else:
+        scales = np.random.uniform(0, 1, size=(n, 1)) ** (1 / r)
+        X *= radius * scales
+    X += ball_center
+
+    assert np.all(X >= 0), "X must be non-negative"
+    distances_l2_ball = np.linalg.norm(X - ball_center, axis=1)
+    if on_boundary:
+        assert np.all(np.abs(distances_l2_ball - radius) < 1e-6), "Some points are not on L2 ball boundary"
+    else:
+        assert np.all(distances_l2_ball <= radius + 1e-6), "Some points lie outside the L2 ball"
+
+    approx_matrix = X.dot(X.T)
+    assert np.allclose(approx_matrix, approx_matrix.T), "matrix must be symmetric"
+    assert np.all(approx_matrix >= 0), "approx_matrix must be non-negative"
+    assert approx_matrix.shape[0] == approx_matrix.shape[1], "approx_matrix must be square"
+
+    X0 = np.ones((rows, r)) * radius + 1e-5 * radius
+    assert np.all(X0 >= 0), "X0 must be non-negative"
+    return approx_matrix, X0
+
+
+def _symnmf_linf_instance(n, r, ball_center, radius=1.0, on_boundary=True):
+    """(M, X0) of FrobeniusSymLossExLInfBall on the host (accbpg/applications.py:363-392), same RNG order and
+    assertions."""
+    X = np.random.randn(n, r)
+    X /= np.max(np.abs(X))
+    if on_boundary:
+        X *= radius
+    else:
+        X *= radius * np.random.uniform(0, 1)
+    X += ball_center
+
+    assert np.all(X >= 0), "X must be non-negative"
+    distances_linf_ball = np.max(np.abs(X - ball_center))
+    if on_boundary:
+        assert np.abs(distances_linf_ball - radius) <= 1e-6, "X is not on L∞ ball boundary"
+    else:
+        assert distances_linf_ball <= radius + 1e-6, "X is outside the L∞ ball"
+
+    approx_matrix = X @ X.T
+    assert np.allclose(approx_matrix, approx_matrix.T), "approx_matrix must be symmetric"
+    assert np.all(approx_matrix >= 0), "approx_matrix must be non-negative"
+
+    X0 = np.ones((n, r)) * radius + 1e-5 * radius
+    assert np.all(X0 >= 0), "X0 must be non-negative"
+    assert np.max(np.abs(X0 - ball_center)) < radius
+    return approx_matrix, X0
+
+
+def FrobeniusSymLossExL2Ball(n, r, ball_center, radius=1.0, on_boundary=True):
+    """SymNMF instance M = X X^T with the rows of X on (or inside) an l2 ball (accbpg/applications.py:330-360).
+    Returns f = FrobeniusSymLoss, h = SumOf2nd4thPowers(6, 2*||M||_2), L = 1, X0 and M (NumPy)."""
+    approx_matrix, X0 = _symnmf_l2_instance(n, r, ball_center, radius, on_boundary)
+    f = FrobeniusSymLoss(approx_matrix, X0)
+    L = 1
+    alpha = 6
+    sigma = 2 * np.linalg.norm(approx_matrix, 2)
+    h = SumOf2nd4thPowers(alpha, sigma)
+    return f, h, L, X0, approx_matrix
+
+
+def FrobeniusSymLossExLInfBall(n, r, ball_center, radius=1.0, on_boundary=True):
+    """SymNMF instance M = X X^T with X on (or inside) an l-infinity ball (accbpg/applications.py:363-399).
+    Returns f, h = SumOf2nd4thPowers(6, 2*||M||_2), L = 1, X0 and M (NumPy)."""
+    approx_matrix, X0 = _symnmf_linf_instance(n, r, ball_center, radius, on_boundary)
+    f = FrobeniusSymLoss(approx_matrix, X0)
+    L = 1
+    alpha = 6
+    sigma = 2 * np.linalg.norm(approx_matrix, 2)
+    h = SumOf2nd4thPowers(alpha, sigma)
+    return f, h, L, X0, approx_matrix
+
+
+def FrobeniusSymLossResMeasEx(M, r, noise=0.0):
+    """SymNMF of a given symmetric M from X0 = rand(n, r) (accbpg/applications.py:402-415).  Returns f,
+    [SumOf2nd4thPowersPositiveOrthant(6, 2*||M||_2), SquaredL2Norm()], L = 1, X0.  As in the reference, `noise`
+    is not passed on."""
+    X0 = np.random.rand(M.shape[0], r)
+    assert np.all(X0 >= 0) >= 0, "X0 must be non-negative"
+    f = FrobeniusSymLoss(M, X0)
+    h = SumOf2nd4thPowersPositiveOrthant(6, 2 * np.linalg.norm(M, 2), upper_bound=None)
+    h_euklid = SquaredL2Norm()
+    L = 1
+    return f, [h, h_euklid], L, X0

@@ -537,6 +537,85 @@ class KLdivRegression(PoissonRegression):
     _match_msg = "A and b size not matching"
 
 
+class FrobeniusSymLoss(RSmoothFunction):
+    """f(X) = 0.5*||M - X X^T||_F^2 for symmetric nonnegative matrix factorisation (accbpg/functions.py:908-976).
+
+    ``M`` (n x n, symmetric) may be a NumPy array (copied to the GPU once) or an fp64 CUDA tensor (borrowed, any row
+    stride >= n); ``X_init`` fixes the iterate shape n x r.  ``self.M``, ``self.M_norm`` and ``self.noise_level`` stay
+    readable as in the reference.  Each evaluation is one fp64 MFMA pass over M for M X, with X^T X, X (X^T X), the
+    gradient combine and the value's two sums in small launches behind it (symnmf_kernels.hip).  With a noise level,
+    every call draws np.random.randn(*X.shape) from the legacy global generator, as the reference does (:961-964)."""
+
+    def __init__(self, M, X_init, noise_level=None):
+        if isinstance(M, torch.Tensor):
+            assert bool(torch.allclose(M, M.T)), "Matrix M must be symmetric."
+            self.M_norm = float(torch.linalg.norm(M.to(torch.float64)))
+        else:
+            assert np.allclose(M, M.T), "Matrix M must be symmetric."
+            self.M_norm = np.linalg.norm(M)
+        self.M = M
+        self.noise_level = noise_level
+        self.n = M.shape[0]
+        self.shape = tuple(X_init.shape)
+        assert len(self.shape) == 2 and self.shape[0] == self.n, "FrobeniusSymLoss: X_init must be n x r."
+        self.r = self.shape[1]
+        if isinstance(M, torch.Tensor) and M.is_cuda and M.dtype == torch.float64 and M.stride(1) == 1 \
+                and M.stride(0) >= self.n:
+            self._M = M                                         # borrowed with its row stride
+        else:
+            self._M, _ = to_dev(M)
+        lib = _lib.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self._M.device):
+            rc = lib.accbpg_symnmf_create(_ptr(self._M), self.n, self._M.stride(0), self.r, float(self.M_norm),
+                                          _stream(), C.byref(h))
+        _lib.check(rc, "accbpg_symnmf_create")
+        self._h = h
+        self._lib = lib
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.accbpg_symnmf_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def __call__(self, x):
+        return self.func_grad(x, flag=0)
+
+    def gradient(self, x):
+        return self.func_grad(x, flag=1)
+
+    def plan(self):
+        """(k pieces of the M X product, rows per piece, wide tile, row chunks of X^T X) of this handle."""
+        out = (C.c_int64 * 4)()
+        _lib.check(self._lib.accbpg_symnmf_plan(self._h, out), "accbpg_symnmf_plan")
+        return tuple(out)
+
+    def func_grad(self, X, flag=2):
+        """flag=0: function, flag=1: gradient, flag=2: function & gradient."""
+        noise = None
+        if self.noise_level is not None:
+            noise = (np.random.randn(*X.shape) - 0.5) * self.noise_level        # functions.py:964
+        assert tuple(X.shape) == self.shape, "FrobeniusSymLoss: X.shape not equal to (n, r)."
+        xd, was_np = to_dev(X)
+        fval = C.c_double(0.0)
+        g = torch.empty(self.shape, dtype=torch.float64, device=self._M.device) if flag != 0 else None
+        with torch.cuda.device(self._M.device):
+            self._lib.accbpg_symnmf_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_symnmf_func_grad(self._h, _ptr(xd), int(flag), C.byref(fval), _ptr(g))
+        _lib.check(rc, "accbpg_symnmf_func_grad")
+        if flag == 0:
+            return np.float64(fval.value)
+        if noise is not None:
+            nd, _ = to_dev(noise)
+            g = vec_axpby(1.0, g, 1.0, nd)                                    # g + noise_vector
+        g = from_dev(g, was_np)
+        return g if flag == 1 else (np.float64(fval.value), g)
+
+
 # ------------------------------------------------------------------ h
 class LegendreFunction:
     """Legendre kernel protocol (accbpg/functions.py:199-235)."""
@@ -771,6 +850,120 @@ class ShannonEntropySimplex(ShannonEntropy):
         return self._prox(y, g, L, "prox_map needs positive arguments.")   # y.min() > 0 on the device (:488)
 
 
+class SumOf2nd4thPowers(LegendreFunction):
+    """h(x) = (sigma/2)||x||^2 + (alpha/4)||x||^4 on vectors or n x r matrices (Frobenius norm), accbpg/functions.py:
+    493-555.  The norms come from device sums of squares; the scalar recurrences (norm**4, norm**2, the cubic of the
+    prox map) run on the host in float64 with the reference's formulas."""
+    _clip = 0
+    upper_bound = None
+
+    def __init__(self, alpha, sigma):
+        self.alpha = alpha
+        self.sigma = sigma
+
+    def _norm(self, xd):
+        return np.sqrt(np.float64(vec_dot(xd, xd)))
+
+    def _h_of_norm(self, norm):
+        return (self.alpha / 4) * norm ** 4 + self.sigma / 2 * norm ** 2
+
+    def __call__(self, x):
+        xd, _ = to_dev(x)
+        return self._h_of_norm(self._norm(xd))
+
+    def gradient(self, x):
+        xd, was_np = to_dev(x)
+        norm = self._norm(xd)
+        return from_dev(vec_axpby(self.sigma + self.alpha * norm ** 2, xd, 0.0, xd), was_np)
+
+    def _divergence_of(self, nx2, ny2, ydiff):
+        """h(x) - (h(y) + <grad h(y), x - y>) from ||x||^2, ||y||^2 and <y, x - y> (functions.py:518-521)."""
+        ny = np.sqrt(np.float64(ny2))
+        c = self.sigma + self.alpha * ny ** 2
+        return self._h_of_norm(np.sqrt(np.float64(nx2))) - (self._h_of_norm(ny) + c * ydiff)
+
+    def divergence(self, x, y):
+        assert x.shape == y.shape, "Bregman div: x and y not same shape."
+        xd, _ = to_dev(x)
+        yd, _ = to_dev(y)
+        o = quartic_ls_terms(None, xd, yd)
+        return self._divergence_of(o[1], o[2], o[3])
+
+    def ls_terms(self, g, x, y, z=None, z1=None):
+        """(<g,x-y>, D(x,y), D(z,z1)) in one launch and one readback."""
+        o = quartic_ls_terms(g, x, y, z, z1)
+        dzz = self._divergence_of(o[4], o[5], o[6]) if z is not None else 0.0
+        return np.float64(o[0]), self._divergence_of(o[1], o[2], o[3]), dzz
+
+    def solve_cubic(self, c, alpha):
+        """The real root of z^3 - alpha*z^2 = c, c > 0 (functions.py:522-544), on the host."""
+        z = alpha / 3.0
+        alpha3 = alpha ** 3
+        delta = c ** 2 + 4 * alpha3 * c / 27.0
+        sq_delta = np.sqrt(delta)
+        b = 0.5 * c + alpha3 / 27.0
+        z += np.cbrt(b + 0.5 * sq_delta)
+        z += np.cbrt(b - 0.5 * sq_delta)
+        return z
+
+    def div_prox_map(self, y, g, L):
+        yd, was_np = to_dev(y)
+        gd, _ = to_dev(g)
+        z = self.alpha * self._norm(yd) ** 2 + self.sigma                     # :551
+        n = yd.numel()
+        out = torch.empty_like(yd)
+        ssq = C.c_double(0.0)
+        ub = np.inf if self.upper_bound is None else float(self.upper_bound)
+        with torch.cuda.device(yd.device):
+            ws = _Workspace.get(n, yd.device)
+            rc = _lib.load().accbpg_quartic_prox_stage(_ptr(yd), _ptr(gd), float(z), float(1 / L), self._clip, ub, n,
+                                                       _ptr(out), C.byref(ssq), _ptr(ws), _stream())
+        _lib.check(rc, "accbpg_quartic_prox_stage")
+        norm = np.sqrt(np.float64(ssq.value))
+        z = self.solve_cubic(self.alpha * norm ** 2, self.sigma)                 # :554
+        return from_dev(vec_div_scalar(out, z), was_np)
+
+
+class SumOf2nd4thPowersPositiveOrthant(SumOf2nd4thPowers):
+    """SumOf2nd4thPowers on the nonnegative orthant (accbpg/functions.py:558-577): the prox map clips
+    z*y - g/L to [0, upper_bound] before the cubic."""
+    _clip = 1
+
+    def __init__(self, alpha, sigma, upper_bound=None):
+        self.alpha = alpha
+        self.sigma = sigma
+        self.upper_bound = upper_bound
+
+
+class SquaredL2Norm(LegendreFunction):
+    """h(x) = (1/2)||x||_2^2 (accbpg/functions.py:738-759), composed from the vector kernels."""
+
+    def __call__(self, x):
+        xd, _ = to_dev(x)
+        return 0.5 * vec_dot(xd, xd)
+
+    def gradient(self, x):
+        return x
+
+    def divergence(self, x, y):
+        assert x.shape == y.shape, "SquaredL2Norm: x and y not same shape."
+        xd, _ = to_dev(x)
+        yd, _ = to_dev(y)
+        xy = vec_axpby(1.0, xd, -1.0, yd)
+        return 0.5 * vec_dot(xy, xy)
+
+    def prox_map(self, g, L):
+        assert L > 0, "SquaredL2Norm: L should be positive."
+        gd, was_np = to_dev(g)
+        return from_dev(vec_axpby(-(1 / L), gd, 0.0, gd), was_np)
+
+    def div_prox_map(self, y, g, L):
+        assert y.shape == g.shape and L > 0, "Vectors y and g not same shape."
+        yd, was_np = to_dev(y)
+        gd, _ = to_dev(g)
+        return from_dev(vec_axpby(1.0, yd, -(1 / L), gd), was_np)
+
+
 # ------------------------------------------------------------------ vector helpers for the solver loops
 def vec_axpby(a, x, b, z):
     """a*x + b*z with NumPy's rounding (two products, one sum)."""
@@ -824,6 +1017,17 @@ def shannon_ls_terms(g, x, y, z=None, z1=None, delta=1e-20):
                                                  float(delta), out, _ptr(ws), _stream())
     _lib.check(rc, "accbpg_shannon_ls_terms", "Some entries are negative.")
     return np.float64(out[0]), np.float64(out[1]), np.float64(out[2])
+
+
+def quartic_ls_terms(g, x, y, z=None, z1=None):
+    """(<g,x-y>, ||x||^2, ||y||^2, <y,x-y>, ||z||^2, ||z1||^2, <z1,z-z1>) in one streaming pass and one readback."""
+    out = (C.c_double * 7)()
+    with torch.cuda.device(x.device):
+        ws = _Workspace.get(x.numel(), x.device)
+        rc = _lib.load().accbpg_quartic_ls_terms(_ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), out,
+                                                 _ptr(ws), _stream())
+    _lib.check(rc, "accbpg_quartic_ls_terms")
+    return tuple(out)
 
 
 def vec_min_sum(x):

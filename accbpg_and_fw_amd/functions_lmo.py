@@ -1,12 +1,16 @@
-"""Linear minimisation oracle for the simplex (accbpg/functions_lmo.py:137-160): the vertex that
-minimises <g, s>, returned with 1e-15 in every other entry as the reference does (so that Burg
-divergences from it stay finite)."""
+"""Linear minimisation oracles (accbpg/functions_lmo.py): the simplex (:137-160), whose vertex that minimises <g, s>
+is returned with 1e-15 in every other entry as the reference does (so that Burg divergences from it stay finite),
+and the l2 and l-infinity balls (:16-51, :106-134) for vector or n x r matrix gradients.  NumPy in, NumPy out;
+CUDA tensor in, CUDA tensor out."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
 
-from .functions import from_dev, to_dev, vec_argminmax, vec_vertex
+from . import _lib
+from .functions import _Workspace, _ptr, _stream, from_dev, to_dev, vec_argminmax, vec_dot, vec_vertex
 
 
 def lmo_simplex(radius=1):
@@ -17,3 +21,73 @@ def lmo_simplex(radius=1):
         imin, _, _, _ = vec_argminmax(gd)
         return from_dev(vec_vertex(imin, radius, 1e-15, gd.numel(), gd.device), was_np)
     return vertex
+
+
+class _Center:
+    """The centre of a ball as the kernels take it: (kind 0, scalar) for None or a scalar, (kind 1, device array
+    broadcast to the gradient's shape) otherwise; the device copy is made once per shape and device."""
+
+    def __init__(self, center):
+        self.center = center
+        self.scalar = center is None or np.ndim(center) == 0
+        self._cache = {}
+
+    def args(self, gd):
+        if self.scalar:
+            return 0, None, 0.0 if self.center is None else float(self.center)
+        key = (tuple(gd.shape), gd.device)
+        cd = self._cache.get(key)
+        if cd is None:
+            if isinstance(self.center, torch.Tensor):
+                cd = torch.broadcast_to(self.center.to(device=gd.device, dtype=torch.float64), gd.shape).contiguous()
+            else:
+                cd = torch.from_numpy(np.array(
+                    np.broadcast_to(np.asarray(self.center, dtype=np.float64), tuple(gd.shape)))).to(gd.device)
+            self._cache = {key: cd}
+        return 1, cd, 0.0
+
+    def full(self, gd):
+        kind, cd, val = self.args(gd)
+        return cd.clone() if kind == 1 else torch.full(gd.shape, val, dtype=torch.float64, device=gd.device)
+
+
+def lmo_l2_ball(radius, center=None):
+    """Returns g -> s = c - radius*g/||g||_F, the minimiser of <g, s> over {||s - c|| <= radius}; the centre itself
+    when ||g|| < 1e-10.  Asserts | ||s - c|| - radius | <= 1e-10 with the norm taken in the same launch."""
+    cen = _Center(center)
+
+    def f(g):
+        gd, was_np = to_dev(g)
+        g_norm = np.sqrt(np.float64(vec_dot(gd, gd)))
+        if g_norm < 1e-10:
+            return from_dev(cen.full(gd), was_np)
+        kind, cd, val = cen.args(gd)
+        n = gd.numel()
+        out = torch.empty_like(gd)
+        dist = C.c_double(0.0)
+        with torch.cuda.device(gd.device):
+            ws = _Workspace.get(n, gd.device)
+            rc = _lib.load().accbpg_lmo_l2_ball(_ptr(gd), kind, _ptr(cd), val, float(radius), float(g_norm), n,
+                                                _ptr(out), C.byref(dist), _ptr(ws), _stream())
+        _lib.check(rc, "accbpg_lmo_l2_ball", "Solution does not lie on ball boundary")
+        return from_dev(out, was_np)
+
+    return lambda g: f(g)
+
+
+def lmo_linf_ball(radius, center=None):
+    """Returns g -> s = c - radius*sign(g) (sign(0) = 0), a vertex of {||s - c||_inf <= radius}.  The centre may be
+    None, a scalar or an array of the gradient's shape."""
+    cen = _Center(center)
+
+    def f(g):
+        gd, was_np = to_dev(g)
+        kind, cd, val = cen.args(gd)
+        out = torch.empty_like(gd)
+        with torch.cuda.device(gd.device):
+            rc = _lib.load().accbpg_lmo_linf_ball(_ptr(gd), kind, _ptr(cd), val, float(radius), gd.numel(), _ptr(out),
+                                                  _stream())
+        _lib.check(rc, "accbpg_lmo_linf_ball")
+        return from_dev(out, was_np)
+
+    return lambda g: f(g)

@@ -337,6 +337,51 @@ int accbpg_shannon_ls_terms(const double* g_dev, const double* x_dev, const doub
 int accbpg_shannon_divergence(const double* x_dev, const double* y_dev, int64_t n, double delta, double* out_host,
                               double* ws_dev, void* stream);
 
+/* ---- Symmetric NMF: f(X) = 0.5*||M - X X^T||_F^2 with quartic kernels and ball LMOs --------------------- */
+
+typedef struct accbpg_symnmf accbpg_symnmf;
+
+/* Replaces FrobeniusSymLoss.__init__ (accbpg/functions.py:913-920).  M_dev: n x n symmetric, row-major, leading
+ * dimension ldm >= n (any base alignment), owned by the caller and borrowed for the handle's lifetime; r: columns of
+ * the iterates X (n x r, row-major, contiguous); m_norm: ||M||_F as the caller computed it (the value's t1 term). */
+int accbpg_symnmf_create(const double* M_dev, int64_t n, int64_t ldm, int64_t r, double m_norm, void* stream,
+                         accbpg_symnmf** out);
+int accbpg_symnmf_destroy(accbpg_symnmf* h);
+int accbpg_symnmf_set_stream(accbpg_symnmf* h, void* stream);
+
+/* FrobeniusSymLoss.func_grad without noise (accbpg/functions.py:958-976): flag 0 -> *f_host = 0.5*(m_norm^2 +
+ * ||X^T X||_F^2) - <X, M X>; flag 1 -> g_dev (n x r) = 2*X(X^T X) - 2*M X; flag 2 -> both.  One fp64 MFMA pass over
+ * M per call.  Synchronises the stream when a value is returned. */
+int accbpg_symnmf_func_grad(accbpg_symnmf* h, const double* X_dev, int flag, double* f_host, double* g_dev);
+
+/* Launch plan of the handle: out4 <- {k pieces of the M X product, rows per piece, wide tile (r > 64), row chunks of
+ * X^T X}. */
+int accbpg_symnmf_plan(accbpg_symnmf* h, int64_t* out4);
+
+/* First stage of SumOf2nd4thPowers(PositiveOrthant).div_prox_map (accbpg/functions.py:546-577): out_dev <- z*y -
+ * invL*g, clipped to [0, upper_bound] when clip == 1 (pass +inf for no upper bound); *ssq_host <- ||out||^2.  The
+ * caller solves the cubic and divides (accbpg_vec_div_scalar).  ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_quartic_prox_stage(const double* y_dev, const double* g_dev, double z, double invL, int clip,
+                              double upper_bound, int64_t n, double* out_dev, double* ssq_host, double* ws_dev,
+                              void* stream);
+
+/* One streaming pass, one readback: out7_host <- { <g,x-y>, ||x||^2, ||y||^2, <y,x-y>, ||z||^2, ||z1||^2,
+ * <z1,z-z1> } (g NULL: 0; z and z1 NULL together: zeros).  SumOf2nd4thPowers.divergence (:518-521) is
+ * h(x) - (h(y) + (sigma + alpha*||y||^2) <y, x-y>). */
+int accbpg_quartic_ls_terms(const double* g_dev, const double* x_dev, const double* y_dev, const double* z_dev,
+                            const double* z1_dev, int64_t n, double* out7_host, double* ws_dev, void* stream);
+
+/* lmo_l2_ball (accbpg/functions_lmo.py:16-51) for ||g|| = gnorm >= 1e-10: out_dev <- c - (radius*g)/gnorm with c =
+ * center_val (center_kind 0) or center_dev (center_kind 1, same length as g); *dist_host <- ||out - c||.  Returns
+ * ACCBPG_ERR_ASSERT when | ||out - c|| - radius | > 1e-10.  ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_lmo_l2_ball(const double* g_dev, int center_kind, const double* center_dev, double center_val,
+                       double radius, double gnorm, int64_t n, double* out_dev, double* dist_host, double* ws_dev,
+                       void* stream);
+
+/* lmo_linf_ball (accbpg/functions_lmo.py:106-134): out_dev <- c - radius*sign(g), sign(0) = 0; c as above. */
+int accbpg_lmo_linf_ball(const double* g_dev, int center_kind, const double* center_dev, double center_val,
+                         double radius, int64_t n, double* out_dev, void* stream);
+
 /* Closed-form Burg-entropy prox maps on x > 0.  kind 0: BurgEntropy.prox_map L/g (accbpg/functions.py:255-262);
  * kind 1: BurgEntropyL1.prox_map L/(lamda+g) (:290-298); kind 2: BurgEntropyL2.prox_map (:316-323).  With
  * y_dev != NULL the argument is g - L*(-1/y) first, i.e. BurgEntropy.div_prox_map (:264-271).

@@ -13,14 +13,15 @@ from .functions import (RSmoothFunction, DOptimalObj, PoissonRegression, KLdivRe
                         BurgEntropy, BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, ShannonEntropy,
                         ShannonEntropyL1, ShannonEntropySimplex, FrobeniusSymLoss, SumOf2nd4thPowers,
                         SumOf2nd4thPowersPositiveOrthant, SquaredL2Norm)
-from .algorithms import BPG, ABPG, ABPG_gain, ABPG_expo, ABDA, solve_theta
+from .algorithms import BPG, ABPG, ABPG_gain, ABPG_expo, ABDA, AIBM, AdaptFGM, UniversalGM, solve_theta
 from .algorithms_fw import FW_alg_div_step, FW_alg_descent_step
-from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball
+from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball, lmo_l2_ball_positive_orthant
 from .D_opt_alg import D_opt_FW, D_opt_FW_away
 from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, Poisson_regrL1, Poisson_regrL2,
                            KL_nonneg_regr, FrobeniusSymLossExL2Ball, FrobeniusSymLossExLInfBall,
-                           FrobeniusSymLossResMeasEx)
-from .utils import load_libsvm_file
+                           FrobeniusSymLossResMeasEx, Poisson_regr_simplex, Poisson_regr_simplex_acc)
+from .utils import (load_libsvm_file, random_point_on_simplex, edge_point_on_simplex, get_random_float,
+                    get_random_vector)
 from .batched import DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, solve_batch, solve_instances
 
 __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunction", "BurgEntropy",
@@ -30,5 +31,7 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "D_opt_FW", "D_opt_FW_away", "D_opt_design", "D_opt_libsvm", "D_opt_KYinit", "load_libsvm_file",
            "FrobeniusSymLoss", "SumOf2nd4thPowers", "SumOf2nd4thPowersPositiveOrthant", "SquaredL2Norm",
            "FW_alg_descent_step", "lmo_l2_ball", "lmo_linf_ball", "FrobeniusSymLossExL2Ball",
-           "FrobeniusSymLossExLInfBall", "FrobeniusSymLossResMeasEx"]
+           "FrobeniusSymLossExLInfBall", "FrobeniusSymLossResMeasEx", "AIBM", "AdaptFGM", "UniversalGM",
+           "Poisson_regr_simplex", "Poisson_regr_simplex_acc", "lmo_l2_ball_positive_orthant",
+           "random_point_on_simplex", "edge_point_on_simplex", "get_random_float", "get_random_vector"]
 __version__ = "0.1.0"

@@ -112,6 +112,11 @@ _SIGS = {
     "accbpg_lmo_linf_ball": (C.c_int, [_P, C.c_int, _P, C.c_double, C.c_double, C.c_int64, _P, _P]),
     "accbpg_burg_reg_div_prox": (C.c_int, [C.c_int, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P]),
     "accbpg_vec_dot": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_double), _P, _P]),
+    "accbpg_combine_ls_terms": (C.c_int, [C.c_int, C.c_double, _P, C.c_double, _P, C.c_double, _P, _P, C.c_int64, _P,
+                                          C.POINTER(C.c_double), _P, _P]),
+    "accbpg_burg_simplex_prox_acc": (C.c_int, [_P, C.c_double, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P,
+                                               C.POINTER(C.c_int), _P]),
+    "accbpg_lmo_l2_ball_pos": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int64, _P, C.POINTER(C.c_double), _P, _P]),
     "accbpg_dopt_profile_enable": (C.c_int, [_P, C.c_int]),
     "accbpg_dopt_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "accbpg_dopt_profile_reset": (C.c_int, [_P]),

@@ -1,6 +1,6 @@
-"""Outer loops of BPG / ABPG / ABPG_gain with the reference's signatures, defaults,
-return tuples, print tables and quirks (accbpg/algorithms.py:11-180, 295-420), running
-on device vectors.  The host keeps the iteration and every scalar decision; all
+"""Outer loops of BPG / ABPG / ABPG_gain / ABPG_expo / ABDA and of the inexact-oracle accelerated
+methods AIBM / AdaptFGM / UniversalGM with the reference's signatures, defaults, return tuples,
+print tables and quirks (accbpg/algorithms.py:11-514, 593-777), running on device vectors.  The host keeps the iteration and every scalar decision; all
 length-n and matrix work goes through libaccbpg_hip.so via the f / h objects of
 ``functions.py`` and the fused vector helpers there.
 
@@ -13,13 +13,16 @@ the default) -- see ``_stamp``.
 """
 from __future__ import annotations
 
+import math
 import time
 
 import numpy as np
 import torch
 
-from .functions import (BurgEntropy, ShannonEntropy, SumOf2nd4thPowers, from_dev, ls_terms, shannon_ls_terms,
-                        to_dev, vec_axpby, vec_div_scalar, vec_dot_diff)
+from .functions import (BurgEntropy, BurgEntropySimplex, ShannonEntropy, SquaredL2Norm, SumOf2nd4thPowers,
+                        combine_ls_terms, from_dev, ls_terms, shannon_ls_terms, to_dev, vec_axpby, vec_div_scalar,
+                        vec_dot_diff)
+from .utils import get_random_float
 
 
 def _divergences(h, g, x, y, z, z_prev):
@@ -509,3 +512,257 @@ def ABDA_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, theta_eq=True,
         yield k
 
     return from_dev(x, as_numpy), F[0:k + 1], G[0:k + 1], T[0:k + 1]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Inexact-oracle accelerated methods (accbpg/algorithms.py:593-777).  One line-search try is a handful of length-n
+# passes around two or three evaluations of f; at the drivers' size those cost launches and read-backs, not
+# bandwidth, so the extrapolated point and the two numbers of the test come from one kernel (combine_ls_terms)
+# and AIBM's accumulated-gradient prox from another (BurgEntropySimplex.prox_map_acc).  FUSED_INEXACT = False
+# composes the same loops from the package's public kernels (same elementwise rounding); tools/inexact_rate.py
+# times both.  Where the reference evaluates f.gradient(x) and f(x) at one point, func_grad(x, 2) gives both.
+# ---------------------------------------------------------------------------------------------------------------
+FUSED_INEXACT = True
+
+
+def _fusable(h):
+    return FUSED_INEXACT and isinstance(h, (BurgEntropy, SquaredL2Norm))
+
+
+def _combine(h, a, u, b, v, c, g=None, x=None):
+    """(w, <g, w-x>, D_h(w, x)) with w = (a*u + b*v)/c; the two numbers only when x is given."""
+    if _fusable(h):
+        return combine_ls_terms(h, a, u, b, v, c, g, x)
+    w = vec_axpby(a, u, b, v)
+    if c != 1:
+        w = vec_div_scalar(w, c)
+    if x is None:
+        return w, None, None
+    lin, dist, _ = _divergences(h, g, w, x, None, None)
+    return w, lin, dist
+
+
+def _doubled(L):
+    """L*2 of a failed try.  The reference's AIBM and AdaptFGM have no way out once L has doubled to infinity (their
+    test is false from then on); here all three methods stop as its UniversalGM does (:759-760)."""
+    L = L * 2
+    if L is None or not math.isfinite(L):
+        raise ValueError("L cannot be None or infinity")
+    return L
+
+
+def AIBM(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, verbose=True, noise=0, verbskip=1):
+    """Adaptive intermediate Bregman method with an inexact oracle (accbpg/algorithms.py:593-658).
+    Returns (x, F, G, T).
+
+    Quirks kept: x0 gives the length only, the run starts from ones * h.prox_map(zeros, 1) (:604); the first search
+    tests with + epsilon + delta (:611), the others with + delta; G[0] = L and the rest of G stays zero; the stopping
+    threshold is 1e-9, not epsilon (:652); a rejected try adds alpha*grad to xi_grad and subtracts it again (:630,
+    :636), which does not restore its bits; the returned x is the last extrapolated point, where F[k] was taken.
+    delta = get_random_float(noise) is drawn once before the first search and once per k."""
+    return _drain(AIBM_steps(f, h, L, x0, gamma, maxitrs, epsilon, verbose, noise, verbskip))
+
+
+def AIBM_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, verbose=True, noise=0, verbskip=1):
+    """Generator form of AIBM: yields k after each outer iteration, returns AIBM's tuple."""
+    if verbose:
+        print("\nAIBM method for min_{x in C} F(x) = f(x) + Psi(x)")
+        print("     k      F(x)       L       time")
+
+    t_start = time.time()
+    F = np.zeros(maxitrs)
+    G = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+    p = 2
+
+    x0d, as_numpy = to_dev(x0)
+    x = z = h.prox_map(torch.zeros(x0d.shape[0], dtype=torch.float64, device=x0d.device), 1)   # :604 (ones * it is exact)
+
+    delta = get_random_float(noise)
+    fx, g = f.func_grad(x, flag=2)
+    y = h.prox_map(g, 1)                                        # :610-611 do not depend on L: evaluated once
+    lin, dist, _ = _divergences(h, g, y, x, None, None)
+    fy = f(y)
+    while True:
+        alpha = 1 / L
+        if fy <= fx + lin + L * dist + epsilon + delta:
+            break
+        L = _doubled(L)
+
+    B = A = alpha
+    xi_grad = vec_axpby(alpha, g, 0.0, g)                       # :616 alpha * f.gradient(x), the gradient held already
+
+    F[0] = fx + h.extra_Psi(x)
+    G[0] = L
+    T[0] = time.time() - t_start
+
+    acc_prox = FUSED_INEXACT and isinstance(h, BurgEntropySimplex)
+    k = 0
+    for k in range(1, maxitrs):
+        L /= 2
+        delta = get_random_float(noise)
+        while True:
+            alpha = (1 / L) * (1 + k / (2 * p)) ** ((p - 1) * (gamma - 1))
+            B = (L * alpha ** gamma) ** (1 / (gamma - 1))
+            x = vec_axpby(alpha / B, z, 1 - alpha / B, y)       # :628
+            fx, grad_x = f.func_grad(x, flag=2)                 # :629 and :633
+            if acc_prox:
+                xi_grad, z_k = h.prox_map_acc(xi_grad, alpha, grad_x)      # :630-631
+            else:
+                xi_grad = vec_axpby(1.0, xi_grad, alpha, grad_x)
+                z_k = h.prox_map(xi_grad, 1)
+            w, lin, dist = _combine(h, alpha / B, z_k, 1 - alpha / B, y, 1, grad_x, x)   # :632 and the terms of :634
+            if f(w) <= fx + lin + L * dist + delta:
+                break
+            xi_grad = vec_axpby(1.0, xi_grad, -alpha, grad_x)   # :636
+            L = _doubled(L)
+
+        F[k] = fx + h.extra_Psi(x)
+        T[k] = time.time() - t_start
+
+        A += alpha
+        y = vec_axpby(B / A, w, 1 - B / A, y)                   # :644
+        z = z_k
+
+        if verbose and k % verbskip == 0:
+            print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:6.1f}".format(k, F[k], L, T[k]))
+
+        if abs(F[k] - F[k - 1]) < 1e-9:                         # :652
+            break
+        yield k
+
+    return from_dev(x, as_numpy), F[0:k + 1], G[0:k + 1], T[0:k + 1]
+
+
+def AdaptFGM(f, h, L, x0, maxitrs, epsilon=1e-14, verbose=True, noise=0, verbskip=1):
+    """Adaptive fast gradient method with an inexact oracle (accbpg/algorithms.py:661-714).  Returns (x_k, F, G, T).
+
+    Quirks kept: x_k, y and u_k all start at ones(x0.shape), off the simplex, and F[0] is taken there (:671-676);
+    f(x_k), not f(y), enters every try (:691-692); the linear term is sum(g_y*(x - y)).  f(x_k) is the value held from
+    the evaluation that accepted x_k (the same number)."""
+    return _drain(AdaptFGM_steps(f, h, L, x0, maxitrs, epsilon, verbose, noise, verbskip))
+
+
+def AdaptFGM_steps(f, h, L, x0, maxitrs, epsilon=1e-14, verbose=True, noise=0, verbskip=1):
+    """Generator form of AdaptFGM: yields k after each outer iteration, returns AdaptFGM's tuple."""
+    if verbose:
+        print("\nAdaptFGM method for min_{x in C} F(x) = f(x) + Psi(x)")
+        print("     k      F(x)       L       time")
+
+    t_start = time.time()
+    F = np.zeros(maxitrs)
+    G = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+
+    x0d, as_numpy = to_dev(x0)
+    x_k = u_k = torch.ones(x0d.shape, dtype=torch.float64, device=x0d.device)
+    A_k = 0
+
+    fxk, g = f.func_grad(x_k, flag=2)
+
+    F[0] = fxk + h.extra_Psi(x_k)
+    G[0] = L
+    T[0] = time.time() - t_start
+
+    k = 0
+    for k in range(1, maxitrs):
+        L /= 2
+        delta = get_random_float(noise)
+        while True:
+            alpha = (1 + math.sqrt(1 + 4 * L * A_k)) / (2 * L)
+            A = L * alpha ** 2
+            y, _, _ = _combine(h, alpha, u_k, A_k, x_k, A)      # :686
+            g_y = f.gradient(y)
+            u = h.div_prox_map(u_k, vec_axpby(alpha, g_y, 0.0, g_y), 1)
+            x, lin, dist = _combine(h, alpha, u, A_k, x_k, A, g_y, y)      # :689 and the terms of :692
+            fx = f(x)
+            if fx <= fxk + lin + L * dist + delta:
+                A_k = A
+                u_k = u
+                x_k = x
+                fxk = fx
+                break
+            L = _doubled(L)
+
+        F[k] = fxk + h.extra_Psi(x_k)
+        G[k] = L
+        T[k] = time.time() - t_start
+
+        if verbose and k % verbskip == 0:
+            print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:6.1f}".format(k, F[k], L, T[k]))
+
+        if abs(F[k] - F[k - 1]) < epsilon:
+            break
+        yield k
+
+    return from_dev(x_k, as_numpy), F[0:k + 1], G[0:k + 1], T[0:k + 1]
+
+
+def UniversalGM(f, h, L, x0, maxitrs, epsilon=1e-14, verbose=True, noise_level=0, verbskip=1):
+    """Universal gradient method with a noisy oracle (accbpg/algorithms.py:717-777).  Returns (x_k, F, G, T).
+
+    Quirks kept: x0 feeds F[0] only (the first y is u_k/(L*alpha) with u_k = ones, since A_k = 0); one scalar
+    noise = np.random.rand()*noise_level is drawn per k when noise_level > 0 and added to every component of the
+    gradient and to f(y)."""
+    return _drain(UniversalGM_steps(f, h, L, x0, maxitrs, epsilon, verbose, noise_level, verbskip))
+
+
+def UniversalGM_steps(f, h, L, x0, maxitrs, epsilon=1e-14, verbose=True, noise_level=0, verbskip=1):
+    """Generator form of UniversalGM: yields k after each outer iteration, returns UniversalGM's tuple."""
+    if verbose:
+        print("\nUniversalGM method for min_{x in C} F(x) = f(x) + Psi(x)")
+        print("     k      F(x)       L       time")
+
+    t_start = time.time()
+    F = np.zeros(maxitrs)
+    G = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+
+    x0d, as_numpy = to_dev(x0)
+    x_k = x0d.clone()
+    fxk = f(x_k)
+    F[0] = fxk + h.extra_Psi(x_k)
+    G[0] = L
+    T[0] = time.time() - t_start
+
+    A_k = 0
+    ones = torch.ones(x0d.shape, dtype=torch.float64, device=x0d.device)
+    u_k = ones
+
+    k = 0
+    for k in range(1, maxitrs):
+        noise = np.random.rand() * noise_level if noise_level > 0 else 0
+
+        L /= 2
+        while True:
+            alpha = (1 + math.sqrt(1 + 4 * L * A_k)) / (2 * L)
+            A = L * alpha ** 2
+            y, _, _ = _combine(h, alpha, u_k, A_k, x_k, A)      # :744
+            fy, g_y = f.func_grad(y, flag=2)                    # :745 and :750
+            if noise_level > 0:
+                g_y = vec_axpby(1.0, g_y, noise, ones)          # g_y += noise
+            u = h.div_prox_map(u_k, vec_axpby(alpha, g_y, 0.0, g_y), 1)
+            x, lin, dist = _combine(h, alpha, u, A_k, x_k, A, g_y, y)      # :748 and the terms of :753
+
+            fy += noise
+            fx = f(x)
+            if fx <= fy + lin + L * dist:
+                A_k = A
+                u_k = u
+                x_k = x
+                fxk = fx
+                break
+            L = _doubled(L)
+
+        F[k] = fxk + h.extra_Psi(x_k)
+        G[k] = L
+        T[k] = time.time() - t_start
+
+        if verbose and k % verbskip == 0:
+            print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:6.1f}".format(k, F[k], L, T[k]))
+
+        if abs(F[k] - F[k - 1]) < epsilon:
+            break
+        yield k
+
+    return from_dev(x_k, as_numpy), F[0:k + 1], G[0:k + 1], T[0:k + 1]

@@ -1,4 +1,5 @@
-"""Problem factories (accbpg/applications.py): D-optimal design, Poisson and KL regression, and symmetric NMF."""
+"""Problem factories (accbpg/applications.py): D-optimal design, Poisson and KL regression (on the orthant and on the
+simplex), and symmetric NMF."""
 from __future__ import annotations
 
 import numpy as np
@@ -6,7 +7,7 @@ import numpy as np
 from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, FrobeniusSymLoss,
                         KLdivRegression, PoissonRegression, ShannonEntropyL1, SquaredL2Norm, SumOf2nd4thPowers,
                         SumOf2nd4thPowersPositiveOrthant, vec_argminmax)
-from .utils import load_libsvm_file
+from .utils import edge_point_on_simplex, load_libsvm_file, random_point_on_simplex
 
 
 def D_opt_libsvm(filename):
@@ -118,6 +119,67 @@ def KL_nonneg_regr(m, n, noise=0.01, lamdaL1=0, randseed=-1, normalizeA=True):
     b = np.dot(A, x) + noise * (np.random.rand(m) - 0.5)
     assert b.min() > 0, "need b > 0 for nonnegative regression."
     return KLdivRegression(A, b), ShannonEntropyL1(lamdaL1), max(A.sum(axis=0)), 0.5 * np.ones(n)
+
+
+def _simplex_instance(m, n, noise, normalizeA, solution):
+    """(A, b) with b = A solution + noise*rand(m) (accbpg/applications.py:212-217, 250-255): the legacy global RNG drawn
+    in the order A, noise, on the host like the reference's."""
+    A = np.random.rand(m, n)
+    if normalizeA:
+        A = A / A.sum(axis=0)
+    b = np.dot(A, solution) + noise * (np.random.rand(m))
+    assert b.min() > 0, "need b > 0 for nonnegative regression."
+    return A, b
+
+
+def Poisson_regr_simplex_acc(m, n, noise=0.01, normalizeA=True):
+    """minimize_{x in simplex} D_KL(b, Ax) for the inexact-oracle accelerated methods (accbpg/applications.py:209-224).
+    Draws x0, the solution, A and the noise in that order.  Returns f, [BurgEntropySimplex(eps=1e-7), SquaredL2Norm()],
+    L = ||b||_1, x0 (a random point of the simplex)."""
+    x0 = random_point_on_simplex(n, center=False)
+    solution = random_point_on_simplex(n, center=False)
+    A, b = _simplex_instance(m, n, noise, normalizeA, solution)
+    f = PoissonRegression(A, b)
+    L = np.abs(b).sum()
+    h = BurgEntropySimplex(eps=1e-7)
+    h_euklid = SquaredL2Norm()
+    return f, [h, h_euklid], L, x0
+
+
+def Poisson_regr_simplex(m, n, noise=0.01, normalizeA=True):
+    """Four instances of minimize_{x in simplex} D_KL(b, Ax) that differ in where x0 and the solution lie
+    (accbpg/applications.py:227-295).  Returns h = BurgEntropySimplex() and a dict placement -> (f, L = sum(b), solution,
+    x0), generated in the reference's order: for each placement x0, solution, then A and the noise."""
+    key1 = 'x0_center_sol_center'
+    key2 = 'x0_edge_sol_edge'
+    key3 = 'x0_edge_sol_center'
+    key4 = 'x0_center_sol_edge'
+
+    def generate_problem(solution_and_x0):
+        solution, x0 = solution_and_x0
+        A, b = _simplex_instance(m, n, noise, normalizeA, solution)
+        return PoissonRegression(A, b), b.sum(), solution, x0
+
+    def generate_sol_and_x0(place):
+        if place == key1:
+            x0 = random_point_on_simplex(n, center=True)
+            solution = random_point_on_simplex(n)
+        elif place == key2:
+            x0 = edge_point_on_simplex(np.random.randint(n), n)
+            solution = edge_point_on_simplex(np.random.randint(n), n)
+        elif place == key3:
+            x0 = edge_point_on_simplex(np.random.randint(n), n)
+            solution = random_point_on_simplex(n, center=True)
+        elif place == key4:
+            x0 = random_point_on_simplex(n, center=True)
+            solution = edge_point_on_simplex(np.random.randint(n), n)
+        else:
+            assert 0, 'Place had not been defined'
+        return solution, x0
+
+    points_positions = {key: generate_problem(generate_sol_and_x0(key)) for key in (key1, key2, key3, key4)}
+    h = BurgEntropySimplex()
+    return h, points_positions
 
 
 def _symnmf_l2_instance(n, r, ball_center, radius=1.0, on_boundary=True):

@@ -57,11 +57,14 @@ __device__ __forceinline__ double block_min_bcast(double v, double* sh) {
 
 // Burg simplex prox, functions.py:336-356 (and :264-271 when y != NULL).
 // EPT > 0: gg lives in registers (n <= PB*EPT); EPT == 0: gg is kept in `ggbuf` and re-read.
-template <int EPT>
+// ACC: the argument is xi + alpha*g, formed on load (one product, one sum) and stored to xi_out -- the
+// accumulated gradient of AIBM (algorithms.py:630-631); everything behind the load is the same code.
+template <int EPT, bool ACC = false>
 __device__ __forceinline__ void burg_prox_body(const double* __restrict__ y, const double* __restrict__ g,
                                                double L, double eps, int64_t n, double* __restrict__ xout,
                                                double* __restrict__ ggbuf, int* __restrict__ info,
-                                               int* __restrict__ flags) {
+                                               int* __restrict__ flags, const double* __restrict__ xi = nullptr,
+                                               double alpha = 0.0, double* __restrict__ xi_out = nullptr) {
     __shared__ double sh[PB / 64];
     const int tid = threadIdx.x;
     constexpr int R = EPT > 0 ? EPT : 1;
@@ -72,6 +75,11 @@ __device__ __forceinline__ void burg_prox_body(const double* __restrict__ y, con
 
     auto make_gg = [&](int64_t i) -> double {
         double a = g[i];
+        if constexpr (ACC) {
+            const double t = alpha * a;       // alpha * grad_x     algorithms.py:630
+            a = xi[i] + t;                    // xi_grad += ...
+            xi_out[i] = a;
+        }
         if (y != nullptr) {
             const double yi = y[i];
             if (!(yi > 0.0)) bad = true;
@@ -163,6 +171,14 @@ __global__ __launch_bounds__(PB) void burg_prox_kernel(const double* __restrict_
                                                       double* __restrict__ ggbuf, int* __restrict__ info,
                                                       int* __restrict__ flags) {
     burg_prox_body<EPT>(y, g, L, eps, n, xout, ggbuf, info, flags);
+}
+// BurgEntropySimplex.prox_map(xi + alpha*g, L) with the sum stored to xi_out (n <= PB*EPT)
+template <int EPT>
+__global__ __launch_bounds__(PB) void burg_prox_acc_kernel(const double* __restrict__ xi, double alpha,
+                                                          const double* __restrict__ g, double L, double eps, int64_t n,
+                                                          double* __restrict__ xi_out, double* __restrict__ xout,
+                                                          int* __restrict__ info, int* __restrict__ flags) {
+    burg_prox_body<EPT, true>(nullptr, g, L, eps, n, xout, nullptr, info, flags, xi, alpha, xi_out);
 }
 // the prox of every active instance of a batch in one launch: a workgroup per instance (row `instance` of the K x n
 // arrays), its own constant L, its own status words
@@ -723,6 +739,35 @@ extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g
     ACC_HIP(hipStreamSynchronize(s));
     if (info_host) { info_host[0] = pin_i[4]; info_host[1] = pin_i[5]; }
     if (pin_i[FLAG_NONPOS]) return ACCBPG_ERR_ASSERT;         // y.min() > 0, functions.py:270
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_burg_simplex_prox_acc(const double* xi_dev, double alpha, const double* g_dev, double L, double eps,
+                                            int64_t n, double* xi_out_dev, double* x_out_dev, double* ws_dev,
+                                            int* info_host, void* stream) {
+    if (!xi_dev || !g_dev || !xi_out_dev || !x_out_dev || n <= 0 || !ws_dev) return ACCBPG_ERR_ARG;
+    if (xi_out_dev == xi_dev || xi_out_dev == g_dev || x_out_dev == xi_out_dev) return ACCBPG_ERR_ARG;
+    if (!(L > 0.0)) return ACCBPG_ERR_ASSERT;                 // functions.py:340
+    hipStream_t s = (hipStream_t)stream;
+    if (n > (int64_t)PB * 32) {
+        // long vectors: the sum in a pass of its own (1.0*xi is exact), then the multi-workgroup prox as it is
+        ACC_TRY(accbpg_vec_axpby(1.0, xi_dev, alpha, g_dev, n, xi_out_dev, stream));
+        return accbpg_burg_simplex_div_prox(nullptr, xi_out_dev, L, eps, n, x_out_dev, ws_dev, info_host, stream);
+    }
+    ACC_TRY(ensure_scratch());
+    int* g_info = g_flags + 4;
+    if (n <= (int64_t)PB * 2)
+        burg_prox_acc_kernel<2><<<1, PB, 0, s>>>(xi_dev, alpha, g_dev, L, eps, n, xi_out_dev, x_out_dev, g_info, g_flags);
+    else if (n <= (int64_t)PB * 8)
+        burg_prox_acc_kernel<8><<<1, PB, 0, s>>>(xi_dev, alpha, g_dev, L, eps, n, xi_out_dev, x_out_dev, g_info, g_flags);
+    else
+        burg_prox_acc_kernel<32><<<1, PB, 0, s>>>(xi_dev, alpha, g_dev, L, eps, n, xi_out_dev, x_out_dev, g_info, g_flags);
+    ACC_HIP(hipGetLastError());
+    if (!info_host) return ACCBPG_OK;                         // no y, so no flag can be raised: nothing to wait for
+    int* pin_i = reinterpret_cast<int*>(g_pin);
+    ACC_HIP(hipMemcpyAsync(pin_i, g_flags, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
+    ACC_HIP(hipStreamSynchronize(s));
+    info_host[0] = pin_i[4]; info_host[1] = pin_i[5];
     return ACCBPG_OK;
 }
 

@@ -765,6 +765,21 @@ class BurgEntropySimplex(BurgEntropy):
         return self._prox(y, g, L)
 
 
+    def prox_map_acc(self, xi, alpha, g):
+        """(xi + alpha*g, prox_map(xi + alpha*g, 1)) in one call on device vectors: AIBM's
+        ``xi_grad += alpha*grad_x; z_k = h.prox_map(xi_grad, 1)`` (accbpg/algorithms.py:630-631).  The prox is the one
+        of ``prox_map``, bit for bit; nothing is read back."""
+        n = xi.numel()
+        xi_out = torch.empty_like(xi)
+        out = torch.empty_like(xi)
+        with torch.cuda.device(xi.device):
+            ws = _Workspace.get(n, xi.device)
+            rc = _lib.load().accbpg_burg_simplex_prox_acc(_ptr(xi), float(alpha), _ptr(g), 1.0, float(self.eps), n,
+                                                          _ptr(xi_out), _ptr(out), _ptr(ws), None, _stream())
+        _lib.check(rc, "accbpg_burg_simplex_prox_acc")
+        return xi_out, out
+
+
 class ShannonEntropy(LegendreFunction):
     """h(x) = sum x_i log x_i for x >= 0, h(0) = 0  (accbpg/functions.py:398-438).  ``delta`` guards the
     logarithms of the divergence at exact zeros."""
@@ -1006,6 +1021,23 @@ def ls_terms(g, x, y, z=None, z1=None):
     # an iterate that has stopped moving -- is then inf or nan with a warning, as in the reference, not an exception
     # (the stopping rule dzz < epsilon right behind it ends the run, accbpg/algorithms.py:155,174)
     return np.float64(out[0]), np.float64(out[1]), np.float64(out[2])
+
+
+def combine_ls_terms(h, a, u, b, v, c, g=None, x=None):
+    """w = (a*u + b*v)/c with NumPy's rounding, and (<g, w - x>, D_h(w, x)) from the same pass and one read-back when x
+    is given; h is this package's Burg entropy (any variant) or SquaredL2Norm.  Returns (w, lin, dist); lin and dist
+    are None without x."""
+    kind = 1 if isinstance(h, SquaredL2Norm) else 0
+    w = torch.empty_like(u)
+    out = (C.c_double * 2)(0.0, 0.0)
+    with torch.cuda.device(u.device):
+        ws = _Workspace.get(u.numel(), u.device) if x is not None else None
+        rc = _lib.load().accbpg_combine_ls_terms(kind, float(a), _ptr(u), float(b), _ptr(v), float(c), _ptr(g), _ptr(x),
+                                                 u.numel(), _ptr(w), out, _ptr(ws), _stream())
+    _lib.check(rc, "accbpg_combine_ls_terms", "Entries of x or y not positive.")
+    if x is None:
+        return w, None, None
+    return w, np.float64(out[0]), np.float64(out[1])
 
 
 def shannon_ls_terms(g, x, y, z=None, z1=None, delta=1e-20):

@@ -1,7 +1,7 @@
 """Linear minimisation oracles (accbpg/functions_lmo.py): the simplex (:137-160), whose vertex that minimises <g, s>
 is returned with 1e-15 in every other entry as the reference does (so that Burg divergences from it stay finite),
-and the l2 and l-infinity balls (:16-51, :106-134) for vector or n x r matrix gradients.  NumPy in, NumPy out;
-CUDA tensor in, CUDA tensor out."""
+the l2 and l-infinity balls (:16-51, :106-134) for vector or n x r matrix gradients, and the l2 ball cut by the
+(strictly) positive orthant (:54-102).  NumPy in, NumPy out; CUDA tensor in, CUDA tensor out."""
 from __future__ import annotations
 
 import ctypes as C
@@ -91,3 +91,37 @@ def lmo_linf_ball(radius, center=None):
         return from_dev(out, was_np)
 
     return lambda g: f(g)
+
+
+def lmo_l2_ball_positive_orthant(radius, center=None, epsilon=0.0):
+    """Returns g -> s = max(c + radius*d, epsilon) with d = -g/||g[g < 0]|| on the negative entries of g and 0
+    elsewhere: the minimiser of <g, s> over the l2 ball moved along the coordinates that pay, then lifted to
+    s >= epsilon.  A gradient with no negative entry gives max(c, epsilon) and, as in the reference, skips both
+    assertions (s >= epsilon, ||s - c|| <= radius + 1e-8).  The centre is None (zeros) or an array of the gradient's
+    shape.  The masked norm, the output and the two checked quantities come from the device with one read-back; g is
+    not copied to the host."""
+    cache = {}
+
+    def f(g):
+        gd, was_np = to_dev(g)
+        cd = None
+        if center is not None:
+            assert tuple(np.shape(center)) == tuple(gd.shape), "Shape mismatch between g and center"
+            key = (tuple(gd.shape), gd.device)
+            cd = cache.get(key)
+            if cd is None:
+                cd, _ = to_dev(center)
+                cd = cd.to(gd.device)
+                cache.clear()
+                cache[key] = cd
+        n = gd.numel()
+        out = torch.empty_like(gd)
+        info = (C.c_double * 3)()
+        with torch.cuda.device(gd.device):
+            ws = _Workspace.get(n, gd.device)
+            rc = _lib.load().accbpg_lmo_l2_ball_pos(_ptr(gd), _ptr(cd), float(radius), float(epsilon), n, _ptr(out), info,
+                                                    _ptr(ws), _stream())
+        _lib.check(rc, "accbpg_lmo_l2_ball_pos")
+        return from_dev(out, was_np)
+
+    return f

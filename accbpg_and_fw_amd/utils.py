@@ -1,5 +1,7 @@
-"""LIBSVM / svmlight text reader with the interface of accbpg/utils.py:22-95: returns
-(scipy.sparse.csr_matrix, labels).  Host-side; the matrix goes to the GPU when an objective is built on it.
+"""Host-side helpers of accbpg/utils.py: the LIBSVM / svmlight text reader (:22-95, returns
+(scipy.sparse.csr_matrix, labels); the matrix goes to the GPU when an objective is built on it) and the random
+points and inexactness levels of the simplex experiments (:252-295), which draw from NumPy's legacy global
+generator exactly as the reference does.
 
 The file is tokenised once and the index / value columns are converted, validated and assembled into CSR
 with array operations (no per-entry Python work), which is what the datasets this package is pointed at
@@ -69,3 +71,40 @@ def load_libsvm_file(filename, dtype=np.float64, n_features=None, zero_based="au
     X = sparse.csr_matrix((vals, ids, row_ptr), (len(records), n_features))
     X.sort_indices()
     return X, labels
+
+
+def random_point_on_simplex(n, radius=1, center=False):
+    """The centre ones(n)/n, or the gaps between n-1 sorted draws of uniform(0.01, radius) padded with 0 and radius
+    (accbpg/utils.py:252-268): one np.random.uniform(size=n-1) call, none for the centre."""
+    if center:
+        return np.ones(n) / n
+    cuts = np.random.uniform(low=0.01, high=radius, size=(n - 1,))
+    cuts.sort()
+    return np.diff(np.concatenate([[0], cuts, [radius]]))
+
+
+def edge_point_on_simplex(edge_index, n, radius=1, tol=1e-5):
+    """tol everywhere and radius - tol*(n-1) at edge_index (accbpg/utils.py:271-275)."""
+    x = np.zeros(n) + tol
+    x[edge_index] = radius - tol * (n - 1)
+    return x
+
+
+def get_random_float(var=1):
+    """var * np.random.random_sample(), or the integer 0 without a draw when var == 0 (accbpg/utils.py:278-285)."""
+    if var == 0:
+        return 0
+    assert var > 0, 'The range must be positive.'
+    val = var * np.random.random_sample()
+    assert val > 0
+    return val
+
+
+def get_random_vector(size, range=1):
+    """range * np.random.random_sample(size), or zeros without a draw when range == 0 (accbpg/utils.py:288-295)."""
+    if range == 0:
+        return np.zeros(size)
+    assert range > 0, 'The range must be positive.'
+    vec = range * np.random.random_sample(size=size)
+    assert vec.min() > 0
+    return vec

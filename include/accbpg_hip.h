@@ -394,6 +394,38 @@ int accbpg_burg_reg_div_prox(int kind, const double* y_dev, const double* g_dev,
 int accbpg_vec_dot(const double* x_dev, const double* y_dev, int64_t n, double* out_host, double* ws_dev,
                    void* stream);
 
+/* ---- inexact-oracle accelerated methods (AIBM, AdaptFGM, UniversalGM; accbpg/algorithms.py:593-777) ---- */
+
+/* One pass, one read-back: w_dev <- (a*u + b*v)/c with NumPy's rounding (two products, one sum, one division; no fused
+ * multiply-add), out2_host <- { <g, w - x>, D_h(w, x) } with h the Burg entropy (kind 0, accbpg/functions.py:253) or
+ * (1/2)||.||^2 (kind 1, :749-751).  c = 1 is AIBM's alpha/B*z + (1-alpha/B)*y (algorithms.py:628, :632); c = A is
+ * (alpha*u + A_k*x_k)/A of AdaptFGM and UniversalGM (:686-689, :744-748).  g_dev NULL: the inner product is 0.
+ * x_dev NULL: only w is written, nothing is read back (out2_host and ws_dev may be NULL).  ACCBPG_ERR_ASSERT (kind 0)
+ * when an entry of w or x is not positive.  w_dev must not alias an input.  Sums use a fixed tree.
+ * ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_combine_ls_terms(int kind, double a, const double* u_dev, double b, const double* v_dev, double c,
+                            const double* g_dev, const double* x_dev, int64_t n, double* w_dev, double* out2_host,
+                            double* ws_dev, void* stream);
+
+/* BurgEntropySimplex.prox_map of an accumulated gradient in one call: xi_out_dev <- xi + alpha*g (one product, one
+ * sum: AIBM's xi_grad += alpha*grad_x, algorithms.py:630) and x_out_dev <- prox_map(xi_out, L) (:631) with the
+ * algorithm of accbpg_burg_simplex_div_prox unchanged -- for a given xi_out the result is that entry's, bit for bit.
+ * Up to n = 32768 the sum is formed as the prox kernel loads its argument; longer vectors take a pass of their own
+ * in front of the multi-workgroup prox.  xi_out_dev must not alias an input.  info_host (optional) receives
+ * {bisection steps, Newton steps}; without it the call does not wait for the device. */
+int accbpg_burg_simplex_prox_acc(const double* xi_dev, double alpha, const double* g_dev, double L, double eps,
+                                 int64_t n, double* xi_out_dev, double* x_out_dev, double* ws_dev, int* info_host,
+                                 void* stream);
+
+/* lmo_l2_ball_positive_orthant (accbpg/functions_lmo.py:54-102): out_dev <- max(c + radius*d, epsilon) with
+ * d = -g/||g_neg|| where g < 0 and 0 elsewhere, ||g_neg|| the norm over the negative entries (fixed-tree sum);
+ * c = center_dev, or zeros when it is NULL.  With no negative entry out_dev <- max(c, epsilon) and nothing is asserted
+ * (:83-84).  info3_host <- { number of negative entries, ||out - c||, min(out) }.  ACCBPG_ERR_ASSERT where the
+ * reference asserts: min(out) < epsilon (:97), ||out - c|| > radius + 1e-8 (:98).  One read-back; g stays on the
+ * device.  ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_lmo_l2_ball_pos(const double* g_dev, const double* center_dev, double radius, double epsilon, int64_t n,
+                           double* out_dev, double* info3_host, double* ws_dev, void* stream);
+
 /* ---- diagnostics ---------------------------------------------------------------------- */
 
 /* Kernel time accounting for the roofline line of bench.py: accumulates HIP-event durations

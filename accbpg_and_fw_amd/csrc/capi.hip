@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include "internal.h"
+#include "reduce.hpp"
 
 namespace accbpg {
 
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(1024) void count_bad_kernel(const double* __restric
     __shared__ int sh[16];
     int c = 0;
     for (int64_t i = threadIdx.x; i < n; i += 1024) c += !(x[i] >= 0.0);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -4,6 +4,7 @@
 // u = Hv^T V, reads and rewrites the m x m inverse H for the rank-one update, and makes a few
 // passes over the length-n vectors.  Compiled with -ffp-contract=off (NumPy ufunc rounding).
 #include "internal.h"
+#include "reduce.hpp"
 
 namespace accbpg {
 
@@ -249,8 +250,7 @@ __global__ __launch_bounds__(FB) void fw_rank1_kernel(double* __restrict__ H, in
         __shared__ double qs[FB / 64];
         double q = 0.0;
         for (int64_t c = threadIdx.x; c < m; c += FB) q = fma(vp[c], hv[c], q);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off);
+        q = wave_sum(q);
         if ((threadIdx.x & 63) == 0) qs[threadIdx.x >> 6] = q;
         __syncthreads();
         if (threadIdx.x == 0) {

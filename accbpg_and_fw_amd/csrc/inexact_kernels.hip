@@ -13,39 +13,19 @@
 // vector that fits one block (n <= 1024) is reduced by the pass itself; longer ones take a second, one-block launch.
 // Compiled with -ffp-contract=off: every product, sum and quotient rounds once, as the NumPy ufuncs do.
 #include "internal.h"
+#include "reduce.hpp"
 
 namespace accbpg {
 
 namespace {
 
-constexpr int IK = 256;          // threads per block
+constexpr int IK = RED_THREADS;  // threads per block
 constexpr int IMAXBLK = 1024;    // 4 * IMAXBLK partials fit behind the n doubles of the vector workspace
 
-__device__ __forceinline__ double i_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-// minimum that keeps a NaN, as np.min does
-__device__ __forceinline__ double i_min_nan(double a, double b) { return (b < a || b != b) ? b : a; }
-__device__ __forceinline__ double i_wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = i_min_nan(v, __shfl_down(v, off));
-    return v;
-}
-
-// three sums and a minimum of a block -> dst[0..3]: wave shuffles, then the waves in order
+// three sums and a minimum of a block -> dst[0..3]
 __device__ __forceinline__ void i_block_store(double s0, double s1, double s2, double mn, double* __restrict__ dst) {
-    __shared__ double sh[4][IK / 64];
-    s0 = i_wave_sum(s0); s1 = i_wave_sum(s1); s2 = i_wave_sum(s2); mn = i_wave_min(mn);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[0][w] = s0; sh[1][w] = s1; sh[2][w] = s2; sh[3][w] = mn; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = sh[0][0], b = sh[1][0], c = sh[2][0], d = sh[3][0];
-        for (int i = 1; i < IK / 64; ++i) { a += sh[0][i]; b += sh[1][i]; c += sh[2][i]; d = i_min_nan(d, sh[3][i]); }
-        dst[0] = a; dst[1] = b; dst[2] = c; dst[3] = d;
-    }
+    double v[4] = {s0, s1, s2, mn};
+    block_reduce_store<IK, 4, true>(v, dst);
 }
 // a one-block grid is the whole reduction: it writes the result; otherwise block b writes its partials
 __device__ __forceinline__ double* i_dst(double* __restrict__ part, double* __restrict__ out) {
@@ -75,7 +55,7 @@ __global__ __launch_bounds__(IK) void combine_ls_kernel(double a, const double* 
             if (KIND == 0) {
                 const double r = wi / xi;
                 s1 += r - log(r) - 1.0;
-                mn = i_min_nan(mn, i_min_nan(wi, xi));
+                mn = min_nan(mn, min_nan(wi, xi));
             } else {
                 s1 += d * d;
             }
@@ -120,28 +100,13 @@ __global__ __launch_bounds__(IK) void lmo_pos_apply_kernel(const double* __restr
         sout[i] = si;
         const double d = si - ci;
         s0 += d * d;
-        mn = i_min_nan(mn, si);
+        mn = min_nan(mn, si);
     }
     i_block_store(s0, 0.0, 0.0, mn, i_dst(part, out));
 }
 
 // the partials of each slot in block order
-__global__ __launch_bounds__(IK) void inexact_final_kernel(const double* __restrict__ part, int nb,
-                                                           double* __restrict__ out) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, mn = __builtin_inf();
-    for (int b = threadIdx.x; b < nb; b += IK) {
-        s0 += part[4 * b]; s1 += part[4 * b + 1]; s2 += part[4 * b + 2];
-        mn = i_min_nan(mn, part[4 * b + 3]);
-    }
-    i_block_store(s0, s1, s2, mn, out);
-}
-
-int i_blocks(int64_t n) {
-    int64_t b = (n + (int64_t)IK * 4 - 1) / ((int64_t)IK * 4);
-    if (b < 1) b = 1;
-    if (b > IMAXBLK) b = IMAXBLK;
-    return (int)b;
-}
+constexpr reduce_final_fn inexact_final_kernel = reduce_final_kernel<IK, 4, true>;
 
 }  // namespace
 
@@ -159,11 +124,8 @@ extern "C" int accbpg_combine_ls_terms(int kind, double a, const double* u_dev, 
     hipStream_t s = (hipStream_t)stream;
     double* pin = nullptr; int* flags = nullptr; double* dout = nullptr;
     ACC_TRY(vec_scratch(&pin, &flags, &dout));
-    int nb = i_blocks(n);
-    if (!x_dev) {                                               // elementwise only: a block per 256 entries
-        const int64_t eb = (n + IK - 1) / IK;
-        nb = (int)(eb > 2048 ? 2048 : eb);
-    }
+    int nb = red_blocks(n, IMAXBLK);
+    if (!x_dev) nb = ew_blocks(n);                              // elementwise only: a block per 256 entries
     double* part = ws_dev ? ws_dev + n : nullptr;
     if (kind == 0)
         combine_ls_kernel<0><<<nb, IK, 0, s>>>(a, u_dev, b, v_dev, c, g_dev, x_dev, n, w_dev, part, dout);
@@ -171,15 +133,11 @@ extern "C" int accbpg_combine_ls_terms(int kind, double a, const double* u_dev, 
         combine_ls_kernel<1><<<nb, IK, 0, s>>>(a, u_dev, b, v_dev, c, g_dev, x_dev, n, w_dev, part, dout);
     ACC_HIP(hipGetLastError());
     if (!x_dev) return ACCBPG_OK;
-    if (nb > 1) {
-        inexact_final_kernel<<<1, IK, 0, s>>>(part, nb, dout);
-        ACC_HIP(hipGetLastError());
-    }
-    ACC_HIP(hipMemcpyAsync(pin + 8, dout, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    out2_host[0] = pin[8];
-    out2_host[1] = kind == 0 ? pin[9] : 0.5 * pin[9];
-    if (kind == 0 && !(pin[11] > 0.0)) {                        // functions.py:252
+    const double* o = reduce_finish(nb > 1 ? inexact_final_kernel : nullptr, part, nb, dout, dout, 4, pin, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out2_host[0] = o[0];
+    out2_host[1] = kind == 0 ? o[1] : 0.5 * o[1];
+    if (kind == 0 && !(o[3] > 0.0)) {                           // functions.py:252
         set_last_error("Entries of x or y not positive.");
         return ACCBPG_ERR_ASSERT;
     }
@@ -193,20 +151,19 @@ extern "C" int accbpg_lmo_l2_ball_pos(const double* g_dev, const double* center_
     hipStream_t s = (hipStream_t)stream;
     double* pin = nullptr; int* flags = nullptr; double* dout = nullptr;
     ACC_TRY(vec_scratch(&pin, &flags, &dout));
-    const int nb = i_blocks(n);
+    const int nb = red_blocks(n, IMAXBLK);
     double* part = ws_dev + n;
     lmo_pos_norm_kernel<<<nb, IK, 0, s>>>(g_dev, n, part, dout);
     if (nb > 1) inexact_final_kernel<<<1, IK, 0, s>>>(part, nb, dout);
     lmo_pos_apply_kernel<<<nb, IK, 0, s>>>(g_dev, center_dev, radius, epsilon, dout, n, out_dev, part, dout + 4);
-    if (nb > 1) inexact_final_kernel<<<1, IK, 0, s>>>(part, nb, dout + 4);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(pin + 8, dout, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    info3_host[0] = pin[10];                                    // entries with g < 0
-    info3_host[1] = sqrt(pin[12]);                              // ||s - c||
-    info3_host[2] = pin[15];                                    // min s
-    if (!(pin[10] > 0.0)) return ACCBPG_OK;                     // early return of :83-84: nothing is asserted
-    if (!(pin[15] >= epsilon)) {                                // :97
+    // both records (norm pass, apply pass) in one copy
+    const double* o = reduce_finish(nb > 1 ? inexact_final_kernel : nullptr, part, nb, dout + 4, dout, 8, pin, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    info3_host[0] = o[2];                                       // entries with g < 0
+    info3_host[1] = sqrt(o[4]);                                 // ||s - c||
+    info3_host[2] = o[7];                                       // min s
+    if (!(o[2] > 0.0)) return ACCBPG_OK;                        // early return of :83-84: nothing is asserted
+    if (!(o[7] >= epsilon)) {                                   // :97
         set_last_error("Output violates epsilon-nonnegativity");
         return ACCBPG_ERR_ASSERT;
     }

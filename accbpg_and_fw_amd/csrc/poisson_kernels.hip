@@ -10,6 +10,7 @@
 // The value is the fixed-tree sum of t.  Algorithmic traffic: 2 * 8 * m * n bytes per func_grad, 8*m*n for a
 // value-only call.  Compiled with -ffp-contract=off so that the epilogue rounds like the NumPy ufunc chain.
 #include "internal.h"
+#include "reduce.hpp"
 
 struct accbpg_poisson {
     const double* A = nullptr;
@@ -34,12 +35,6 @@ struct accbpg_kldiv : accbpg_poisson {};
 namespace accbpg {
 
 constexpr int QB = 256;
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
 
 struct PoissonEpilogue {
     __device__ __forceinline__ static void apply(double ax, double bi, int64_t row, double* __restrict__ Ax,
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(QB) void poisson_ax_kernel(const double* __restrict
             for (int64_t c = sub; c < n; c += TPR) s0 = fma(ar[c], x[c], s0);
         }
     }
-    double s = wsum(s0 + s1);
+    double s = wave_sum(s0 + s1);
     if (TPR == 64) {
         if (live && lane == 0) Epi::apply(s, b[row], row, Ax, r, t);
     } else {
@@ -117,7 +112,7 @@ __global__ __launch_bounds__(1024) void poisson_fsum_kernel(const double* __rest
     __shared__ double sh[16];
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < m; i += 1024) s += t[i];
-    s = wsum(s);
+    s = wave_sum(s);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) sh[w] = s;
     __syncthreads();

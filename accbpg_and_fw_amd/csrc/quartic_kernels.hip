@@ -12,39 +12,19 @@
 // Every sum is reduced over a fixed tree (a fixed number of blocks, wavefront shuffles, block order), so results are
 // reproducible run to run.  Compiled with -ffp-contract=off: one rounding per NumPy ufunc, no fused multiply-add.
 #include "internal.h"
+#include "reduce.hpp"
 
 namespace accbpg {
 
 namespace {
 
-constexpr int QK = 256;          // threads per block
+constexpr int QK = RED_THREADS;  // threads per block
 constexpr int QNS = 8;           // partial-sum slots per block
 constexpr int QMAXBLK = 512;     // QNS * QMAXBLK partials fit behind the n doubles of the vector workspace
-constexpr int QEWBLK = 2048;     // blocks of the elementwise passes
 
-__device__ __forceinline__ double q_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
-// the QNS slots of a block, each reduced over wave shuffles and then the waves in order, to part[block*QNS + k]
-__device__ __forceinline__ void q_block_store(double* s, double* __restrict__ part) {
-    __shared__ double sh[QNS][QK / 64];
-#pragma unroll
-    for (int k = 0; k < QNS; ++k) s[k] = q_wave_sum(s[k]);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < QNS; ++k) sh[k][w] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < QNS) {
-        const int k = threadIdx.x;
-        double a = sh[k][0];
-        for (int j = 1; j < QK / 64; ++j) a += sh[k][j];
-        part[blockIdx.x * QNS + k] = a;
-    }
+// the QNS sums of a block to part[block*QNS + k]
+__device__ __forceinline__ void q_block_store(double (&s)[QNS], double* __restrict__ part) {
+    block_reduce_store<QK, QNS, false>(s, part + blockIdx.x * QNS);
 }
 
 // y' = z*y - invL*g (functions.py:553-554), clipped to [0, ub] when clip (np.clip(y, 0, upper_bound), :573);
@@ -127,53 +107,12 @@ __global__ __launch_bounds__(QK) void lmo_linf_kernel(const double* __restrict__
     }
 }
 
-// the partials of each slot added in block order
-__global__ __launch_bounds__(QK) void quartic_final_kernel(const double* __restrict__ part, int nb,
-                                                           double* __restrict__ out) {
-    __shared__ double sh[QNS][QK / 64];
-    double s[QNS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nb; b += QK) {
-#pragma unroll
-        for (int k = 0; k < QNS; ++k) s[k] += part[b * QNS + k];
-    }
-#pragma unroll
-    for (int k = 0; k < QNS; ++k) s[k] = q_wave_sum(s[k]);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < QNS; ++k) sh[k][w] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < QNS) {
-        const int k = threadIdx.x;
-        double a = sh[k][0];
-        for (int j = 1; j < QK / 64; ++j) a += sh[k][j];
-        out[k] = a;
-    }
-}
-
-int q_ew_blocks(int64_t n) {
-    int64_t b = (n + QK - 1) / QK;
-    return (int)(b > QEWBLK ? QEWBLK : b);
-}
-
-int q_red_blocks(int64_t n) {
-    int64_t b = (n + (int64_t)QK * 4 - 1) / ((int64_t)QK * 4);
-    if (b < 1) b = 1;
-    if (b > QMAXBLK) b = QMAXBLK;
-    return (int)b;
-}
-
-// final reduction of `nb` block partials and a readback of the QNS slots to out_host
-int q_finish(const double* part, int nb, double* out_host, hipStream_t s) {
+// the partials of each slot added in block order and read back: *o = the QNS slots on the host
+int q_finish(const double* part, int nb, hipStream_t s, const double** o) {
     double* pin = nullptr; int* flags = nullptr; double* dout = nullptr;
     ACC_TRY(vec_scratch(&pin, &flags, &dout));
-    quartic_final_kernel<<<1, QK, 0, s>>>(part, nb, dout);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(pin + 8, dout, QNS * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < QNS; ++k) out_host[k] = pin[8 + k];
-    return ACCBPG_OK;
+    *o = reduce_finish(reduce_final_kernel<QK, QNS, false>, part, nb, dout, dout, QNS, pin, s);
+    return *o ? ACCBPG_OK : ACCBPG_ERR_HIP;
 }
 
 }  // namespace
@@ -187,12 +126,11 @@ extern "C" int accbpg_quartic_prox_stage(const double* y_dev, const double* g_de
                                          double* ws_dev, void* stream) {
     if (!y_dev || !g_dev || !out_dev || !ssq_host || !ws_dev || n <= 0 || clip < 0 || clip > 1) return ACCBPG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int nb = q_red_blocks(n);
+    const int nb = red_blocks(n, QMAXBLK);
     double* part = ws_dev + n;
     quartic_prox_kernel<<<nb, QK, 0, s>>>(y_dev, g_dev, z, invL, clip, upper_bound, n, out_dev, part);
-    ACC_HIP(hipGetLastError());
-    double o[QNS];
-    ACC_TRY(q_finish(part, nb, o, s));
+    const double* o = nullptr;
+    ACC_TRY(q_finish(part, nb, s, &o));
     ssq_host[0] = o[0];
     return ACCBPG_OK;
 }
@@ -203,12 +141,11 @@ extern "C" int accbpg_quartic_ls_terms(const double* g_dev, const double* x_dev,
     if (!x_dev || !y_dev || n <= 0 || !out7_host || !ws_dev) return ACCBPG_ERR_ARG;
     if ((z_dev == nullptr) != (z1_dev == nullptr)) return ACCBPG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int nb = q_red_blocks(n);
+    const int nb = red_blocks(n, QMAXBLK);
     double* part = ws_dev + n;
     quartic_ls_kernel<<<nb, QK, 0, s>>>(g_dev, x_dev, y_dev, z_dev, z1_dev, n, part);
-    ACC_HIP(hipGetLastError());
-    double o[QNS];
-    ACC_TRY(q_finish(part, nb, o, s));
+    const double* o = nullptr;
+    ACC_TRY(q_finish(part, nb, s, &o));
     for (int k = 0; k < 7; ++k) out7_host[k] = o[k];
     return ACCBPG_OK;
 }
@@ -219,12 +156,11 @@ extern "C" int accbpg_lmo_l2_ball(const double* g_dev, int center_kind, const do
     if (!g_dev || !out_dev || !dist_host || !ws_dev || n <= 0 || center_kind < 0 || center_kind > 1) return ACCBPG_ERR_ARG;
     if (center_kind == 1 && !center_dev) return ACCBPG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int nb = q_red_blocks(n);
+    const int nb = red_blocks(n, QMAXBLK);
     double* part = ws_dev + n;
     lmo_l2_kernel<<<nb, QK, 0, s>>>(g_dev, center_kind, center_dev, center_val, radius, gnorm, n, out_dev, part);
-    ACC_HIP(hipGetLastError());
-    double o[QNS];
-    ACC_TRY(q_finish(part, nb, o, s));
+    const double* o = nullptr;
+    ACC_TRY(q_finish(part, nb, s, &o));
     dist_host[0] = sqrt(o[0]);
     if (!(fabs(dist_host[0] - radius) <= 1e-10)) {                // functions_lmo.py:45-46
         set_last_error("Solution does not lie on ball boundary");
@@ -238,7 +174,7 @@ extern "C" int accbpg_lmo_linf_ball(const double* g_dev, int center_kind, const 
     if (!g_dev || !out_dev || n <= 0 || center_kind < 0 || center_kind > 1) return ACCBPG_ERR_ARG;
     if (center_kind == 1 && !center_dev) return ACCBPG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    lmo_linf_kernel<<<q_ew_blocks(n), QK, 0, s>>>(g_dev, center_kind, center_dev, center_val, radius, n, out_dev);
+    lmo_linf_kernel<<<ew_blocks(n), QK, 0, s>>>(g_dev, center_kind, center_dev, center_val, radius, n, out_dev);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }

@@ -9,29 +9,16 @@
 // inside the reference's own rounding band there.  Compiled with -ffp-contract=off: the reference evaluates these
 // expressions with separate NumPy ufuncs (one rounding per operation), so no multiply-add may be fused.
 #include "internal.h"
+#include "reduce.hpp"
 
 namespace accbpg {
 
 namespace {
 
-constexpr int SB = 256;          // threads of the Shannon kernels
+constexpr int SB = RED_THREADS;  // threads of the Shannon kernels
 constexpr int SNS = 8;           // partial-sum slots per block of the streaming reductions
 constexpr int SMAXBLK = 512;     // blocks of a reduction: SNS * SMAXBLK partials fit behind the n doubles of the
                                  // vector workspace (vec_ws_doubles)
-constexpr int SEWBLK = 2048;     // blocks of the elementwise passes
-
-__device__ __forceinline__ double s_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-// minimum that keeps a NaN (np.min does, so a NaN fails the reference's `x.min() >= 0`)
-__device__ __forceinline__ double s_min_nan(double a, double b) { return (b < a || b != b) ? b : a; }
-__device__ __forceinline__ double s_wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = s_min_nan(v, __shfl_down(v, off));
-    return v;
-}
 
 // argument of the exponential: the L1 kind adds lamda to g first (functions.py:456-466), then -g/L
 __device__ __forceinline__ double neg_g_over_L(int kind, double gi, double L, double lamda) {
@@ -66,7 +53,6 @@ __global__ __launch_bounds__(SB) void shannon_simplex_partial_kernel(const doubl
                                                                     double* __restrict__ out,
                                                                     double* __restrict__ part,
                                                                     int* __restrict__ flags) {
-    __shared__ double sh[SB / 64];
     const int64_t stride = (int64_t)gridDim.x * SB;
     bool bad_y = false;
     double s = 0.0;
@@ -84,22 +70,15 @@ __global__ __launch_bounds__(SB) void shannon_simplex_partial_kernel(const doubl
         s += xi;
     }
     if (bad_y) flags[FLAG_NONPOS] = 1;
-    s = s_wave_sum(s);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int k = 0; k < SB / 64; ++k) a += sh[k];
-        part[blockIdx.x] = a;
-    }
+    double v[1] = {s};
+    block_reduce_store<SB, 1, false>(v, part + blockIdx.x);
 }
 
 // sum of the nb partials in a fixed order (every block obtains the same total), broadcast to the block
 __device__ __forceinline__ double block_total(const double* __restrict__ part, int nb, double* sh) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nb; b += SB) s += part[b];
-    s = s_wave_sum(s);
+    s = wave_sum(s);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) sh[w] = s;
     __syncthreads();
@@ -131,9 +110,8 @@ __global__ __launch_bounds__(SB) void shannon_ls_partial_kernel(const double* __
                                                                const double* __restrict__ z,
                                                                const double* __restrict__ z1, int64_t n, double delta,
                                                                double* __restrict__ part) {
-    __shared__ double sh[SNS][SB / 64];
-    double s[SNS - 1] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double mn = __builtin_inf();
+    double s[SNS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, __builtin_inf()};
+    double& mn = s[SNS - 1];
     const int64_t stride = (int64_t)gridDim.x * SB;
     for (int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x; i < n; i += stride) {
         const double xi = x[i], yi = y[i];
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(SB) void shannon_ls_partial_kernel(const double* __
             s[1] += xi * lg;
             s[2] += xi;
             s[3] += yi;
-            mn = s_min_nan(mn, s_min_nan(xi, yi));
+            mn = min_nan(mn, min_nan(xi, yi));
         }
         if (z != nullptr) {
             const double zi = z[i], wi = z1[i];
@@ -158,66 +136,10 @@ __global__ __launch_bounds__(SB) void shannon_ls_partial_kernel(const double* __
             s[4] += zi * lg;
             s[5] += zi;
             s[6] += wi;
-            mn = s_min_nan(mn, s_min_nan(zi, wi));
+            mn = min_nan(mn, min_nan(zi, wi));
         }
     }
-#pragma unroll
-    for (int k = 0; k < SNS - 1; ++k) s[k] = s_wave_sum(s[k]);
-    mn = s_wave_min(mn);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < SNS - 1; ++k) sh[k][w] = s[k];
-        sh[SNS - 1][w] = mn;
-    }
-    __syncthreads();
-    if (threadIdx.x < SNS) {
-        const int k = threadIdx.x;
-        double a = sh[k][0];
-        for (int j = 1; j < SB / 64; ++j) a = (k == SNS - 1) ? s_min_nan(a, sh[k][j]) : a + sh[k][j];
-        part[blockIdx.x * SNS + k] = a;
-    }
-}
-
-// stage 2: one workgroup adds the partials of each slot in block order; out[0..7] as the slots
-__global__ __launch_bounds__(SB) void shannon_ls_final_kernel(const double* __restrict__ part, int nb,
-                                                             double* __restrict__ out) {
-    __shared__ double sh[SNS][SB / 64];
-    double s[SNS - 1] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double mn = __builtin_inf();
-    for (int b = threadIdx.x; b < nb; b += SB) {
-#pragma unroll
-        for (int k = 0; k < SNS - 1; ++k) s[k] += part[b * SNS + k];
-        mn = s_min_nan(mn, part[b * SNS + SNS - 1]);
-    }
-#pragma unroll
-    for (int k = 0; k < SNS - 1; ++k) s[k] = s_wave_sum(s[k]);
-    mn = s_wave_min(mn);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < SNS - 1; ++k) sh[k][w] = s[k];
-        sh[SNS - 1][w] = mn;
-    }
-    __syncthreads();
-    if (threadIdx.x < SNS) {
-        const int k = threadIdx.x;
-        double a = sh[k][0];
-        for (int j = 1; j < SB / 64; ++j) a = (k == SNS - 1) ? s_min_nan(a, sh[k][j]) : a + sh[k][j];
-        out[k] = a;
-    }
-}
-
-int ew_blocks(int64_t n) {
-    int64_t b = (n + SB - 1) / SB;
-    return (int)(b > SEWBLK ? SEWBLK : b);
-}
-
-int sred_blocks(int64_t n) {
-    int64_t b = (n + (int64_t)SB * 4 - 1) / ((int64_t)SB * 4);
-    if (b < 1) b = 1;
-    if (b > SMAXBLK) b = SMAXBLK;
-    return (int)b;
+    block_reduce_store<SB, SNS, true>(s, part + blockIdx.x * SNS);
 }
 
 }  // namespace
@@ -239,7 +161,7 @@ extern "C" int accbpg_shannon_div_prox(int kind, const double* y_dev, const doub
     hipStream_t s = (hipStream_t)stream;
     ACC_HIP(hipMemsetAsync(flags, 0, 8 * sizeof(int), s));
     if (kind == 2) {
-        const int nb = sred_blocks(n);
+        const int nb = red_blocks(n, SMAXBLK);
         double* part = ws_dev + n;
         shannon_simplex_partial_kernel<<<nb, SB, 0, s>>>(y_dev, g_dev, L, n, x_out_dev, part, flags);
         shannon_simplex_scale_kernel<<<ew_blocks(n), SB, 0, s>>>(part, nb, n, x_out_dev);
@@ -265,14 +187,12 @@ extern "C" int accbpg_shannon_ls_terms(const double* g_dev, const double* x_dev,
     double* pin = nullptr; int* flags = nullptr; double* dout = nullptr;
     ACC_TRY(vec_scratch(&pin, &flags, &dout));
     hipStream_t s = (hipStream_t)stream;
-    const int nb = sred_blocks(n);
+    const int nb = red_blocks(n, SMAXBLK);
     double* part = ws_dev + n;
     shannon_ls_partial_kernel<<<nb, SB, 0, s>>>(g_dev, x_dev, y_dev, z_dev, z1_dev, n, delta, part);
-    shannon_ls_final_kernel<<<1, SB, 0, s>>>(part, nb, dout);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(pin + 8, dout, SNS * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    const double* o = pin + 8;
+    // stage 2: one workgroup adds the partials of each slot in block order; o[0..7] as the slots
+    const double* o = reduce_finish(reduce_final_kernel<SB, SNS, true>, part, nb, dout, dout, SNS, pin, s);
+    if (!o) return ACCBPG_ERR_HIP;
     out_host[0] = o[0];
     out_host[1] = o[1] + (o[3] - o[2]);                         // sum(x log(..)) + (sum(y) - sum(x)), functions.py:421
     out_host[2] = o[4] + (o[6] - o[5]);

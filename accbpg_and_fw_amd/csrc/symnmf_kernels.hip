@@ -17,6 +17,7 @@
 // epilogue rounds like the NumPy ufunc chain (the MFMA products are unaffected).
 #include "internal.h"
 #include "mfma_tile.hpp"
+#include "reduce.hpp"
 
 #include <math.h>
 #include <algorithm>
@@ -51,14 +52,9 @@ constexpr int Y_MAXCB = 1024;
 using TileR64 = Tile<256, 64, 64, 64, true>;
 using TileR128 = TileBig<true>;
 
-__device__ __forceinline__ double y_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
 // block sum in a fixed order (wave shuffles, then the four waves in order); valid in thread 0
 __device__ __forceinline__ double y_block_sum(double v, double* sh) {
-    v = y_wave_sum(v);
+    v = wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) sh[w] = v;
     __syncthreads();

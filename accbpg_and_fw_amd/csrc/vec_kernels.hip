@@ -10,26 +10,13 @@
 #include <mutex>
 
 #include "internal.h"
+#include "reduce.hpp"
 
 namespace accbpg {
 
 constexpr int PB = 1024;   // threads of the single-workgroup prox kernel
-constexpr int RB = 256;    // threads of the streaming reductions
+constexpr int RB = RED_THREADS;    // threads of the streaming reductions
 constexpr int RMAXBLK = 1024;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-// minimum that keeps a NaN (np.min does; fmin would drop it and a NaN would slip through the reference's
-// `x.min() > 0` assertions, functions.py:252)
-__device__ __forceinline__ double min_nan(double a, double b) { return (b < a || b != b) ? b : a; }
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min_nan(v, __shfl_down(v, off));
-    return v;
-}
 
 // sum over the PB threads of the prox workgroup, result broadcast to every thread
 __device__ __forceinline__ double block_sum_bcast(double v, double* sh) {
@@ -352,7 +339,6 @@ __device__ __forceinline__ void ls_terms_partial_body(const double* __restrict__
                                                       const double* __restrict__ z,
                                                       const double* __restrict__ z1, int64_t n,
                                                       int want_div_xy, double* __restrict__ part) {
-    __shared__ double sh[4][RB / 64];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, mn = __builtin_inf();
     const int64_t stride = (int64_t)gridDim.x * RB;
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
@@ -375,16 +361,8 @@ __device__ __forceinline__ void ls_terms_partial_body(const double* __restrict__
             mn = min_nan(mn, min_nan(zi, wi));
         }
     }
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); mn = wave_min(mn);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[0][w] = s0; sh[1][w] = s1; sh[2][w] = s2; sh[3][w] = mn; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0, c = 0.0, d = sh[3][0];
-        for (int i = 0; i < RB / 64; ++i) { a += sh[0][i]; b += sh[1][i]; c += sh[2][i]; d = min_nan(d, sh[3][i]); }
-        part[blockIdx.x * 4 + 0] = a; part[blockIdx.x * 4 + 1] = b;
-        part[blockIdx.x * 4 + 2] = c; part[blockIdx.x * 4 + 3] = d;
-    }
+    double v[4] = {s0, s1, s2, mn};
+    block_reduce_store<RB, 4, true>(v, part + blockIdx.x * 4);
 }
 
 __global__ __launch_bounds__(RB) void ls_terms_partial_kernel(const double* __restrict__ g,
@@ -408,33 +386,14 @@ __global__ __launch_bounds__(RB) void ls_terms_partial_batch_kernel(BatchAct act
 }
 
 // stage 2: one workgroup adds the partials in block order
-__device__ __forceinline__ void ls_terms_final_body(const double* __restrict__ part, int nblk,
-                                                    double* __restrict__ out) {
-    __shared__ double sh[4][RB / 64];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, mn = __builtin_inf();
-    for (int b = threadIdx.x; b < nblk; b += RB) {
-        s0 += part[b * 4 + 0]; s1 += part[b * 4 + 1]; s2 += part[b * 4 + 2];
-        mn = min_nan(mn, part[b * 4 + 3]);
-    }
-    s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2); mn = wave_min(mn);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[0][w] = s0; sh[1][w] = s1; sh[2][w] = s2; sh[3][w] = mn; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0, c = 0.0, d = sh[3][0];
-        for (int i = 0; i < RB / 64; ++i) { a += sh[0][i]; b += sh[1][i]; c += sh[2][i]; d = min_nan(d, sh[3][i]); }
-        out[0] = a; out[1] = b; out[2] = c; out[3] = d;
-    }
-}
-
 __global__ __launch_bounds__(RB) void ls_terms_final_kernel(const double* __restrict__ part, int nblk,
                                                            double* __restrict__ out) {
-    ls_terms_final_body(part, nblk, out);
+    reduce_final_body<RB, 4, true>(part, nblk, out);
 }
 __global__ __launch_bounds__(RB) void ls_terms_final_batch_kernel(BatchAct act, const double* __restrict__ part,
                                                                  int64_t pstride, int nblk, double* __restrict__ out) {
     const int inst = act.idx[blockIdx.x];
-    ls_terms_final_body(part + (int64_t)inst * pstride, nblk, out + 4 * inst);
+    reduce_final_body<RB, 4, true>(part + (int64_t)inst * pstride, nblk, out + 4 * inst);
 }
 
 // out = a*x + b*z for every active instance of a batch (its own a and b), NumPy's rounding as in axpby_kernel
@@ -454,7 +413,6 @@ __global__ __launch_bounds__(RB) void axpby_batch_kernel(BatchAct act, BatchVals
 
 __global__ __launch_bounds__(RB) void min_sum_partial_kernel(const double* __restrict__ x, int64_t n,
                                                             double* __restrict__ part) {
-    __shared__ double sh[2][RB / 64];
     double s = 0.0, mn = __builtin_inf();
     const int64_t stride = (int64_t)gridDim.x * RB;
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
@@ -462,16 +420,8 @@ __global__ __launch_bounds__(RB) void min_sum_partial_kernel(const double* __res
         s += v;
         mn = min_nan(mn, v);
     }
-    s = wave_sum(s); mn = wave_min(mn);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { sh[0][w] = s; sh[1][w] = mn; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, d = sh[1][0];
-        for (int i = 0; i < RB / 64; ++i) { a += sh[0][i]; d = min_nan(d, sh[1][i]); }
-        part[blockIdx.x * 4 + 0] = a; part[blockIdx.x * 4 + 1] = 0.0;
-        part[blockIdx.x * 4 + 2] = 0.0; part[blockIdx.x * 4 + 3] = d;
-    }
+    double v[2] = {s, mn};
+    block_reduce_store<RB, 2, true, 4>(v, part + blockIdx.x * 4);
 }
 
 // out = a*x + b*z with NumPy's rounding of (1-theta)*x + theta*z   (algorithms.py:147,150,369,374)
@@ -503,20 +453,11 @@ __global__ __launch_bounds__(RB) void vertex_kernel(int64_t idx, double value, d
 // sum x*y  (np.dot(x, x) of BurgEntropyL2.extra_Psi, functions.py:314)
 __global__ __launch_bounds__(RB) void dot_partial_kernel(const double* __restrict__ x, const double* __restrict__ y,
                                                         int64_t n, double* __restrict__ part) {
-    __shared__ double sh[RB / 64];
     double s = 0.0;
     const int64_t stride = (int64_t)gridDim.x * RB;
     for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) s += x[i] * y[i];
-    s = wave_sum(s);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int i = 0; i < RB / 64; ++i) a += sh[i];
-        part[blockIdx.x * 4 + 0] = a; part[blockIdx.x * 4 + 1] = 0.0;
-        part[blockIdx.x * 4 + 2] = 0.0; part[blockIdx.x * 4 + 3] = 0.0;
-    }
+    double v[1] = {s};
+    block_reduce_store<RB, 1, false, 4>(v, part + blockIdx.x * 4);
 }
 
 // Closed-form Burg-entropy prox maps on x > 0 with NumPy's operation order:
@@ -677,11 +618,9 @@ static bool g_prox_multi_off = false;    // set when the multi-workgroup prox ha
 
 int64_t vec_ws_doubles(int64_t n) { return n + 4 * RMAXBLK + 64; }
 
-static int red_blocks(int64_t n) {
-    int64_t b = (n + (int64_t)RB * 4 - 1) / ((int64_t)RB * 4);
-    if (b < 1) b = 1;
-    if (b > RMAXBLK) b = RMAXBLK;
-    return (int)b;
+// the tail of the 4-slot reductions: final stage over nb block records behind the n doubles of ws, result on the host
+static const double* finish4(const double* part, int nb, hipStream_t s) {
+    return reduce_finish(ls_terms_final_kernel, part, nb, g_out, g_out, 4, g_pin, s);
 }
 
 }  // namespace accbpg
@@ -777,15 +716,13 @@ extern "C" int accbpg_ls_terms(const double* g_dev, const double* x_dev, const d
     if ((z_dev == nullptr) != (z1_dev == nullptr)) return ACCBPG_ERR_ARG;
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
-    const int nb = red_blocks(n);
+    const int nb = red_blocks(n, RMAXBLK);
     double* part = ws_dev + n;
     ls_terms_partial_kernel<<<nb, RB, 0, s>>>(g_dev, x_dev, y_dev, z_dev, z1_dev, n, 1, part);
-    ls_terms_final_kernel<<<1, RB, 0, s>>>(part, nb, g_out);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(g_pin + 8, g_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    out_host[0] = g_pin[8]; out_host[1] = g_pin[9]; out_host[2] = g_pin[10];
-    if (!(g_pin[11] > 0.0)) return ACCBPG_ERR_ASSERT;         // functions.py:252
+    const double* o = finish4(part, nb, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out_host[0] = o[0]; out_host[1] = o[1]; out_host[2] = o[2];
+    if (!(o[3] > 0.0)) return ACCBPG_ERR_ASSERT;              // functions.py:252
     return ACCBPG_OK;
 }
 
@@ -803,14 +740,12 @@ extern "C" int accbpg_vec_dot_diff(const double* g_dev, const double* x_dev, con
     if (!g_dev || !x_dev || !y_dev || n <= 0 || !out_host || !ws_dev) return ACCBPG_ERR_ARG;
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
-    const int nb = red_blocks(n);
+    const int nb = red_blocks(n, RMAXBLK);
     double* part = ws_dev + n;
     ls_terms_partial_kernel<<<nb, RB, 0, s>>>(g_dev, x_dev, y_dev, nullptr, nullptr, n, 0, part);
-    ls_terms_final_kernel<<<1, RB, 0, s>>>(part, nb, g_out);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(g_pin + 8, g_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    out_host[0] = g_pin[8];
+    const double* o = finish4(part, nb, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out_host[0] = o[0];
     return ACCBPG_OK;
 }
 
@@ -818,15 +753,13 @@ extern "C" int accbpg_vec_min_sum(const double* x_dev, int64_t n, double* out_ho
     if (!x_dev || n <= 0 || !out_host || !ws_dev) return ACCBPG_ERR_ARG;
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
-    const int nb = red_blocks(n);
+    const int nb = red_blocks(n, RMAXBLK);
     double* part = ws_dev + n;
     min_sum_partial_kernel<<<nb, RB, 0, s>>>(x_dev, n, part);
-    ls_terms_final_kernel<<<1, RB, 0, s>>>(part, nb, g_out);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(g_pin + 8, g_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    out_host[0] = g_pin[11];
-    out_host[1] = g_pin[8];
+    const double* o = finish4(part, nb, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out_host[0] = o[3];
+    out_host[1] = o[0];
     return ACCBPG_OK;
 }
 
@@ -834,27 +767,21 @@ extern "C" int accbpg_vec_axpby(double a, const double* x_dev, double b, const d
                                 double* out_dev, void* stream) {
     if (!x_dev || !z_dev || !out_dev || n <= 0) return ACCBPG_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    int64_t nb = (n + RB - 1) / RB;
-    if (nb > 2048) nb = 2048;
-    axpby_kernel<<<(int)nb, RB, 0, s>>>(a, x_dev, b, z_dev, n, out_dev);
+    axpby_kernel<<<ew_blocks(n), RB, 0, s>>>(a, x_dev, b, z_dev, n, out_dev);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
 
 extern "C" int accbpg_vec_div_scalar(const double* x_dev, double d, int64_t n, double* out_dev, void* stream) {
     if (!x_dev || !out_dev || n <= 0) return ACCBPG_ERR_ARG;
-    int64_t nb = (n + RB - 1) / RB;
-    if (nb > 2048) nb = 2048;
-    div_scalar_kernel<<<(int)nb, RB, 0, (hipStream_t)stream>>>(x_dev, d, n, out_dev);
+    div_scalar_kernel<<<ew_blocks(n), RB, 0, (hipStream_t)stream>>>(x_dev, d, n, out_dev);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
 
 extern "C" int accbpg_vec_vertex(int64_t idx, double value, double fill, int64_t n, double* out_dev, void* stream) {
     if (!out_dev || n <= 0 || idx < 0 || idx >= n) return ACCBPG_ERR_ARG;
-    int64_t nb = (n + RB - 1) / RB;
-    if (nb > 2048) nb = 2048;
-    vertex_kernel<<<(int)nb, RB, 0, (hipStream_t)stream>>>(idx, value, fill, n, out_dev);
+    vertex_kernel<<<ew_blocks(n), RB, 0, (hipStream_t)stream>>>(idx, value, fill, n, out_dev);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
@@ -864,7 +791,7 @@ extern "C" int accbpg_vec_argminmax(const double* x_dev, int64_t n, int64_t* idx
     if (!x_dev || n <= 0 || !idx_host || !ws_dev) return ACCBPG_ERR_ARG;
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
-    int nb = red_blocks(n);
+    int nb = red_blocks(n, RMAXBLK);
     if (nb > 128) nb = 128;                                     // 128 records of 32 B = the 4096-double tail of ws
     MinMaxRec* part = reinterpret_cast<MinMaxRec*>(ws_dev + n + (n & 1));
     MinMaxRec* out = reinterpret_cast<MinMaxRec*>(g_out + 8);
@@ -885,14 +812,12 @@ extern "C" int accbpg_vec_dot(const double* x_dev, const double* y_dev, int64_t 
     if (!x_dev || !y_dev || n <= 0 || !out_host || !ws_dev) return ACCBPG_ERR_ARG;
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
-    const int nb = red_blocks(n);
+    const int nb = red_blocks(n, RMAXBLK);
     double* part = ws_dev + n;
     dot_partial_kernel<<<nb, RB, 0, s>>>(x_dev, y_dev, n, part);
-    ls_terms_final_kernel<<<1, RB, 0, s>>>(part, nb, g_out);
-    ACC_HIP(hipGetLastError());
-    ACC_HIP(hipMemcpyAsync(g_pin + 8, g_out, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    ACC_HIP(hipStreamSynchronize(s));
-    out_host[0] = g_pin[8];
+    const double* o = finish4(part, nb, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out_host[0] = o[0];
     return ACCBPG_OK;
 }
 
@@ -907,9 +832,7 @@ extern "C" int accbpg_burg_reg_div_prox(int kind, const double* y_dev, const dou
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
     ACC_HIP(hipMemsetAsync(g_flags, 0, 8 * sizeof(int), s));
-    int64_t nb = (n + RB - 1) / RB;
-    if (nb > 2048) nb = 2048;
-    burg_reg_prox_kernel<<<(int)nb, RB, 0, s>>>(kind, y_dev, g_dev, L, lamda, n, x_out_dev, g_flags);
+    burg_reg_prox_kernel<<<ew_blocks(n), RB, 0, s>>>(kind, y_dev, g_dev, L, lamda, n, x_out_dev, g_flags);
     ACC_HIP(hipGetLastError());
     int* pin_i = reinterpret_cast<int*>(g_pin);
     ACC_HIP(hipMemcpyAsync(pin_i, g_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1018,7 +941,7 @@ extern "C" int accbpg_dopt_batch_ls_terms(accbpg_dopt_batch* b, const double* g_
     const BatchAct act = batch_active(b, active_host);
     if (act.n == 0) return ACCBPG_OK;
     hipStream_t s = b->stream;
-    const int nb = red_blocks(n);
+    const int nb = red_blocks(n, RMAXBLK);
     ls_terms_partial_batch_kernel<<<dim3(nb, act.n), RB, 0, s>>>(act, g_dev, x_dev, y_dev, z_dev, z1_dev, ld, n, b->vpart,
                                                                 4 * RMAXBLK);
     ls_terms_final_batch_kernel<<<act.n, RB, 0, s>>>(act, b->vpart, 4 * RMAXBLK, nb, b->vout);

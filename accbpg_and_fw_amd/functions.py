@@ -74,6 +74,17 @@ class _Workspace:
         return ws
 
 
+_WS = object()      # in the arguments of _call: the pointer to the workspace of the reference tensor's size
+
+
+def _call(name, ref, *args, assert_msg=None):
+    """The C entry `name` on ref's device: args (with _WS filled in) and the current stream, then the status check."""
+    with torch.cuda.device(ref.device):
+        args = [_ptr(_Workspace.get(ref.numel(), ref.device)) if a is _WS else a for a in args]
+        rc = getattr(_lib.load(), name)(*args, _stream())
+    _lib.check(rc, name, assert_msg)
+
+
 # ------------------------------------------------------------------ f
 class RSmoothFunction:
     """Relatively-smooth function protocol (accbpg/functions.py:10-24)."""
@@ -661,10 +672,8 @@ class BurgEntropy(LegendreFunction):
         yd, _ = to_dev(y)
         n = xd.numel()
         out = C.c_double(0.0)
-        with torch.cuda.device(xd.device):
-            ws = _Workspace.get(n, xd.device)
-            rc = _lib.load().accbpg_burg_divergence(_ptr(xd), _ptr(yd), n, C.byref(out), _ptr(ws), _stream())
-        _lib.check(rc, "accbpg_burg_divergence", "Entries of x or y not positive.")
+        _call("accbpg_burg_divergence", xd, _ptr(xd), _ptr(yd), n, C.byref(out), _WS,
+              assert_msg="Entries of x or y not positive.")
         return np.float64(out.value)                            # a NumPy scalar, as the reference's sum is (:253)
 
     _kind = 0       # closed-form variant of accbpg_burg_reg_div_prox
@@ -747,11 +756,8 @@ class BurgEntropySimplex(BurgEntropy):
         n = gd.numel()
         out = torch.empty(n, dtype=torch.float64, device=gd.device)
         info = (C.c_int * 2)(0, 0)
-        with torch.cuda.device(gd.device):
-            ws = _Workspace.get(n, gd.device)
-            rc = _lib.load().accbpg_burg_simplex_div_prox(_ptr(yd), _ptr(gd), float(L), float(self.eps), n,
-                                                          _ptr(out), _ptr(ws), info, _stream())
-        _lib.check(rc, "accbpg_burg_simplex_div_prox", "Either y or L is not positive.")
+        _call("accbpg_burg_simplex_div_prox", gd, _ptr(yd), _ptr(gd), float(L), float(self.eps), n, _ptr(out), _WS,
+              info, assert_msg="Either y or L is not positive.")
         self.last_info = (info[0], info[1])
         return from_dev(out, was_np)
 
@@ -772,11 +778,8 @@ class BurgEntropySimplex(BurgEntropy):
         n = xi.numel()
         xi_out = torch.empty_like(xi)
         out = torch.empty_like(xi)
-        with torch.cuda.device(xi.device):
-            ws = _Workspace.get(n, xi.device)
-            rc = _lib.load().accbpg_burg_simplex_prox_acc(_ptr(xi), float(alpha), _ptr(g), 1.0, float(self.eps), n,
-                                                          _ptr(xi_out), _ptr(out), _ptr(ws), None, _stream())
-        _lib.check(rc, "accbpg_burg_simplex_prox_acc")
+        _call("accbpg_burg_simplex_prox_acc", xi, _ptr(xi), float(alpha), _ptr(g), 1.0, float(self.eps), n,
+              _ptr(xi_out), _ptr(out), _WS, None)
         return xi_out, out
 
 
@@ -807,11 +810,8 @@ class ShannonEntropy(LegendreFunction):
         yd, _ = to_dev(y)
         n = xd.numel()
         out = C.c_double(0.0)
-        with torch.cuda.device(xd.device):
-            ws = _Workspace.get(n, xd.device)
-            rc = _lib.load().accbpg_shannon_divergence(_ptr(xd), _ptr(yd), n, float(self.delta), C.byref(out),
-                                                       _ptr(ws), _stream())
-        _lib.check(rc, "accbpg_shannon_divergence", "Some entries are negative.")
+        _call("accbpg_shannon_divergence", xd, _ptr(xd), _ptr(yd), n, float(self.delta), C.byref(out), _WS,
+              assert_msg="Some entries are negative.")
         return np.float64(out.value)                            # a NumPy scalar, as the reference's sum is (:421)
 
     def _prox(self, y, g, L, msg):
@@ -821,11 +821,8 @@ class ShannonEntropy(LegendreFunction):
             yd, _ = to_dev(y)
         n = gd.numel()
         out = torch.empty_like(gd)
-        with torch.cuda.device(gd.device):
-            ws = _Workspace.get(n, gd.device) if self._kind == 2 else None
-            rc = _lib.load().accbpg_shannon_div_prox(self._kind, _ptr(yd), _ptr(gd), float(L), float(self.lamda), n,
-                                                     _ptr(out), _ptr(ws), _stream())
-        _lib.check(rc, "accbpg_shannon_div_prox", msg)
+        _call("accbpg_shannon_div_prox", gd, self._kind, _ptr(yd), _ptr(gd), float(L), float(self.lamda), n, _ptr(out),
+              _WS if self._kind == 2 else _ptr(None), assert_msg=msg)
         return from_dev(out, was_np)
 
     def prox_map(self, g, L):
@@ -929,11 +926,8 @@ class SumOf2nd4thPowers(LegendreFunction):
         out = torch.empty_like(yd)
         ssq = C.c_double(0.0)
         ub = np.inf if self.upper_bound is None else float(self.upper_bound)
-        with torch.cuda.device(yd.device):
-            ws = _Workspace.get(n, yd.device)
-            rc = _lib.load().accbpg_quartic_prox_stage(_ptr(yd), _ptr(gd), float(z), float(1 / L), self._clip, ub, n,
-                                                       _ptr(out), C.byref(ssq), _ptr(ws), _stream())
-        _lib.check(rc, "accbpg_quartic_prox_stage")
+        _call("accbpg_quartic_prox_stage", yd, _ptr(yd), _ptr(gd), float(z), float(1 / L), self._clip, ub, n, _ptr(out),
+              C.byref(ssq), _WS)
         norm = np.sqrt(np.float64(ssq.value))
         z = self.solve_cubic(self.alpha * norm ** 2, self.sigma)                 # :554
         return from_dev(vec_div_scalar(out, z), was_np)
@@ -983,40 +977,29 @@ class SquaredL2Norm(LegendreFunction):
 def vec_axpby(a, x, b, z):
     """a*x + b*z with NumPy's rounding (two products, one sum)."""
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().accbpg_vec_axpby(float(a), _ptr(x), float(b), _ptr(z), x.numel(), _ptr(out), _stream())
-    _lib.check(rc, "accbpg_vec_axpby")
+    _call("accbpg_vec_axpby", x, float(a), _ptr(x), float(b), _ptr(z), x.numel(), _ptr(out))
     return out
 
 
 def vec_dot_diff(g, x, y):
     """<g, x - y>  (np.dot(g, x1-x), algorithms.py:53)."""
     out = C.c_double(0.0)
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_vec_dot_diff(_ptr(g), _ptr(x), _ptr(y), x.numel(), C.byref(out), _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_vec_dot_diff")
+    _call("accbpg_vec_dot_diff", x, _ptr(g), _ptr(x), _ptr(y), x.numel(), C.byref(out), _WS)
     return out.value
 
 
 def vec_dot(x, y):
     """<x, y>  (np.dot(x, x) of BurgEntropyL2.extra_Psi, functions.py:314)."""
     out = C.c_double(0.0)
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_vec_dot(_ptr(x), _ptr(y), x.numel(), C.byref(out), _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_vec_dot")
+    _call("accbpg_vec_dot", x, _ptr(x), _ptr(y), x.numel(), C.byref(out), _WS)
     return out.value
 
 
 def ls_terms(g, x, y, z=None, z1=None):
     """(<g,x-y>, D(x,y), D(z,z1)) in one launch and one readback."""
     out = (C.c_double * 3)(0.0, 0.0, 0.0)
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_ls_terms(_ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), out, _ptr(ws),
-                                         _stream())
-    _lib.check(rc, "accbpg_ls_terms", "Entries of x or y not positive.")
+    _call("accbpg_ls_terms", x, _ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), out, _WS,
+          assert_msg="Entries of x or y not positive.")
     # NumPy scalars, as the reference's sums are (accbpg/functions.py:253): D(x+,y) / D(z+,z) with D(z+,z) == 0 --
     # an iterate that has stopped moving -- is then inf or nan with a warning, as in the reference, not an exception
     # (the stopping rule dzz < epsilon right behind it ends the run, accbpg/algorithms.py:155,174)
@@ -1030,11 +1013,8 @@ def combine_ls_terms(h, a, u, b, v, c, g=None, x=None):
     kind = 1 if isinstance(h, SquaredL2Norm) else 0
     w = torch.empty_like(u)
     out = (C.c_double * 2)(0.0, 0.0)
-    with torch.cuda.device(u.device):
-        ws = _Workspace.get(u.numel(), u.device) if x is not None else None
-        rc = _lib.load().accbpg_combine_ls_terms(kind, float(a), _ptr(u), float(b), _ptr(v), float(c), _ptr(g), _ptr(x),
-                                                 u.numel(), _ptr(w), out, _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_combine_ls_terms", "Entries of x or y not positive.")
+    _call("accbpg_combine_ls_terms", u, kind, float(a), _ptr(u), float(b), _ptr(v), float(c), _ptr(g), _ptr(x),
+          u.numel(), _ptr(w), out, _WS if x is not None else _ptr(None), assert_msg="Entries of x or y not positive.")
     if x is None:
         return w, None, None
     return w, np.float64(out[0]), np.float64(out[1])
@@ -1043,40 +1023,28 @@ def combine_ls_terms(h, a, u, b, v, c, g=None, x=None):
 def shannon_ls_terms(g, x, y, z=None, z1=None, delta=1e-20):
     """(<g,x-y>, D(x,y), D(z,z1)) of the Shannon entropy in one streaming pass and one readback (g None: 0)."""
     out = (C.c_double * 3)(0.0, 0.0, 0.0)
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_shannon_ls_terms(_ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(),
-                                                 float(delta), out, _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_shannon_ls_terms", "Some entries are negative.")
+    _call("accbpg_shannon_ls_terms", x, _ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), float(delta), out,
+          _WS, assert_msg="Some entries are negative.")
     return np.float64(out[0]), np.float64(out[1]), np.float64(out[2])
 
 
 def quartic_ls_terms(g, x, y, z=None, z1=None):
     """(<g,x-y>, ||x||^2, ||y||^2, <y,x-y>, ||z||^2, ||z1||^2, <z1,z-z1>) in one streaming pass and one readback."""
     out = (C.c_double * 7)()
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_quartic_ls_terms(_ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), out,
-                                                 _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_quartic_ls_terms")
+    _call("accbpg_quartic_ls_terms", x, _ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), out, _WS)
     return tuple(out)
 
 
 def vec_min_sum(x):
     out = (C.c_double * 2)(0.0, 0.0)
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_vec_min_sum(_ptr(x), x.numel(), out, _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_vec_min_sum")
+    _call("accbpg_vec_min_sum", x, _ptr(x), x.numel(), out, _WS)
     return out[0], out[1]
 
 
 def vec_div_scalar(x, d):
     """x / d elementwise (NumPy true division)."""
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().accbpg_vec_div_scalar(_ptr(x), float(d), x.numel(), _ptr(out), _stream())
-    _lib.check(rc, "accbpg_vec_div_scalar")
+    _call("accbpg_vec_div_scalar", x, _ptr(x), float(d), x.numel(), _ptr(out))
     return out
 
 
@@ -1084,16 +1052,11 @@ def vec_argminmax(x):
     """(first argmin, first argmax, min, max) of a device vector."""
     idx = (C.c_int64 * 2)(0, 0)
     val = (C.c_double * 2)(0.0, 0.0)
-    with torch.cuda.device(x.device):
-        ws = _Workspace.get(x.numel(), x.device)
-        rc = _lib.load().accbpg_vec_argminmax(_ptr(x), x.numel(), idx, val, _ptr(ws), _stream())
-    _lib.check(rc, "accbpg_vec_argminmax")
+    _call("accbpg_vec_argminmax", x, _ptr(x), x.numel(), idx, val, _WS)
     return idx[0], idx[1], val[0], val[1]
 
 
 def vec_vertex(idx, value, fill, n, device):
     out = torch.empty(n, dtype=torch.float64, device=device)
-    with torch.cuda.device(device):
-        rc = _lib.load().accbpg_vec_vertex(int(idx), float(value), float(fill), int(n), _ptr(out), _stream())
-    _lib.check(rc, "accbpg_vec_vertex")
+    _call("accbpg_vec_vertex", out, int(idx), float(value), float(fill), int(n), _ptr(out))
     return out

@@ -99,6 +99,21 @@ def _drain(gen):
             return stop.value
 
 
+def _fw_decide(m, w_i, w_j, eps):
+    """The scalar decisions of one Frank-Wolfe iteration, as the reference writes them (D_opt_alg.py:63-64, :72,
+    :75-80), from the probe's w_i = max w and w_j = min of w over the support.  Returns (eps_pos, eps_neg, update,
+    detmul): update = (xscale, xadd, hcoef, hdiv) of the rank-one update with pivot i, or None when the stop test
+    holds; detmul the factor det(V X V^T) takes (:80).  One copy for the single and the lock-step solver."""
+    eps_pos = w_i / m - 1                                       # :63
+    eps_neg = 1 - w_j / m                                       # :64
+    if eps_pos <= eps and eps_neg <= eps:                       # :72
+        return eps_pos, eps_neg, None, None
+    t = (w_i / m - 1) / (w_i - 1)                               # :75
+    coef = t / (1 + t * (w_i - 1))                              # :79,:82
+    detmul = np.power(1 - t, m - 1) * (1 + t * (w_i - 1))       # :80
+    return eps_pos, eps_neg, (1 - t, t, -coef, 1 - t), detmul   # :76-79,:82
+
+
 def D_opt_FW(V, x0, eps, maxitrs, verbose=True, verbskip=1):
     """Frank-Wolfe with exact line search (accbpg/D_opt_alg.py:9-88).
     Returns (x, F, SP, SN, T).  F[k] = -log(detVXVT) with the determinant tracked by
@@ -127,9 +142,7 @@ def D_opt_FW_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1):
         F[k] = - np.log(detVXVT)                                # :52
         T[k] = time.time() - start_time
         pr = st.probe(away=0, refresh_logdet=0)                 # :59-61
-        w_i = pr.w_i
-        eps_pos = w_i / m - 1                                   # :63
-        eps_neg = 1 - pr.w_j / m                                # :64
+        eps_pos, eps_neg, upd, detmul = _fw_decide(m, pr.w_i, pr.w_j, eps)
         SP[k] = eps_pos
         SN[k] = eps_neg
 
@@ -137,13 +150,11 @@ def D_opt_FW_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1):
             print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:10.3e}  {4:6.1f}".format(
                 k, F[k], eps_pos, eps_neg, T[k]))
 
-        if eps_pos <= eps and eps_neg <= eps:                   # :72
+        if upd is None:                                         # :72
             break
 
-        t = (w_i / m - 1) / (w_i - 1)                           # :75
-        coef = t / (1 + t * (w_i - 1))                          # :79,:82
-        st.update(pr.i, 1 - t, t, -coef, 1 - t)                 # :76-79,:82
-        detVXVT *= np.power(1 - t, m - 1) * (1 + t * (w_i - 1))  # :80
+        st.update(pr.i, *upd)                                   # :76-79,:82
+        detVXVT *= detmul                                       # :80
         yield k
 
     return st.x(), F[0:k + 1], SP[0:k + 1], SN[0:k + 1], T[0:k + 1]
@@ -158,6 +169,110 @@ def D_opt_FW_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1):
 # factorisations in flight (1520 with one).  The every-iteration form stays one keyword away (logdet_refresh=1).
 LOGDET_REFRESH_DEFAULT = 16
 LOGDET_RING_DEFAULT = 3
+
+
+def _away_modes(logdet_refresh, logdet_ring):
+    """(R, depth) of D_opt_FW_away's ``logdet_refresh`` / ``logdet_ring`` keywords."""
+    R = LOGDET_REFRESH_DEFAULT if logdet_refresh is None else int(logdet_refresh)
+    depth = LOGDET_RING_DEFAULT if logdet_ring is None else int(logdet_ring)
+    if R != 1:
+        depth = 1                                               # anchors are R iterations apart: one in flight is enough
+    return R, depth
+
+
+class _AwayRun:
+    """Host side of ONE away-step run: the traces, the bookkeeping of F[k] = log det(H_k) (anchors in flight, log-space
+    steps between them) and the scalar decisions of an iteration as the reference writes them (D_opt_alg.py:150-179).
+    One copy for the single and the lock-step solver.
+
+    F[k] is filled in (and its table row printed) when its value is in: an anchor -- a fresh factorisation of H_a
+    started at iteration a on a side stream -- arrives `depth` refreshing iterations later; the iterations between
+    two anchors follow from the first by the log-space steps, each known one probe after its update (q_prev)."""
+
+    def __init__(self, m, maxitrs, R, depth, verbose=False, verbskip=1):
+        self.m, self.R, self.depth = m, R, depth
+        self.verbose, self.verbskip = verbose, verbskip
+        self.F = np.zeros(maxitrs)
+        self.SP = np.zeros(maxitrs)
+        self.SN = np.zeros(maxitrs)
+        self.T = np.zeros(maxitrs)
+        self.anchors = []            # iterations whose factorisation is in flight, oldest first
+        self.delta = np.zeros(maxitrs)   # delta[k] = log det(H_{k+1}) - log det(H_k) by the determinant lemma
+        self.filled = 0              # F[0:filled] is final
+        self.step = None             # (hcoef, hdiv) of the update applied at the previous iteration
+        self.k = -1                  # last iteration that ran
+
+    def refresh(self, k):
+        """Does iteration k start a factorisation of H_k?"""
+        return (self.R > 0) and (k % self.R == 0)
+
+    def fill(self, upto):
+        """F[filled:upto] from F[filled-1] by the log-space steps (upto exclusive), and print their rows."""
+        for j in range(self.filled, upto):
+            self.F[j] = self.F[j - 1] + self.delta[j - 1]
+            self.row(j)
+        self.filled = max(self.filled, upto)
+
+    def row(self, j):
+        if self.verbose and j % self.verbskip == 0:
+            print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:10.3e}  {4:6.1f}".format(j, self.F[j], self.SP[j], self.SN[j],
+                                                                             self.T[j]))
+
+    def settle(self, a, value):
+        """The anchor of iteration a is in."""
+        self.fill(a)
+        self.F[a] = value
+        self.row(a)
+        self.filled = a + 1
+
+    def iterate(self, k, pr, collected, now, logdet_gram, eps):
+        """Iteration k from its probe record `pr`; `collected`: the anchor value that came in with this iteration's
+        snapshot (refreshing iterations only).  Returns (p, xscale, xadd, hcoef, hdiv) of the update, or None when the
+        stop test holds."""
+        m = self.m
+        self.k = k
+        self.T[k] = now
+        if self.step is not None:
+            hcoef, hdiv = self.step
+            arg = hcoef * pr.q_prev
+            self.delta[k - 1] = (math.log1p(arg) - m * math.log(hdiv)) if (arg > -1.0 and hdiv > 0.0) else float("nan")
+        if self.refresh(k):
+            if len(self.anchors) >= self.depth:
+                self.settle(self.anchors.pop(0), collected)
+            self.anchors.append(k)
+        elif self.R == 0 and k == 0:
+            self.F[0] = -logdet_gram
+            self.filled = 1
+        w_i, w_j = pr.w_i, pr.w_j
+        eps_pos = w_i / m - 1                                   # :150
+        eps_neg = 1 - w_j / m                                   # :151
+        self.SP[k] = eps_pos
+        self.SN[k] = eps_neg
+        if self.R == 0 and k == 0:
+            self.row(0)
+
+        if eps_pos <= eps and eps_neg <= eps:                   # :159
+            return None
+
+        if eps_pos >= eps_neg:                                  # :162-170
+            t = (w_i / m - 1) / (w_i - 1)
+            coef = t / (1 - t + t * w_i)
+            self.step = (-coef, 1 - t)
+            return (pr.i, 1 - t, t, -coef, 1 - t)
+        x_j = pr.x_j                                            # :171-179
+        t = min((1 - w_j / m) / (w_j - 1), x_j / (1 - x_j))
+        coef = t / (1 + t - t * w_j)
+        self.step = (coef, 1 + t)
+        return (pr.j, 1 + t, -t, coef, 1 + t)
+
+    def finish(self, flush):
+        """Collect the anchors still in flight (`flush()` returns the oldest) and fill F to the end; returns
+        (F, SP, SN, T) cut to the iterations that ran."""
+        while self.anchors:
+            self.settle(self.anchors.pop(0), flush())
+        self.fill(self.k + 1)
+        e = self.k + 1
+        return self.F[0:e], self.SP[0:e], self.SN[0:e], self.T[0:e]
 
 
 def D_opt_FW_away(V, x0, eps, maxitrs, verbose=True, verbskip=1, logdet_refresh=None, logdet_ring=None):
@@ -180,90 +295,136 @@ def D_opt_FW_away_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1, logdet_re
     """Generator form of D_opt_FW_away: yields k after each update, returns D_opt_FW_away's tuple."""
     start_time = time.time()
     st = _FWState(V, x0)
-    m = st.m
-    F = np.zeros(maxitrs)
-    SP = np.zeros(maxitrs)
-    SN = np.zeros(maxitrs)
-    T = np.zeros(maxitrs)
-    R = LOGDET_REFRESH_DEFAULT if logdet_refresh is None else int(logdet_refresh)
-    depth = LOGDET_RING_DEFAULT if logdet_ring is None else int(logdet_ring)
-    if R != 1:
-        depth = 1                                               # anchors are R iterations apart: one in flight is enough
+    R, depth = _away_modes(logdet_refresh, logdet_ring)
     st.logdet_ring(depth)
+    run = _AwayRun(st.m, maxitrs, R, depth, verbose, verbskip)
 
     if verbose:
         print("\nSolving D-opt design problem using Frank-Wolfe method with away steps")
         print("     k      F(x)     pos_slack   neg_slack    time")
 
-    # F[k] is filled in (and its table row printed) when its value is in: an anchor -- a fresh factorisation of H_a
-    # started at iteration a on a side stream -- arrives `depth` refreshing iterations later; the iterations between
-    # two anchors follow from the first by the log-space steps, each known one probe after its update (q_prev).
-    anchors = []            # iterations whose factorisation is in flight, oldest first
-    delta = np.zeros(maxitrs)   # delta[k] = log det(H_{k+1}) - log det(H_k) by the determinant lemma
-    filled = 0              # F[0:filled] is final
-    step = None             # (hcoef, hdiv) of the update applied at the previous iteration
-
-    def fill(upto):
-        """F[filled:upto] from F[filled-1] by the log-space steps (upto exclusive), and print their rows."""
-        nonlocal filled
-        for j in range(filled, upto):
-            F[j] = F[j - 1] + delta[j - 1]
-            row(j)
-        filled = max(filled, upto)
-
-    def row(j):
-        if verbose and j % verbskip == 0:
-            print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:10.3e}  {4:6.1f}".format(j, F[j], SP[j], SN[j], T[j]))
-
-    def settle(a, value):
-        """The anchor of iteration a is in."""
-        nonlocal filled
-        fill(a)
-        F[a] = value
-        row(a)
-        filled = a + 1
-
-    k = -1
     for k in range(maxitrs):
-        refresh = (R > 0) and (k % R == 0)
-        pr = st.probe(away=1, refresh_logdet=2 if refresh else 0)   # :136, :145-147
-        T[k] = time.time() - start_time
-        if step is not None:
-            hcoef, hdiv = step
-            arg = hcoef * pr.q_prev
-            delta[k - 1] = (math.log1p(arg) - m * math.log(hdiv)) if (arg > -1.0 and hdiv > 0.0) else float("nan")
-        if refresh:
-            if len(anchors) >= depth:
-                settle(anchors.pop(0), pr.logdet_H)
-            anchors.append(k)
-        elif R == 0 and k == 0:
-            F[0] = -st.logdet_gram
-            filled = 1
-        w_i, w_j = pr.w_i, pr.w_j
-        eps_pos = w_i / m - 1                                   # :150
-        eps_neg = 1 - w_j / m                                   # :151
-        SP[k] = eps_pos
-        SN[k] = eps_neg
-        if R == 0 and k == 0:
-            row(0)
-
-        if eps_pos <= eps and eps_neg <= eps:                   # :159
+        pr = st.probe(away=1, refresh_logdet=2 if run.refresh(k) else 0)   # :136, :145-147
+        upd = run.iterate(k, pr, pr.logdet_H, time.time() - start_time, st.logdet_gram, eps)
+        if upd is None:                                         # :159
             break
-
-        if eps_pos >= eps_neg:                                  # :162-170
-            t = (w_i / m - 1) / (w_i - 1)
-            coef = t / (1 - t + t * w_i)
-            step = (-coef, 1 - t)
-            st.update(pr.i, 1 - t, t, -coef, 1 - t)
-        else:                                                   # :171-179
-            x_j = pr.x_j
-            t = min((1 - w_j / m) / (w_j - 1), x_j / (1 - x_j))
-            coef = t / (1 + t - t * w_j)
-            step = (coef, 1 + t)
-            st.update(pr.j, 1 + t, -t, coef, 1 + t)
+        st.update(*upd)
         yield k
 
-    while anchors:
-        settle(anchors.pop(0), st.flush_logdet())
-    fill(k + 1)
-    return st.x(), F[0:k + 1], SP[0:k + 1], SN[0:k + 1], T[0:k + 1]
+    F, SP, SN, T = run.finish(st.flush_logdet)
+    return st.x(), F, SP, SN, T
+
+
+# ---- lock-step batches -----------------------------------------------------------------------------------------------
+def _batch_x0(batch, x0):
+    """x0 (one vector or K x n) as a K x n device tensor with row stride n."""
+    x0d, as_numpy = to_dev(x0)
+    X = x0d.reshape(1, -1).repeat(batch.K, 1) if x0d.dim() == 1 else x0d.clone()
+    X = X.to(batch.device).contiguous()
+    assert X.shape == (batch.K, batch.n), "x0: one vector of length n, or a K x n array"
+    return X, as_numpy
+
+
+def _batch_eps(batch, eps):
+    """eps (a scalar, or one per instance) as a list of K floats."""
+    return [float(v) for v in np.broadcast_to(np.asarray(eps, dtype=np.float64), (batch.K,))]
+
+
+def D_opt_FW_batch(batch, x0, eps, maxitrs):
+    """D_opt_FW on the K instances of a ``DOptimalBatch`` in lock-step: every step kernel is launched once for the
+    instances that are still running, and one synchronisation returns all their probe records.  ``x0``: one vector
+    or a K x n array; ``eps``: a scalar or one per instance.  The decisions (stop test, step length, tracked
+    determinant) are kept per instance exactly as the sequential solver takes them; an instance that meets its stop
+    test drops out of the later launches.  Silent.  Returns a list of K tuples (x, F, SP, SN, T), x, F, SP and SN
+    bit-identical to ``D_opt_FW(batch.instance(i), x0_i, eps_i, maxitrs, verbose=False)``.
+
+    For a rank's share of many instances (``solve_instances`` hands a solver one problem at a time): build the batch
+    from the matrices of ``sharded.split_instances(N, world, rank)`` and call this on it."""
+    return _drain(D_opt_FW_batch_steps(batch, x0, eps, maxitrs))
+
+
+def D_opt_FW_batch_steps(batch, x0, eps, maxitrs):
+    """Generator form of D_opt_FW_batch: yields k after each lock-step update, returns D_opt_FW_batch's list."""
+    start_time = time.time()
+    K, m = batch.K, batch.m
+    X0, as_numpy = _batch_x0(batch, x0)
+    epsv = _batch_eps(batch, eps)
+    logdet = batch.fw_init(X0)
+    F = np.zeros((K, maxitrs)); SP = np.zeros((K, maxitrs)); SN = np.zeros((K, maxitrs)); T = np.zeros((K, maxitrs))
+    detVXVT = [np.exp(ld) for ld in logdet]                     # :41
+    active = [True] * K
+    last = [-1] * K
+    upd = [None] * K
+    for k in range(maxitrs):
+        if not any(active):
+            break
+        now = time.time() - start_time
+        for i in range(K):
+            if active[i]:
+                F[i, k] = - np.log(detVXVT[i])                  # :52
+                T[i, k] = now
+        prs = batch.fw_probe(0, active)                         # :59-61
+        for i in range(K):
+            if not active[i]:
+                continue
+            SP[i, k], SN[i, k], u, detmul = _fw_decide(m, prs[i].w_i, prs[i].w_j, epsv[i])
+            last[i] = k
+            if u is None:                                       # :72
+                active[i] = False
+                continue
+            upd[i] = (prs[i].i,) + u
+            detVXVT[i] *= detmul                                # :80
+        if not any(active):
+            break
+        batch.fw_update(active, upd)                            # :76-79,:82
+        yield k
+    out = []
+    for i in range(K):
+        e = last[i] + 1
+        out.append((batch.fw_x(i, as_numpy), F[i, :e].copy(), SP[i, :e].copy(), SN[i, :e].copy(), T[i, :e].copy()))
+    return out
+
+
+def D_opt_FW_away_batch(batch, x0, eps, maxitrs, logdet_refresh=None, logdet_ring=None):
+    """D_opt_FW_away on the K instances of a ``DOptimalBatch`` in lock-step (see ``D_opt_FW_batch``).  F[k] =
+    log det(H_k) is formed per instance as the sequential solver forms it -- ``logdet_refresh`` / ``logdet_ring`` as
+    there, each instance's side factorisations on its own handle's ring -- so F, too, is bit-identical to
+    ``D_opt_FW_away(batch.instance(i), x0_i, eps_i, maxitrs, verbose=False, logdet_refresh=..., logdet_ring=...)``."""
+    return _drain(D_opt_FW_away_batch_steps(batch, x0, eps, maxitrs, logdet_refresh, logdet_ring))
+
+
+def D_opt_FW_away_batch_steps(batch, x0, eps, maxitrs, logdet_refresh=None, logdet_ring=None):
+    """Generator form of D_opt_FW_away_batch: yields k after each lock-step update, returns its list."""
+    start_time = time.time()
+    K, m = batch.K, batch.m
+    X0, as_numpy = _batch_x0(batch, x0)
+    epsv = _batch_eps(batch, eps)
+    R, depth = _away_modes(logdet_refresh, logdet_ring)
+    logdet = batch.fw_init(X0)
+    batch.fw_logdet_ring(depth)
+    runs = [_AwayRun(m, maxitrs, R, depth) for _ in range(K)]
+    active = [True] * K
+    upd = [None] * K
+    nan = float("nan")
+    for k in range(maxitrs):
+        if not any(active):
+            break
+        # anchors: a snapshot of H_k per running instance, each factored beside the steps on its own handle's ring
+        collected = batch.fw_logdet_snapshot(active) if runs[0].refresh(k) else [nan] * K      # :136
+        prs = batch.fw_probe(1, active)                         # :145-147
+        now = time.time() - start_time
+        for i in range(K):
+            if not active[i]:
+                continue
+            upd[i] = runs[i].iterate(k, prs[i], collected[i], now, logdet[i], epsv[i])
+            if upd[i] is None:                                  # :159
+                active[i] = False
+        if not any(active):
+            break
+        batch.fw_update(active, upd)
+        yield k
+    out = []
+    for i in range(K):
+        F, SP, SN, T = runs[i].finish(lambda i=i: batch.fw_logdet_flush(i))
+        out.append((batch.fw_x(i, as_numpy), F.copy(), SP.copy(), SN.copy(), T.copy()))
+    return out

@@ -86,6 +86,12 @@ _SIGS = {
     "accbpg_fw_logdet_pending": (C.c_int, [_P]),
     "accbpg_fw_update": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "accbpg_fw_get_state": (C.c_int, [_P, _P, _P, _P]),
+    "accbpg_fw_logdet_snapshot": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "accbpg_dopt_batch_fw_init": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int)]),
+    "accbpg_dopt_batch_fw_probe": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(FwProbe)]),
+    "accbpg_dopt_batch_fw_update": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "accbpg_poisson_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(_P)]),
     "accbpg_poisson_destroy": (C.c_int, [_P]),
     "accbpg_poisson_set_stream": (C.c_int, [_P, _P]),

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .functions import DOptimalObj, _ptr, _stream, to_dev
+from .functions import DOptimalObj, _ptr, _stream, from_dev, to_dev
 
 
 class DOptimalBatch:
@@ -49,6 +49,9 @@ class DOptimalBatch:
         self.chunk = int(self._lib.accbpg_dopt_batch_chunk(h))      # instances one launch covers
         self.calls = {"value": 0, "grad": 0}        # per instance-evaluation, as DOptimalObj counts them
         self._views = {}
+        # host arrays of the lock-step Frank-Wolfe calls (probe records; p, xscale, xadd, hcoef, hdiv of an update)
+        self._fw_probes = (_lib.FwProbe * self.K)()
+        self._fw_args = ((C.c_int64 * self.K)(),) + tuple((C.c_double * self.K)() for _ in range(4))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -215,6 +218,89 @@ class DOptimalBatch:
             rc = self._lib.accbpg_dopt_batch_axpby(self._h, av, _ptr(X), bv, _ptr(Z), self.n, mask, _ptr(out))
         _lib.check(rc, "accbpg_dopt_batch_axpby")
         return out
+
+
+    # ---- Frank-Wolfe steps in lock-step (C-ABI ``accbpg_dopt_batch_fw_*``); the state lives in the instance handles ----
+    def _inst_h(self, i):
+        return self.instance(i)._h
+
+    def fw_init(self, X0, active=None):
+        """``accbpg_fw_init`` for the active instances from the rows of X0 (K x n); returns log det(V_i diag(x0_i) V_i^T)
+        per instance (nan for inactive ones).  A singular instance raises as the single solver does."""
+        self._rows(X0=X0)
+        mask, idx = self._mask(active)
+        ld = (C.c_double * self.K)(*([float("nan")] * self.K))
+        st = (C.c_int * self.K)()
+        with torch.cuda.device(self.device):
+            self._lib.accbpg_dopt_batch_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_dopt_batch_fw_init(self._h, _ptr(X0), self.n, mask, ld, st)
+        _lib.check(rc, "accbpg_dopt_batch_fw_init")
+        self._raise(st, idx, "accbpg_dopt_batch_fw_init", None)
+        return list(ld)
+
+    def fw_probe(self, away, active=None):
+        """One probe of the active instances: one launch chain, one synchronisation.  Returns the K records
+        (``_lib.FwProbe``; those of inactive instances are stale), ``logdet_H`` nan."""
+        mask, _ = self._mask(active)
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_dopt_batch_fw_probe(self._h, int(away), mask, self._fw_probes)
+        if rc:
+            _lib.check(rc, "accbpg_dopt_batch_fw_probe")
+        return self._fw_probes
+
+    def fw_update(self, active, updates):
+        """One rank-one update per active instance: updates[i] = (p, xscale, xadd, hcoef, hdiv)."""
+        mask, idx = self._mask(active)
+        p, xs, xa, hc, hd = self._fw_args
+        for i in idx:
+            p[i], xs[i], xa[i], hc[i], hd[i] = updates[i]
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_dopt_batch_fw_update(self._h, mask, p, xs, xa, hc, hd)
+        if rc:
+            _lib.check(rc, "accbpg_dopt_batch_fw_update")
+
+    def fw_logdet_ring(self, depth, small_launches=2):
+        """``accbpg_fw_logdet_ring`` on every instance handle."""
+        with torch.cuda.device(self.device):
+            for i in range(self.K):
+                _lib.check(self._lib.accbpg_fw_logdet_ring(self._inst_h(i), int(depth), int(small_launches)),
+                           "accbpg_fw_logdet_ring")
+
+    def fw_logdet_snapshot(self, active=None):
+        """``accbpg_fw_logdet_snapshot`` on the active instances' handles: each snapshots its H into its own ring and
+        starts the side factorisation.  Returns, per instance, the value of the slot that came round (nan: none)."""
+        _, idx = self._mask(active)
+        out = [float("nan")] * self.K
+        val = C.c_double(0.0)
+        with torch.cuda.device(self.device):
+            for i in idx:
+                _lib.check(self._lib.accbpg_fw_logdet_snapshot(self._inst_h(i), C.byref(val)), "accbpg_fw_logdet_snapshot")
+                out[i] = val.value
+        return out
+
+    def fw_logdet_flush(self, i):
+        """The oldest side factorisation of instance i still in flight (``accbpg_fw_logdet_flush``)."""
+        val = C.c_double(0.0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.accbpg_fw_logdet_flush(self._inst_h(i), C.byref(val)), "accbpg_fw_logdet_flush")
+        return val.value
+
+    def fw_state(self, i):
+        """(x, w, H) of instance i as device tensors (``accbpg_fw_get_state`` on its handle)."""
+        x = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        w = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        H = torch.empty(self.m, self.m, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_fw_get_state(self._inst_h(i), _ptr(x), _ptr(w), _ptr(H))
+        _lib.check(rc, "accbpg_fw_get_state")
+        return x, w, H
+
+    def fw_x(self, i, as_numpy=True):
+        x = torch.empty(self.n, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_fw_get_state(self._inst_h(i), _ptr(x), None, None)
+        _lib.check(rc, "accbpg_fw_get_state")
+        return from_dev(x, as_numpy)
 
 
 def ABPG_batch_steps(batch, h, L, x0, gamma, maxitrs, epsilon=1e-14, theta_eq=False, restart=False, restart_rule='g',

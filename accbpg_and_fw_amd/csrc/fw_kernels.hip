@@ -59,7 +59,7 @@ __device__ __forceinline__ ValIdx block_reduce_vi_n(ValIdx a, ValIdx* sh) {
 // away index j = argmin((w - w_i) * [x > 1e-8]) (:146-147) is taken on the ROUNDED differences, and two
 // masked entries with different w can round to the same difference from a much larger w_i, in which case
 // NumPy returns the first of them: stage 2 therefore evaluates that expression itself once w_i is known.
-__global__ __launch_bounds__(FB) void fw_probe_partial_kernel(const double* __restrict__ w,
+__device__ __forceinline__ void fw_probe_partial_body(const double* __restrict__ w,
                                                              const double* __restrict__ x, int64_t n, int away,
                                                              ValIdx* __restrict__ part) {
     __shared__ ValIdx sh[FB / 64];
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(FB) void fw_probe_partial_kernel(const double* __re
 }
 
 // stage 2: combine the partials (block order), resolve the all-zero case, fetch w_j and x_j
-__global__ __launch_bounds__(FB) void fw_probe_final_kernel(const ValIdx* __restrict__ part, int nblk,
+__device__ __forceinline__ void fw_probe_final_body(const ValIdx* __restrict__ part, int nblk,
                                                            const double* __restrict__ w,
                                                            const double* __restrict__ x, int64_t n, int away,
                                                            double* __restrict__ dout, int64_t* __restrict__ iout,
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(FB) void fw_probe_final_kernel(const ValIdx* __rest
 // first-index minimum of d_k = (w_k - w_i) * [x_k > 1e-8] -- formed exactly as the reference forms it, D_opt_alg.py:146-147
 // -- over its slice; workgroup 0 leaves (w_i, i) for the final stage.
 constexpr int AWAY_NB = 128;        // at most this many slices
-__global__ __launch_bounds__(FB) void fw_probe_away_partial_kernel(const ValIdx* __restrict__ part, int nblk,
+__device__ __forceinline__ void fw_probe_away_partial_body(const ValIdx* __restrict__ part, int nblk,
                                                                   const double* __restrict__ w,
                                                                   const double* __restrict__ x, int64_t n,
                                                                   ValIdx* __restrict__ part2, ValIdx* __restrict__ mxslot) {
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(FB) void fw_probe_away_partial_kernel(const ValIdx*
         if (blockIdx.x == 0) *mxslot = mx;
     }
 }
-__global__ __launch_bounds__(FB) void fw_probe_away_final_kernel(const ValIdx* __restrict__ part2, int nb2,
+__device__ __forceinline__ void fw_probe_away_final_body(const ValIdx* __restrict__ part2, int nb2,
                                                                 const ValIdx* __restrict__ mxslot,
                                                                 const double* __restrict__ w,
                                                                 const double* __restrict__ x, int64_t n,
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(FB) void fw_probe_away_final_kernel(const ValIdx* _
 }
 
 // x <- x*xscale; x[p] += xadd   (D_opt_alg.py:76-77,164-165,173-174); vp <- V[:,p]
-__global__ __launch_bounds__(FB) void fw_xupdate_gather_kernel(double* __restrict__ x, int64_t n, int64_t p,
+__device__ __forceinline__ void fw_xupdate_gather_body(double* __restrict__ x, int64_t n, int64_t p,
                                                               double xscale, double xadd,
                                                               const double* __restrict__ V, int64_t ldv, int64_t m,
                                                               double* __restrict__ vp) {
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(FB) void fw_xupdate_gather_kernel(double* __restric
 }
 
 // hv = H vp, one wave per row of H          (np.dot(H, V[:,i]), D_opt_alg.py:78,166,175)
-__global__ __launch_bounds__(FB) void fw_gemv_h_kernel(const double* __restrict__ H, int64_t m,
+__device__ __forceinline__ void fw_gemv_h_body(const double* __restrict__ H, int64_t m,
                                                       const double* __restrict__ vp, double* __restrict__ hv) {
     // one wave per PAIR of rows (twice the loads in flight per wave; the per-row summation order is that of one
     // row per wave)
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(FB) void fw_gemv_h_kernel(const double* __restrict_
 // tracked w_p drifts away from it: w is never refreshed, D_opt_alg.py:82): by the matrix determinant lemma
 // det(H+) = det(H) (1 + hcoef q) / hdiv^m holds for exactly this q, which is what the log-space advance of log det(H)
 // between two factorisations uses (accbpg_fw_probe: q_prev).
-__global__ __launch_bounds__(FB) void fw_rank1_kernel(double* __restrict__ H, int64_t m,
+__device__ __forceinline__ void fw_rank1_body(double* __restrict__ H, int64_t m,
                                                      const double* __restrict__ hv, double hcoef, double hdiv,
                                                      const double* __restrict__ vp, double* __restrict__ qout) {
     if (blockIdx.x == 0) {
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(FB) void fw_rank1_kernel(double* __restrict__ H, in
 }
 
 // partial u[s][k] = sum over the rows of split s of hv[r]*V[r][k]; two columns per thread
-__global__ __launch_bounds__(FB) void fw_vgemv_partial_kernel(const double* __restrict__ V, int64_t ldv, int64_t m,
+__device__ __forceinline__ void fw_vgemv_partial_body(const double* __restrict__ V, int64_t ldv, int64_t m,
                                                              int64_t n, const double* __restrict__ hv, int nsplit,
                                                              double* __restrict__ upart, bool vec_ok) {
     const int64_t k = (int64_t)blockIdx.x * VG_COLS + 2 * threadIdx.x;
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(FB) void fw_wupdate_kernel(double* __restrict__ w, 
 
 // The same update fused with stage 1 of the NEXT iteration's probe (fw_probe_partial_kernel): the new w
 // is in registers anyway, x was updated earlier in this step.
-__global__ __launch_bounds__(FB) void fw_wupdate_probe_kernel(double* __restrict__ w, int64_t n,
+__device__ __forceinline__ void fw_wupdate_probe_body(double* __restrict__ w, int64_t n,
                                                              const double* __restrict__ upart, int nsplit,
                                                              double hcoef, double hdiv,
                                                              const double* __restrict__ x, int away,
@@ -359,6 +359,124 @@ __global__ __launch_bounds__(FB) void fw_wupdate_probe_kernel(double* __restrict
         part[2 * blockIdx.x] = mx;
         part[2 * blockIdx.x + 1] = mn;
     }
+}
+
+// ---- the step kernels: one instance (the handle's pointers as arguments) ----------------------------------------
+// Each is a thin wrapper round the body above; the lock-step forms below wrap the SAME bodies, so an instance of a
+// batch goes through the very arithmetic, partition and summation order of the single handle.
+__global__ __launch_bounds__(FB) void fw_probe_partial_kernel(const double* __restrict__ w,
+                                                             const double* __restrict__ x, int64_t n, int away,
+                                                             ValIdx* __restrict__ part) {
+    fw_probe_partial_body(w, x, n, away, part);
+}
+__global__ __launch_bounds__(FB) void fw_probe_final_kernel(const ValIdx* __restrict__ part, int nblk,
+                                                           const double* __restrict__ w,
+                                                           const double* __restrict__ x, int64_t n, int away,
+                                                           double* __restrict__ dout, int64_t* __restrict__ iout,
+                                                           const double* __restrict__ qsrc) {
+    fw_probe_final_body(part, nblk, w, x, n, away, dout, iout, qsrc);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_partial_kernel(const ValIdx* __restrict__ part, int nblk,
+                                                                  const double* __restrict__ w,
+                                                                  const double* __restrict__ x, int64_t n,
+                                                                  ValIdx* __restrict__ part2, ValIdx* __restrict__ mxslot) {
+    fw_probe_away_partial_body(part, nblk, w, x, n, part2, mxslot);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_final_kernel(const ValIdx* __restrict__ part2, int nb2,
+                                                                const ValIdx* __restrict__ mxslot,
+                                                                const double* __restrict__ w,
+                                                                const double* __restrict__ x, int64_t n,
+                                                                double* __restrict__ dout, int64_t* __restrict__ iout,
+                                                                const double* __restrict__ qsrc) {
+    fw_probe_away_final_body(part2, nb2, mxslot, w, x, n, dout, iout, qsrc);
+}
+__global__ __launch_bounds__(FB) void fw_xupdate_gather_kernel(double* __restrict__ x, int64_t n, int64_t p,
+                                                              double xscale, double xadd,
+                                                              const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                              double* __restrict__ vp) {
+    fw_xupdate_gather_body(x, n, p, xscale, xadd, V, ldv, m, vp);
+}
+__global__ __launch_bounds__(FB) void fw_gemv_h_kernel(const double* __restrict__ H, int64_t m,
+                                                      const double* __restrict__ vp, double* __restrict__ hv) {
+    fw_gemv_h_body(H, m, vp, hv);
+}
+__global__ __launch_bounds__(FB) void fw_rank1_kernel(double* __restrict__ H, int64_t m,
+                                                     const double* __restrict__ hv, double hcoef, double hdiv,
+                                                     const double* __restrict__ vp, double* __restrict__ qout) {
+    fw_rank1_body(H, m, hv, hcoef, hdiv, vp, qout);
+}
+__global__ __launch_bounds__(FB) void fw_vgemv_partial_kernel(const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                             int64_t n, const double* __restrict__ hv, int nsplit,
+                                                             double* __restrict__ upart, bool vec_ok) {
+    fw_vgemv_partial_body(V, ldv, m, n, hv, nsplit, upart, vec_ok);
+}
+__global__ __launch_bounds__(FB) void fw_wupdate_probe_kernel(double* __restrict__ w, int64_t n,
+                                                             const double* __restrict__ upart, int nsplit,
+                                                             double hcoef, double hdiv,
+                                                             const double* __restrict__ x, int away,
+                                                             ValIdx* __restrict__ part) {
+    fw_wupdate_probe_body(w, n, upart, nsplit, hcoef, hdiv, x, away, part);
+}
+
+// ---- the step kernels: the active instances of a batch in lock-step ----------------------------------------------
+// The instance is a grid dimension (blockIdx.z for the pass over V, whose blockIdx.y is the row split; blockIdx.y
+// elsewhere); blockIdx.x and gridDim.x are what the single launch of that instance has, so the bodies partition and
+// sum as they do there.  Pointers come from the batch's device table (FwInst), the active set and the per-instance
+// scalars travel by value in the kernel arguments: no second synchronisation per step.
+__device__ __forceinline__ ValIdx* fw_part_of(const FwInst& t, int64_t m) {
+    return reinterpret_cast<ValIdx*>(t.hv + 2 * m);             // 2*512 stage-1 records behind Hv / vp
+}
+__global__ __launch_bounds__(FB) void fw_probe_partial_batch_kernel(const FwInst* __restrict__ tab, BatchAct act,
+                                                                   int64_t m, int64_t n, int away) {
+    const FwInst t = tab[act.idx[blockIdx.y]];
+    fw_probe_partial_body(t.w, t.x, n, away, fw_part_of(t, m));
+}
+__global__ __launch_bounds__(FB) void fw_probe_final_batch_kernel(const FwInst* __restrict__ tab, FwProbeArgs pa,
+                                                                 int64_t m, int64_t n, int away) {
+    const FwInst t = tab[pa.idx[blockIdx.y]];
+    fw_probe_final_body(fw_part_of(t, m), pa.nblk[blockIdx.y], t.w, t.x, n, away, t.rec + 4,
+                        reinterpret_cast<int64_t*>(t.rec + 8), t.q);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_partial_batch_kernel(const FwInst* __restrict__ tab, FwProbeArgs pa,
+                                                                        int64_t m, int64_t n) {
+    const FwInst t = tab[pa.idx[blockIdx.y]];
+    ValIdx* part = fw_part_of(t, m);
+    ValIdx* part2 = part + 2 * 512;
+    fw_probe_away_partial_body(part, pa.nblk[blockIdx.y], t.w, t.x, n, part2, part2 + AWAY_NB);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_final_batch_kernel(const FwInst* __restrict__ tab, FwProbeArgs pa,
+                                                                      int nb2, int64_t m, int64_t n) {
+    const FwInst t = tab[pa.idx[blockIdx.y]];
+    ValIdx* part2 = fw_part_of(t, m) + 2 * 512;
+    fw_probe_away_final_body(part2, nb2, part2 + AWAY_NB, t.w, t.x, n, t.rec + 4, reinterpret_cast<int64_t*>(t.rec + 8),
+                             t.q);
+}
+__global__ __launch_bounds__(FB) void fw_xupdate_gather_batch_kernel(const FwInst* __restrict__ tab, FwUpdArgs ua,
+                                                                    int64_t m, int64_t n, int64_t ldv) {
+    const int a = blockIdx.y;
+    const FwInst t = tab[ua.idx[a]];
+    fw_xupdate_gather_body(t.x, n, ua.p[a], ua.xscale[a], ua.xadd[a], t.V, ldv, m, t.hv + m);
+}
+__global__ __launch_bounds__(FB) void fw_gemv_h_batch_kernel(const FwInst* __restrict__ tab, BatchAct act, int64_t m) {
+    const FwInst t = tab[act.idx[blockIdx.y]];
+    fw_gemv_h_body(t.H, m, t.hv + m, t.hv);
+}
+__global__ __launch_bounds__(FB) void fw_rank1_batch_kernel(const FwInst* __restrict__ tab, FwUpdArgs ua, int64_t m) {
+    const int a = blockIdx.y;
+    const FwInst t = tab[ua.idx[a]];
+    fw_rank1_body(t.H, m, t.hv, ua.hcoef[a], ua.hdiv[a], t.hv + m, t.q);
+}
+__global__ __launch_bounds__(FB) void fw_vgemv_partial_batch_kernel(const FwInst* __restrict__ tab, BatchAct act,
+                                                                   int64_t ldv, int64_t m, int64_t n, int nsplit) {
+    const FwInst t = tab[act.idx[blockIdx.z]];
+    fw_vgemv_partial_body(t.V, ldv, m, n, t.hv, nsplit, t.vws, t.vec_ok != 0);
+}
+__global__ __launch_bounds__(FB) void fw_wupdate_probe_batch_kernel(const FwInst* __restrict__ tab, FwUpdArgs ua,
+                                                                   int64_t m, int64_t n, int nsplit) {
+    const int a = blockIdx.y;
+    const FwInst t = tab[ua.idx[a]];
+    fw_wupdate_probe_body(t.w, n, t.vws, nsplit, ua.hcoef[a], ua.hdiv[a], t.x, (int)((ua.awaymask >> a) & 1ull),
+                          fw_part_of(t, m));
 }
 
 // u = sum of the row-split partials (u = V^T q)
@@ -557,25 +675,36 @@ extern "C" int accbpg_fw_logdet_flush(accbpg_dopt* h, double* logdet_host) {
     return ACCBPG_OK;
 }
 
+// The refresh_logdet == 2 step on its own: snapshot H_k into the ring slot that comes round and start its side
+// factorisation; *collected_host is the value that slot held (the call made `depth` such calls ago), NaN if none.
+extern "C" int accbpg_fw_logdet_snapshot(accbpg_dopt* h, double* collected_host) {
+    if (!h || !collected_host || !h->fw_ready) return ACCBPG_ERR_ARG;
+    double logdet = __builtin_nan("");
+    *collected_host = logdet;
+    ACC_TRY(fw_ring_setup(h));
+    // the slot that comes round: collect what it holds -- the value of the call made `depth` such calls ago
+    if (h->fw_ring_issued - h->fw_ring_collected >= h->fw_ring_depth) ACC_TRY(accbpg_fw_logdet_flush(h, &logdet));
+    accbpg_dopt::FwSlot& sl = h->fw_ring[(size_t)(h->fw_ring_issued % h->fw_ring_depth)];
+    accbpg_dopt* a = sl.aux;
+    const int64_t T = (h->m + NB - 1) / NB;
+    if (!a->chol_tiles_off)
+        a->chol_tiles_off = h->fw_ring_small == 1 || (h->fw_ring_small == 2 && T * (T + 1) / 2 >= h->num_cu);
+    double* snap = chol_tiles_usable(a) ? a->Gbuf : a->Lbuf;
+    ACC_TRY(device_copy(snap, h->fw_H, (size_t)h->m * h->m, h->stream));   // H_k, in order with the updates
+    ACC_HIP(hipEventRecord(sl.ev_snap, h->stream));
+    ACC_HIP(hipStreamWaitEvent(sl.stream, sl.ev_snap, 0));
+    ACC_TRY(fw_slot_factor(sl, snap));
+    sl.pending = true;
+    ++h->fw_ring_issued;
+    *collected_host = logdet;
+    return ACCBPG_OK;
+}
+
 extern "C" int accbpg_fw_probe_step(accbpg_dopt* h, int away, int refresh_logdet, accbpg_fw_probe* out) {
     if (!h || !out || !h->fw_ready) return ACCBPG_ERR_ARG;
     double logdet = __builtin_nan("");
     if (refresh_logdet == 2) {
-        ACC_TRY(fw_ring_setup(h));
-        // the slot that comes round: collect what it holds -- the value of the call made `depth` such calls ago
-        if (h->fw_ring_issued - h->fw_ring_collected >= h->fw_ring_depth) ACC_TRY(accbpg_fw_logdet_flush(h, &logdet));
-        accbpg_dopt::FwSlot& sl = h->fw_ring[(size_t)(h->fw_ring_issued % h->fw_ring_depth)];
-        accbpg_dopt* a = sl.aux;
-        const int64_t T = (h->m + NB - 1) / NB;
-        if (!a->chol_tiles_off)
-            a->chol_tiles_off = h->fw_ring_small == 1 || (h->fw_ring_small == 2 && T * (T + 1) / 2 >= h->num_cu);
-        double* snap = chol_tiles_usable(a) ? a->Gbuf : a->Lbuf;
-        ACC_TRY(device_copy(snap, h->fw_H, (size_t)h->m * h->m, h->stream));   // H_k, in order with the updates
-        ACC_HIP(hipEventRecord(sl.ev_snap, h->stream));
-        ACC_HIP(hipStreamWaitEvent(sl.stream, sl.ev_snap, 0));
-        ACC_TRY(fw_slot_factor(sl, snap));
-        sl.pending = true;
-        ++h->fw_ring_issued;
+        ACC_TRY(accbpg_fw_logdet_snapshot(h, &logdet));
     } else if (refresh_logdet) {
         // F[k] = log det(H) from a fresh factorisation of the maintained inverse (D_opt_alg.py:136)
         // (the factor goes to Lbuf; H itself is read in place by the one-launch kernel, copied otherwise)
@@ -667,6 +796,148 @@ extern "C" int accbpg_fw_get_state(accbpg_dopt* h, double* x_dev, double* w_dev,
     if (H_dev)
         ACC_TRY(device_copy(H_dev, h->fw_H, (size_t)h->m * h->m, h->stream));
     ACC_HIP(hipStreamSynchronize(h->stream));
+    return ACCBPG_OK;
+}
+
+// ---- lock-step batches (accbpg_dopt_batch_fw_*) -----------------------------------------------------------------
+// The Frank-Wolfe state stays in the instance handles; a batched call is ONE launch per step kernel over the active
+// instances and -- for the probe -- one synchronisation.  What it leaves in an instance (x, w, H, the stage-1 records
+// and their bookkeeping) is what the single-handle entries leave, so the two may be mixed.
+static int fw_batch_table(accbpg_dopt_batch* b) {
+    if (b->fw_table) return ACCBPG_OK;
+    std::vector<FwInst> tab((size_t)b->K);
+    for (int i = 0; i < b->K; ++i) {
+        accbpg_dopt* h = b->inst[i];
+        ACC_TRY(fw_alloc(h));
+        tab[i] = FwInst{h->fw_x, h->fw_w, h->fw_H, h->fw_hv, h->V, h->vws, h->dscal + 10, h->fw_hpin_dev,
+                        h->vec_ok ? 1 : 0};
+    }
+    ACC_HIP(hipMalloc(&b->fw_table, sizeof(FwInst) * (size_t)b->K));
+    ACC_HIP(hipMemcpy(b->fw_table, tab.data(), sizeof(FwInst) * (size_t)b->K, hipMemcpyHostToDevice));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_init(accbpg_dopt_batch* b, const double* x0_dev, int64_t ldx, const int* active_host,
+                                         double* logdet_gram_host, int* status_host) {
+    if (!b || !x0_dev || !status_host || ldx < b->inst[0]->n) return ACCBPG_ERR_ARG;
+    ACC_TRY(fw_batch_table(b));
+    for (int i = 0; i < b->K; ++i) {
+        if (active_host && !active_host[i]) continue;
+        accbpg_dopt* h = b->inst[i];
+        h->stream = b->stream;
+        double ld = __builtin_nan("");
+        const int rc = accbpg_fw_init(h, x0_dev + (size_t)i * ldx, &ld);
+        if (rc == ACCBPG_ERR_HIP || rc == ACCBPG_ERR_ARG) return rc;
+        if (rc != ACCBPG_OK) h->fw_ready = false;               // (x was overwritten: no state to step from)
+        status_host[i] = rc;
+        if (logdet_gram_host) logdet_gram_host[i] = ld;
+    }
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_probe(accbpg_dopt_batch* b, int away, const int* active_host,
+                                          accbpg_fw_probe* probes_host) {
+    if (!b || !probes_host) return ACCBPG_ERR_ARG;
+    const int64_t m = b->inst[0]->m, n = b->inst[0]->n;
+    int nblk = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
+    if (nblk < 1) nblk = 1;
+    if (nblk > 512) nblk = 512;
+    FwProbeArgs pa;
+    BatchAct fresh;                                             // instances without stage-1 records for this threshold
+    for (int i = 0; i < b->K; ++i) {
+        if (active_host && !active_host[i]) continue;
+        accbpg_dopt* h = b->inst[i];
+        if (!h->fw_ready || !b->fw_table) {
+            set_last_error("accbpg_dopt_batch_fw_probe: instance %d has no Frank-Wolfe state (accbpg_dopt_batch_fw_init)", i);
+            return ACCBPG_ERR_ARG;
+        }
+        pa.idx[pa.n] = i;
+        if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
+            pa.nblk[pa.n] = h->fw_part_nblk;                    // stage 1 came with the last update of w
+        } else {
+            pa.nblk[pa.n] = nblk;
+            fresh.idx[fresh.n++] = i;
+        }
+        ++pa.n;
+    }
+    if (pa.n == 0) return ACCBPG_OK;
+    hipStream_t s = b->stream;
+    if (fresh.n > 0)
+        fw_probe_partial_batch_kernel<<<dim3((unsigned)nblk, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, away);
+    if (away && n >= 4096) {
+        int nb2 = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
+        if (nb2 > AWAY_NB) nb2 = AWAY_NB;
+        fw_probe_away_partial_batch_kernel<<<dim3((unsigned)nb2, (unsigned)pa.n), FB, 0, s>>>(b->fw_table, pa, m, n);
+        fw_probe_away_final_batch_kernel<<<dim3(1, (unsigned)pa.n), FB, 0, s>>>(b->fw_table, pa, nb2, m, n);
+    } else {
+        fw_probe_final_batch_kernel<<<dim3(1, (unsigned)pa.n), FB, 0, s>>>(b->fw_table, pa, m, n, away);
+    }
+    ACC_HIP(hipGetLastError());
+    ACC_HIP(hipStreamSynchronize(s));                           // every record is in its instance's pinned buffer
+    for (int a = 0; a < pa.n; ++a) {
+        accbpg_dopt* h = b->inst[pa.idx[a]];
+        h->fw_part_nblk = 0;
+        h->fw_part_away = (away != 0);
+        const int64_t* ih = reinterpret_cast<const int64_t*>(h->hpin + 8);
+        accbpg_fw_probe* out = probes_host + pa.idx[a];
+        out->i = ih[0];
+        out->j = ih[1];
+        out->w_i = h->hpin[4];
+        out->w_j = h->hpin[5];
+        out->x_j = h->hpin[6];
+        out->logdet_H = __builtin_nan("");
+        out->q_prev = h->hpin[10];
+    }
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* active_host, const int64_t* p_host,
+                                           const double* xscale_host, const double* xadd_host,
+                                           const double* hcoef_host, const double* hdiv_host) {
+    if (!b || !p_host || !xscale_host || !xadd_host || !hcoef_host || !hdiv_host) return ACCBPG_ERR_ARG;
+    const int64_t m = b->inst[0]->m, n = b->inst[0]->n, ldv = b->inst[0]->ldv;
+    FwUpdArgs ua;
+    BatchAct act;
+    for (int i = 0; i < b->K; ++i) {
+        if (active_host && !active_host[i]) continue;
+        accbpg_dopt* h = b->inst[i];
+        if (!h->fw_ready || !b->fw_table || p_host[i] < 0 || p_host[i] >= n) {
+            set_last_error("accbpg_dopt_batch_fw_update: instance %d: no Frank-Wolfe state (accbpg_dopt_batch_fw_init) or "
+                           "pivot index %lld outside [0, n)", i, (long long)p_host[i]);
+            return ACCBPG_ERR_ARG;                              // (nothing has been launched)
+        }
+        const int a = ua.n++;
+        ua.idx[a] = i;
+        if (h->fw_part_away) ua.awaymask |= 1ull << a;          // same support threshold as the instance's last probe
+        ua.p[a] = p_host[i];
+        ua.xscale[a] = xscale_host[i];
+        ua.xadd[a] = xadd_host[i];
+        ua.hcoef[a] = hcoef_host[i];
+        ua.hdiv[a] = hdiv_host[i];
+        act.idx[act.n++] = i;
+    }
+    if (ua.n == 0) return ACCBPG_OK;
+    const unsigned na = (unsigned)ua.n;
+    hipStream_t s = b->stream;
+    accbpg_dopt* h0 = b->inst[0];
+    int64_t gb = (std::max(n, m) + FB - 1) / FB;
+    if (gb > 1024) gb = 1024;
+    fw_xupdate_gather_batch_kernel<<<dim3((unsigned)gb, na), FB, 0, s>>>(b->fw_table, ua, m, n, ldv);
+    const int64_t pairs = (m + 1) / 2;
+    fw_gemv_h_batch_kernel<<<dim3((unsigned)((pairs + FB / 64 - 1) / (FB / 64)), na), FB, 0, s>>>(b->fw_table, act, m);
+    int64_t rb = m;
+    if (rb > 4096) rb = 4096;
+    fw_rank1_batch_kernel<<<dim3((unsigned)rb, na), FB, 0, s>>>(b->fw_table, ua, m);
+    const int ns = fw_nsplit(h0);                               // one shape, one device: every instance's own partition
+    dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns, na);
+    prof_begin(h0, PROF_FWV);
+    fw_vgemv_partial_batch_kernel<<<vg, FB, 0, s>>>(b->fw_table, act, ldv, m, n, ns);
+    prof_end(h0, PROF_FWV);
+    int64_t wb = (n + FB - 1) / FB;
+    if (wb > 512) wb = 512;                                     // 2*512 probe records behind Hv / vp
+    fw_wupdate_probe_batch_kernel<<<dim3((unsigned)wb, na), FB, 0, s>>>(b->fw_table, ua, m, n, ns);
+    for (int a = 0; a < ua.n; ++a) b->inst[ua.idx[a]]->fw_part_nblk = (int)wb;
+    ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
 

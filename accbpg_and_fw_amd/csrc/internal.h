@@ -75,6 +75,31 @@ struct BatchInst {
     int* chol_ready;
 };
 
+// Frank-Wolfe state of one instance as the lock-step step kernels (fw_kernels.hip) address it
+struct FwInst {
+    double* x;              // fw_x
+    double* w;              // fw_w
+    double* H;              // fw_H
+    double* hv;             // fw_hv: Hv, vp and the probe scratch behind them
+    const double* V;
+    double* vws;            // row-split partials of u = Hv^T V
+    double* q;              // dscal + 10: q of the last update
+    double* rec;            // the instance's pinned host record, as the device addresses it
+    int64_t vec_ok;         // V rows are 16-byte aligned
+};
+struct FwProbeArgs {        // active instances of a probe and the stage-1 records each has waiting
+    int n = 0;
+    int idx[BATCH_MAX] = {};
+    int nblk[BATCH_MAX] = {};
+};
+struct FwUpdArgs {          // active instances of an update and their scalars, by position in idx
+    int n = 0;
+    int idx[BATCH_MAX] = {};
+    unsigned long long awaymask = 0;    // bit a: support threshold of the fused stage 1 (1e-8 instead of 0)
+    int64_t p[BATCH_MAX] = {};
+    double xscale[BATCH_MAX] = {}, xadd[BATCH_MAX] = {}, hcoef[BATCH_MAX] = {}, hdiv[BATCH_MAX] = {};
+};
+
 struct CholJob { int i, j; };                     // i == j: owner of the diagonal tile (and of (i, i-1))
 struct CholInst {                                  // one factorisation (one entry per instance of a batched launch)
     const double* src;      // matrix to factor (lower triangle significant), leading dimension ld
@@ -223,6 +248,7 @@ struct accbpg_dopt_batch {
     double* vgg = nullptr;                  // K * n doubles: gg of the prox when it does not fit in registers
     double* vws = nullptr;                  // workspace of the single-instance prox (long vectors, one instance at a time)
     double* vpin = nullptr;                 // pinned mirror (K * 8 doubles)
+    accbpg::FwInst* fw_table = nullptr;     // device, K entries: Frank-Wolfe state of every instance (built by the first accbpg_dopt_batch_fw_init)
     // the evaluation in flight between _begin and _end
     accbpg::BatchAct pend_act;
     const double* pend_x = nullptr;

@@ -281,6 +281,32 @@ int accbpg_fw_update(accbpg_dopt* h, int64_t p, double xscale, double xadd, doub
 /* Copy state out (device to device): x (n), w (n), H (m*m, row-major).  NULL skips. */
 int accbpg_fw_get_state(accbpg_dopt* h, double* x_dev, double* w_dev, double* H_dev);
 
+/* The refresh_logdet = 2 part of accbpg_fw_probe_step as a call of its own: copies the current H into the ring slot
+ * that comes round and starts its side factorisation; *collected_host <- the value that slot held (the snapshot taken
+ * `depth` such calls earlier), NaN while there is none.  accbpg_fw_probe_step(h, away, 2, ...) is this call followed by
+ * the probe. */
+int accbpg_fw_logdet_snapshot(accbpg_dopt* h, double* collected_host);
+
+/* Lock-step Frank-Wolfe steps for the instances of a batch (accbpg_dopt_batch_create): ONE launch per step kernel
+ * covers the active instances (active_host[i] != 0; NULL = all) and ONE synchronisation returns all probe records.
+ * The state lives in the instance handles: after a batched step, x, w and H of instance i are bit for bit those of
+ * accbpg_fw_update on accbpg_dopt_batch_instance(b, i), accbpg_fw_get_state on that handle returns them, and
+ * single-handle and batched calls may be mixed.  Works for every shape a batch can hold.  All host arrays have K
+ * entries, entry i = instance i; entries of inactive instances are neither read nor written.
+ *   _fw_init:   accbpg_fw_init per active instance with x0 = row i of x0_dev (leading dimension ldx).  status_host[i]
+ *               <- ACCBPG_OK or ACCBPG_ERR_NOT_PD (that instance has no state then; the others are initialised);
+ *               logdet_gram_host (may be NULL) as accbpg_fw_init.
+ *   _fw_probe:  the records of accbpg_fw_probe_step(h_i, away, 0, ...): logdet_H is NaN (log det(H) beside the steps:
+ *               accbpg_fw_logdet_snapshot on the instance handles).
+ *   _fw_update: accbpg_fw_update(h_i, p_host[i], xscale_host[i], xadd_host[i], hcoef_host[i], hdiv_host[i]).  A pivot
+ *               outside [0, n) on an active instance returns ACCBPG_ERR_ARG before anything is launched. */
+int accbpg_dopt_batch_fw_init(accbpg_dopt_batch* b, const double* x0_dev, int64_t ldx, const int* active_host,
+                              double* logdet_gram_host, int* status_host);
+int accbpg_dopt_batch_fw_probe(accbpg_dopt_batch* b, int away, const int* active_host, accbpg_fw_probe* probes_host);
+int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* active_host, const int64_t* p_host,
+                                const double* xscale_host, const double* xadd_host, const double* hcoef_host,
+                                const double* hdiv_host);
+
 /* ---- Poisson linear inverse problem with Burg L1 / L2 kernels -------- */
 
 typedef struct accbpg_poisson accbpg_poisson;

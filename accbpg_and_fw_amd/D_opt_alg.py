@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import struct
 import time
 
 import numpy as np
@@ -34,6 +35,7 @@ class _FWState:
             rc = self.lib.accbpg_fw_init(self.h, _ptr(x0d), C.byref(logdet))
         _lib.check(rc, "accbpg_fw_init")
         self.logdet_gram = logdet.value
+        self._steps = None
 
     def _on_device(self):
         """True when the objective's device is already the current one (then the two calls per iteration skip the
@@ -73,6 +75,32 @@ class _FWState:
                 rc = self.lib.accbpg_fw_update(self.h, int(p), float(xscale), float(xadd), float(hcoef), float(hdiv))
         if rc:
             _lib.check(rc, "accbpg_fw_update")
+
+    def snapshot(self):
+        """Start the side factorisation of the current H (accbpg_fw_logdet_snapshot); returns the value that comes in."""
+        out = C.c_double(0.0)
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_logdet_snapshot(self.h, C.byref(out))
+        _lib.check(rc, "accbpg_fw_logdet_snapshot")
+        return out.value
+
+    def run(self, away, eps, nsteps):
+        """``nsteps`` iterations decided on the device behind one synchronisation (accbpg_fw_run): the records of the
+        iterations that ran.  A record with status 2 (pivot outside [0, n)) is returned, not raised: the replay reaches it
+        in its turn and calls ``bad_pivot``."""
+        if self._steps is None:
+            self._steps = (_lib.FwStep * _lib.FW_RUN_MAX)()
+        nrun = C.c_int(0)
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_run(self.h, int(away), float(eps), int(nsteps), self._steps, C.byref(nrun))
+        if rc and not (rc == _lib.ERR_ARG and nrun.value > 0 and self._steps[nrun.value - 1].status == _lib.FW_BAD_PIVOT):
+            _lib.check(rc, "accbpg_fw_run")
+        return [self._steps[k] for k in range(nrun.value)]
+
+    def bad_pivot(self):
+        """The exception of the sequential solver's ``update`` with such a pivot (the library's last error is still the
+        message accbpg_fw_run left)."""
+        _lib.check(_lib.ERR_ARG, "accbpg_fw_update")
 
     def x(self):
         out = torch.empty(self.n, dtype=torch.float64, device=self.obj.device)
@@ -310,6 +338,155 @@ def D_opt_FW_away_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1, logdet_re
             break
         st.update(*upd)
         yield k
+
+    F, SP, SN, T = run.finish(st.flush_logdet)
+    return st.x(), F, SP, SN, T
+
+
+# ---- several iterations per host round trip ----------------------------------------------------------------------------
+SYNC_EVERY_DEFAULT = 64
+_GUARD_FIELDS = ("p", "xscale", "xadd", "hcoef", "hdiv")
+
+
+def _guard(st, k, rec, upd):
+    """The device's decision of iteration k (record ``rec`` of accbpg_fw_run) against the host's own ``upd`` -- (p,
+    xscale, xadd, hcoef, hdiv), or None when the stop test holds -- bit for bit (a NaN equals a NaN).  Raises RuntimeError naming k and the
+    field; a pivot outside [0, n) raises what the sequential solver's update raises."""
+    if upd is None:
+        if rec.status != _lib.FW_STOPPED:
+            raise RuntimeError("iteration %d: the host's stop test holds, the device's did not (field status = %d)"
+                               % (k, rec.status))
+        return
+    if rec.status == _lib.FW_STOPPED:
+        raise RuntimeError("iteration %d: the device's stop test held, the host's does not (field status = 1)" % k)
+    for name, mine, fmt in zip(_GUARD_FIELDS, upd, "qdddd"):
+        theirs = getattr(rec, name)
+        if struct.pack(fmt, mine) != struct.pack(fmt, theirs) and not (mine != mine and theirs != theirs):   # (NaN for NaN)
+            raise RuntimeError("iteration %d: field %s decided on the device (%r) differs from the host's (%r)"
+                               % (k, name, theirs, mine))
+    if rec.status == _lib.FW_BAD_PIVOT:
+        st.bad_pivot()
+    if rec.status != _lib.FW_APPLIED:
+        raise RuntimeError("iteration %d: unexpected field status = %d" % (k, rec.status))
+
+
+def _chunk(k, maxitrs, sync_every, R=0):
+    """Iterations of the chunk that starts at k: ``sync_every`` (None: R, or SYNC_EVERY_DEFAULT when R = 0), cut so
+    that the chunk ends before the next multiple of R (R > 0), at maxitrs, and at what one call holds."""
+    S = (R if R > 0 else SYNC_EVERY_DEFAULT) if sync_every is None else int(sync_every)
+    if S < 1:
+        raise ValueError("sync_every must be at least 1")
+    if R > 0:
+        S = min(S, R - k % R)
+    return min(S, maxitrs - k, _lib.FW_RUN_MAX)
+
+
+def D_opt_FW_device(V, x0, eps, maxitrs, verbose=True, verbskip=1, sync_every=SYNC_EVERY_DEFAULT):
+    """D_opt_FW with ``sync_every`` iterations per host round trip; T[k] of all iterations of a chunk is the time at
+    which the chunk's records arrived, and the table rows are printed per chunk, in order k = 0, 1, 2, ...
+
+    The stop test, the step length and the rank-one coefficients of an iteration are computed on the device
+    (accbpg_fw_run) by the sequential solver's kernels on its grids; the host replays every record through
+    ``_fw_decide`` for F, SP and SN and compares its own update scalars with the device's bit for bit (RuntimeError on
+    a difference).  Returns D_opt_FW's tuple; x, F, SP, SN and the iteration count are bit-identical to D_opt_FW's."""
+    return _drain(D_opt_FW_device_steps(V, x0, eps, maxitrs, verbose, verbskip, sync_every))
+
+
+def D_opt_FW_device_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1, sync_every=SYNC_EVERY_DEFAULT):
+    """Generator form of D_opt_FW_device: yields the last k of each chunk, returns D_opt_FW_device's tuple."""
+    return _fw_device_steps(_FWState(V, x0), eps, maxitrs, verbose, verbskip, sync_every, time.time())
+
+
+def _fw_device_steps(st, eps, maxitrs, verbose, verbskip, sync_every, start_time):
+    """D_opt_FW_device_steps on a state object (``m``, ``logdet_gram``, ``run``, ``bad_pivot``, ``x``)."""
+    m = st.m
+    F = np.zeros(maxitrs)
+    SP = np.zeros(maxitrs)
+    SN = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+    detVXVT = np.exp(st.logdet_gram)                            # :41
+
+    if verbose:
+        print("\nSolving D-opt design problem using Frank-Wolfe method")
+        print("     k      F(x)     pos_slack   neg_slack    time")
+
+    k = -1
+    stopped = False
+    while k + 1 < maxitrs and not stopped:
+        recs = st.run(0, eps, _chunk(k + 1, maxitrs, sync_every))
+        now = time.time() - start_time
+        for rec in recs:
+            k += 1
+            F[k] = - np.log(detVXVT)                            # :52
+            T[k] = now
+            eps_pos, eps_neg, upd, detmul = _fw_decide(m, rec.w_i, rec.w_j, eps)
+            SP[k] = eps_pos
+            SN[k] = eps_neg
+            if verbose and k % verbskip == 0:
+                print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:10.3e}  {4:6.1f}".format(
+                    k, F[k], eps_pos, eps_neg, T[k]))
+            _guard(st, k, rec, None if upd is None else (rec.i,) + upd)
+            if upd is None:                                     # :72
+                stopped = True
+                break
+            detVXVT *= detmul                                   # :80
+        if not stopped:
+            yield k
+
+    return st.x(), F[0:k + 1], SP[0:k + 1], SN[0:k + 1], T[0:k + 1]
+
+
+def D_opt_FW_away_device(V, x0, eps, maxitrs, verbose=True, verbskip=1, sync_every=None, logdet_refresh=None,
+                         logdet_ring=None):
+    """D_opt_FW_away with up to ``sync_every`` iterations per host round trip; T[k] of all iterations of a chunk is the
+    time at which the chunk's records arrived, and the table rows are printed per chunk, in order k = 0, 1, 2, ...
+
+    The stop test, the choice between a Frank-Wolfe and an away step, the step length and the rank-one coefficients are
+    computed on the device (accbpg_fw_run); the host replays every record through ``_AwayRun.iterate`` and compares
+    its own update scalars with the device's bit for bit (RuntimeError on a difference).  A chunk never spans an
+    iteration that refactors H (a multiple of R = ``logdet_refresh``): it ends before the next one, the snapshot is
+    issued between chunks, and F is formed as D_opt_FW_away forms it.  ``sync_every=None`` means R (64 when R = 0);
+    R = 1 gives chunks of one.  Returns D_opt_FW_away's tuple, x, F, SP, SN and the iteration count bit-identical to it
+    for the same ``logdet_refresh`` / ``logdet_ring``."""
+    return _drain(D_opt_FW_away_device_steps(V, x0, eps, maxitrs, verbose, verbskip, sync_every, logdet_refresh,
+                                             logdet_ring))
+
+
+def D_opt_FW_away_device_steps(V, x0, eps, maxitrs, verbose=True, verbskip=1, sync_every=None, logdet_refresh=None,
+                               logdet_ring=None):
+    """Generator form of D_opt_FW_away_device: yields the last k of each chunk, returns its tuple."""
+    return _away_device_steps(_FWState(V, x0), eps, maxitrs, verbose, verbskip, sync_every, logdet_refresh, logdet_ring,
+                              time.time())
+
+
+def _away_device_steps(st, eps, maxitrs, verbose, verbskip, sync_every, logdet_refresh, logdet_ring, start_time):
+    """D_opt_FW_away_device_steps on a state object (as _fw_device_steps, and ``logdet_ring``, ``snapshot``,
+    ``flush_logdet``)."""
+    R, depth = _away_modes(logdet_refresh, logdet_ring)
+    st.logdet_ring(depth)
+    run = _AwayRun(st.m, maxitrs, R, depth, verbose, verbskip)
+    nan = float("nan")
+
+    if verbose:
+        print("\nSolving D-opt design problem using Frank-Wolfe method with away steps")
+        print("     k      F(x)     pos_slack   neg_slack    time")
+
+    k = 0
+    stopped = False
+    while k < maxitrs and not stopped:
+        collected = st.snapshot() if run.refresh(k) else nan     # :136: the chunk starts on the anchor, or holds none
+        recs = st.run(1, eps, _chunk(k, maxitrs, sync_every, R))     # :145-147, :150-179
+        now = time.time() - start_time
+        for rec in recs:
+            upd = run.iterate(k, rec, collected, now, st.logdet_gram, eps)
+            collected = nan
+            _guard(st, k, rec, upd)
+            if upd is None:                                     # :159
+                stopped = True
+                break
+            k += 1
+        if not stopped:
+            yield k - 1
 
     F, SP, SN, T = run.finish(st.flush_logdet)
     return st.x(), F, SP, SN, T

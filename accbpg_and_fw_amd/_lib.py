@@ -24,6 +24,16 @@ class FwProbe(C.Structure):
                 ("x_j", C.c_double), ("logdet_H", C.c_double), ("q_prev", C.c_double)]
 
 
+class FwStep(C.Structure):
+    """One record of accbpg_fw_run: the probe record, the update the device applied, and what became of the step."""
+    _fields_ = [("i", C.c_int64), ("j", C.c_int64), ("w_i", C.c_double), ("w_j", C.c_double), ("x_j", C.c_double),
+                ("q_prev", C.c_double), ("p", C.c_int64), ("xscale", C.c_double), ("xadd", C.c_double),
+                ("hcoef", C.c_double), ("hdiv", C.c_double), ("kind", C.c_int32), ("status", C.c_int32)]
+
+
+FW_RUN_MAX = 1024           # ACCBPG_FW_RUN_MAX
+FW_APPLIED, FW_STOPPED, FW_BAD_PIVOT, FW_NOT_RUN = 0, 1, 2, 3      # accbpg_fw_step.status
+
 _P = C.c_void_p
 _SIGS = {
     "accbpg_abi_version": (C.c_int, []),
@@ -87,6 +97,7 @@ _SIGS = {
     "accbpg_fw_update": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "accbpg_fw_get_state": (C.c_int, [_P, _P, _P, _P]),
     "accbpg_fw_logdet_snapshot": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "accbpg_fw_run": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, C.POINTER(FwStep), C.POINTER(C.c_int)]),
     "accbpg_dopt_batch_fw_init": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                             C.POINTER(C.c_int)]),
     "accbpg_dopt_batch_fw_probe": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(FwProbe)]),

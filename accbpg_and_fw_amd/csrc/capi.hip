@@ -104,6 +104,8 @@ extern "C" int accbpg_dopt_destroy(accbpg_dopt* h) {
     hipFree(h->vws); hipFree(h->xbuf); hipFree(h->ops); hipFree(h->chol_op); hipFree(h->red); hipFree(h->Pbuf);
     hipFree(h->fw_x); hipFree(h->fw_w); hipFree(h->fw_H); hipFree(h->fw_hv);
     hipFree(h->chol_jobs); hipFree(h->chol_ready); hipFree(h->chol_aux); hipFree(h->chol_hand); hipFree(h->Gbuf);
+    hipFree(h->fw_run);
+    if (h->fw_steps_pin) hipHostFree(h->fw_steps_pin);
     if (h->hpin) hipHostFree(h->hpin);
     if (h->ev_done) hipEventDestroy(h->ev_done);
     for (auto& sl : h->fw_ring) {

@@ -479,6 +479,119 @@ __global__ __launch_bounds__(FB) void fw_wupdate_probe_batch_kernel(const FwInst
                           fw_part_of(t, m));
 }
 
+// ---- the step kernels: several iterations per host round trip (accbpg_fw_run) -----------------------------------
+// The "run" forms wrap the SAME bodies on the single handle's grids.  The scalars of the step come from the handle's
+// FwRun in device memory instead of the kernel arguments, and every kernel returns at once when that record says the
+// run has stopped (the load is the same for every thread of the grid: the branch is uniform).  Thread 0 of the probe's
+// final stage takes the decisions of the iteration -- D_opt_alg.py:63-82 and :150-179, operation for operation as
+// _fw_decide and _AwayRun.iterate of the Python package write them; this file is compiled with -ffp-contract=off --
+// writes FwRun for the update kernels behind it and the record of the step straight into the pinned host array.
+__device__ __forceinline__ int fw_run_stop(const FwRun* run) {
+    return *reinterpret_cast<const volatile int32_t*>(&run->stop);
+}
+__device__ __forceinline__ void fw_run_decide(FwRun* run, const double* rec, int64_t m, int64_t n, int away, double eps,
+                                              accbpg_fw_step* __restrict__ out) {
+    // rec: the scratch record the body has just written (this thread wrote it), laid out as the pinned record is
+    const int64_t* irec = reinterpret_cast<const int64_t*>(rec + 8);
+    const int64_t i = irec[0], j = irec[1];
+    const double w_i = rec[4], w_j = rec[5], x_j = rec[6], q_prev = rec[10];
+    const double md = (double)m;
+    const double eps_pos = w_i / md - 1.0;                      // :63, :150
+    const double eps_neg = 1.0 - w_j / md;                      // :64, :151
+    accbpg_fw_step st;
+    st.i = i; st.j = j; st.w_i = w_i; st.w_j = w_j; st.x_j = x_j; st.q_prev = q_prev;
+    st.p = -1; st.xscale = 0.0; st.xadd = 0.0; st.hcoef = 0.0; st.hdiv = 0.0;
+    st.kind = -1; st.status = 1;
+    if (!(eps_pos <= eps && eps_neg <= eps)) {                  // :72, :159 (a NaN does not stop)
+        int64_t p;
+        double xscale, xadd, hcoef, hdiv;
+        int kind;
+        if (!away || eps_pos >= eps_neg) {                      // :162 (a NaN takes the away branch)
+            const double t = (w_i / md - 1.0) / (w_i - 1.0);    // :75, :163
+            const double coef = away ? t / (1.0 - t + t * w_i)  // :167
+                                     : t / (1.0 + t * (w_i - 1.0));   // :79
+            p = i; xscale = 1.0 - t; xadd = t; hcoef = -coef; hdiv = 1.0 - t; kind = 0;
+        } else {
+            const double a = (1.0 - w_j / md) / (w_j - 1.0);    // :172
+            const double b = x_j / (1.0 - x_j);
+            const double t = (b < a) ? b : a;                   // Python's min(a, b)
+            const double coef = t / (1.0 + t - t * w_j);        // :176
+            p = j; xscale = 1.0 + t; xadd = -t; hcoef = coef; hdiv = 1.0 + t; kind = 1;
+        }
+        st.p = p; st.xscale = xscale; st.xadd = xadd; st.hcoef = hcoef; st.hdiv = hdiv; st.kind = kind;
+        st.status = (p >= 0 && p < n) ? 0 : 2;
+        if (st.status == 0) {
+            run->p = p; run->xscale = xscale; run->xadd = xadd; run->hcoef = hcoef; run->hdiv = hdiv;
+        }
+    }
+    if (st.status != 0) *reinterpret_cast<volatile int32_t*>(&run->stop) = st.status;
+    *out = st;
+}
+__global__ __launch_bounds__(FB) void fw_probe_final_run_kernel(FwRun* run, const ValIdx* __restrict__ part, int nblk,
+                                                               const double* __restrict__ w,
+                                                               const double* __restrict__ x, int64_t m, int64_t n,
+                                                               int away, double eps, double* rec,
+                                                               const double* __restrict__ qsrc,
+                                                               accbpg_fw_step* __restrict__ out) {
+    if (fw_run_stop(run)) return;
+    fw_probe_final_body(part, nblk, w, x, n, away, rec + 4, reinterpret_cast<int64_t*>(rec + 8), qsrc);
+    if (threadIdx.x == 0) fw_run_decide(run, rec, m, n, away, eps, out);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_partial_run_kernel(const FwRun* run, const ValIdx* __restrict__ part,
+                                                                      int nblk, const double* __restrict__ w,
+                                                                      const double* __restrict__ x, int64_t n,
+                                                                      ValIdx* __restrict__ part2,
+                                                                      ValIdx* __restrict__ mxslot) {
+    if (fw_run_stop(run)) return;
+    fw_probe_away_partial_body(part, nblk, w, x, n, part2, mxslot);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_final_run_kernel(FwRun* run, const ValIdx* __restrict__ part2, int nb2,
+                                                                    const ValIdx* __restrict__ mxslot,
+                                                                    const double* __restrict__ w,
+                                                                    const double* __restrict__ x, int64_t m, int64_t n,
+                                                                    double eps, double* rec,
+                                                                    const double* __restrict__ qsrc,
+                                                                    accbpg_fw_step* __restrict__ out) {
+    if (fw_run_stop(run)) return;
+    fw_probe_away_final_body(part2, nb2, mxslot, w, x, n, rec + 4, reinterpret_cast<int64_t*>(rec + 8), qsrc);
+    if (threadIdx.x == 0) fw_run_decide(run, rec, m, n, 1, eps, out);
+}
+__global__ __launch_bounds__(FB) void fw_xupdate_gather_run_kernel(const FwRun* __restrict__ run, double* __restrict__ x,
+                                                                  int64_t n, const double* __restrict__ V, int64_t ldv,
+                                                                  int64_t m, double* __restrict__ vp) {
+    const FwRun r = *run;
+    if (r.stop) return;
+    fw_xupdate_gather_body(x, n, r.p, r.xscale, r.xadd, V, ldv, m, vp);
+}
+__global__ __launch_bounds__(FB) void fw_gemv_h_run_kernel(const FwRun* __restrict__ run, const double* __restrict__ H,
+                                                          int64_t m, const double* __restrict__ vp,
+                                                          double* __restrict__ hv) {
+    if (run->stop) return;
+    fw_gemv_h_body(H, m, vp, hv);
+}
+__global__ __launch_bounds__(FB) void fw_rank1_run_kernel(const FwRun* __restrict__ run, double* __restrict__ H, int64_t m,
+                                                         const double* __restrict__ hv, const double* __restrict__ vp,
+                                                         double* __restrict__ qout) {
+    const FwRun r = *run;
+    if (r.stop) return;
+    fw_rank1_body(H, m, hv, r.hcoef, r.hdiv, vp, qout);
+}
+__global__ __launch_bounds__(FB) void fw_vgemv_partial_run_kernel(const FwRun* __restrict__ run,
+                                                                 const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                                 int64_t n, const double* __restrict__ hv, int nsplit,
+                                                                 double* __restrict__ upart, bool vec_ok) {
+    if (run->stop) return;
+    fw_vgemv_partial_body(V, ldv, m, n, hv, nsplit, upart, vec_ok);
+}
+__global__ __launch_bounds__(FB) void fw_wupdate_probe_run_kernel(const FwRun* __restrict__ run, double* __restrict__ w,
+                                                                 int64_t n, const double* __restrict__ upart, int nsplit,
+                                                                 const double* __restrict__ x, int away,
+                                                                 ValIdx* __restrict__ part) {
+    const FwRun r = *run;
+    if (r.stop) return;
+    fw_wupdate_probe_body(w, n, upart, nsplit, r.hcoef, r.hdiv, x, away, part);
+}
+
 // u = sum of the row-split partials (u = V^T q)
 __global__ __launch_bounds__(FB) void fw_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
                                                     double* __restrict__ u) {
@@ -786,6 +899,103 @@ extern "C" int accbpg_fw_update(accbpg_dopt* h, int64_t p, double xscale, double
                                                           h->fw_part_away ? 1 : 0, part);
     h->fw_part_nblk = (int)wb;
     ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+
+// ---- several iterations per synchronisation (accbpg_fw_run) -----------------------------------------------------
+static int fw_run_alloc(accbpg_dopt* h) {
+    if (!h->fw_steps_pin) {
+        ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fw_steps_pin), sizeof(accbpg_fw_step) * ACCBPG_FW_RUN_MAX,
+                              hipHostMallocDefault));
+        ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_steps_dev), h->fw_steps_pin, 0));
+    }
+    // FwRun, then a scratch probe record laid out as the pinned one (16 doubles)
+    if (!h->fw_run) ACC_HIP(hipMalloc(reinterpret_cast<void**>(&h->fw_run), sizeof(FwRun) + sizeof(double) * 16));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_fw_run(accbpg_dopt* h, int away, double eps, int nsteps, accbpg_fw_step* steps_host,
+                             int* nrun_host) {
+    if (!h || !h->fw_ready || !steps_host || !nrun_host || nsteps < 1 || nsteps > ACCBPG_FW_RUN_MAX) return ACCBPG_ERR_ARG;
+    ACC_TRY(fw_run_alloc(h));
+    const int64_t m = h->m, n = h->n;
+    hipStream_t s = h->stream;
+    FwRun* run = h->fw_run;
+    double* rec = reinterpret_cast<double*>(run + 1);
+    for (int k = 0; k < nsteps; ++k) {                          // (nothing of an earlier call is in flight: it synchronised)
+        accbpg_fw_step& st = h->fw_steps_pin[k];
+        st = accbpg_fw_step{};
+        st.p = -1;
+        st.kind = -1;
+        st.status = 3;
+    }
+    ACC_HIP(hipMemsetAsync(run, 0, sizeof(FwRun), s));
+    // the grids of accbpg_fw_probe_step and accbpg_fw_update
+    ValIdx* part = reinterpret_cast<ValIdx*>(h->fw_hv + 2 * m);
+    ValIdx* part2 = part + 2 * 512;
+    ValIdx* mxslot = part2 + AWAY_NB;
+    int nblk = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
+    if (nblk < 1) nblk = 1;
+    if (nblk > 512) nblk = 512;
+    int nb2 = nblk;
+    if (nb2 > AWAY_NB) nb2 = AWAY_NB;
+    int64_t gb = (std::max(n, m) + FB - 1) / FB;
+    if (gb > 1024) gb = 1024;
+    const int64_t pairs = (m + 1) / 2;
+    const int hb = (int)((pairs + FB / 64 - 1) / (FB / 64));
+    int64_t rb = m;
+    if (rb > 4096) rb = 4096;
+    const int ns = fw_nsplit(h);
+    const dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns);
+    int64_t wb = (n + FB - 1) / FB;
+    if (wb > 512) wb = 512;
+    double* vp = h->fw_hv + m;
+    double* q = h->dscal + 10;
+    if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
+        nblk = h->fw_part_nblk;                                 // stage 1 came with the last update of w
+    } else {
+        fw_probe_partial_kernel<<<nblk, FB, 0, s>>>(h->fw_w, h->fw_x, n, away, part);
+    }
+    h->fw_part_nblk = 0;                                        // (no claim of reuse survives an error return below)
+    h->fw_part_away = (away != 0);
+    for (int k = 0; k < nsteps; ++k) {
+        accbpg_fw_step* out = h->fw_steps_dev + k;
+        if (away && n >= 4096) {
+            fw_probe_away_partial_run_kernel<<<nb2, FB, 0, s>>>(run, part, nblk, h->fw_w, h->fw_x, n, part2, mxslot);
+            fw_probe_away_final_run_kernel<<<1, FB, 0, s>>>(run, part2, nb2, mxslot, h->fw_w, h->fw_x, m, n, eps, rec, q, out);
+        } else {
+            fw_probe_final_run_kernel<<<1, FB, 0, s>>>(run, part, nblk, h->fw_w, h->fw_x, m, n, away, eps, rec, q, out);
+        }
+        fw_xupdate_gather_run_kernel<<<(int)gb, FB, 0, s>>>(run, h->fw_x, n, h->V, h->ldv, m, vp);
+        fw_gemv_h_run_kernel<<<hb, FB, 0, s>>>(run, h->fw_H, m, vp, h->fw_hv);
+        fw_rank1_run_kernel<<<(int)rb, FB, 0, s>>>(run, h->fw_H, m, h->fw_hv, vp, q);
+        fw_vgemv_partial_run_kernel<<<vg, FB, 0, s>>>(run, h->V, h->ldv, m, n, h->fw_hv, ns, h->vws, h->vec_ok);
+        fw_wupdate_probe_run_kernel<<<(int)wb, FB, 0, s>>>(run, h->fw_w, n, h->vws, ns, h->fw_x, away ? 1 : 0, part);
+        nblk = (int)wb;                                         // the next probe's stage 1 came with this update
+    }
+    ACC_HIP(hipGetLastError());
+    ACC_HIP(hipStreamSynchronize(s));
+    int nrun = 0;
+    bool bad_pivot = false;
+    long long bad_p = 0;
+    for (int k = 0; k < nsteps; ++k) {
+        const accbpg_fw_step& st = h->fw_steps_pin[k];
+        steps_host[k] = st;
+        if (st.status != 3) ++nrun;
+        if (st.status == 2) {
+            bad_pivot = true;
+            bad_p = (long long)st.p;
+        }
+    }
+    *nrun_host = nrun;
+    // what a later probe finds: the stage-1 records of the last update, if the call ended on one (as accbpg_fw_update
+    // leaves them); after a stop none, as after accbpg_fw_probe_step (x and w are as that probe read them)
+    h->fw_part_nblk = (nrun == nsteps && steps_host[nsteps - 1].status == 0) ? (int)wb : 0;
+    if (bad_pivot) {
+        set_last_error("accbpg_fw_update: no Frank-Wolfe state (call accbpg_fw_init) or pivot index %lld outside [0, n)",
+                       bad_p);
+        return ACCBPG_ERR_ARG;
+    }
     return ACCBPG_OK;
 }
 

@@ -100,6 +100,15 @@ struct FwUpdArgs {          // active instances of an update and their scalars, 
     double xscale[BATCH_MAX] = {}, xadd[BATCH_MAX] = {}, hcoef[BATCH_MAX] = {}, hdiv[BATCH_MAX] = {};
 };
 
+// One handle's step as its "run" kernels read it (accbpg_fw_run): written by thread 0 of the probe's final stage, read
+// by the update kernels of that step; once stop != 0 every later kernel of the call returns at once
+struct FwRun {
+    int32_t stop;           // 0 running; 1 the stop test held; 2 pivot outside [0, n)
+    int32_t pad;
+    int64_t p;
+    double xscale, xadd, hcoef, hdiv;
+};
+
 struct CholJob { int i, j; };                     // i == j: owner of the diagonal tile (and of (i, i-1))
 struct CholInst {                                  // one factorisation (one entry per instance of a batched launch)
     const double* src;      // matrix to factor (lower triangle significant), leading dimension ld
@@ -196,6 +205,11 @@ struct accbpg_dopt {
     long long fw_ring_issued = 0, fw_ring_collected = 0;
     int fw_part_nblk = 0;       // probe stage-1 records left behind by the last w update (0: none)
     bool fw_part_away = false;  // support threshold they were computed for
+    // accbpg_fw_run: the step's scalars and a scratch probe record on the device, the records of a call in pinned host
+    // memory (allocated by the first call, freed with the handle)
+    accbpg::FwRun* fw_run = nullptr;
+    accbpg_fw_step* fw_steps_pin = nullptr;     // ACCBPG_FW_RUN_MAX records
+    accbpg_fw_step* fw_steps_dev = nullptr;     // ... as the device addresses them
 
     bool use_glds = true;       // direct-to-LDS staging for interior big tiles (debug switch)
     int kern_variant = 0;       // schedule of the direct-to-LDS Gram / gradient kernels (development switch)

@@ -287,6 +287,31 @@ int accbpg_fw_get_state(accbpg_dopt* h, double* x_dev, double* w_dev, double* H_
  * the probe. */
 int accbpg_fw_logdet_snapshot(accbpg_dopt* h, double* collected_host);
 
+/* Several iterations per host round trip: the scalar decisions of an iteration (D_opt_alg.py:63-82 for away = 0,
+ * :150-179 for away = 1) are taken ON THE DEVICE, by thread 0 of the probe's final stage, in plain float64 + - * / and
+ * comparisons written operation for operation as the reference writes them (no fused multiply-add, NaN falls through
+ * the comparisons as it does there):
+ *   eps_pos = w_i / m - 1, eps_neg = 1 - w_j / m; stop when eps_pos <= eps && eps_neg <= eps           (:72, :159)
+ *   away = 0, or eps_pos >= eps_neg: t = (w_i / m - 1) / (w_i - 1), update (i, 1 - t, t, -coef, 1 - t) with
+ *       coef = t / (1 + t * (w_i - 1)) for away = 0 (:75-82), coef = t / (1 - t + t * w_i) for away = 1 (:162-170)
+ *   otherwise: t = min((1 - w_j / m) / (w_j - 1), x_j / (1 - x_j)), coef = t / (1 + t - t * w_j), update
+ *       (j, 1 + t, -t, coef, 1 + t)                                                                    (:171-179)
+ * One call enqueues nsteps iterations (1 <= nsteps <= 1024), each the kernels of accbpg_fw_probe_step(h, away, 0, ...)
+ * followed by those of accbpg_fw_update with the scalars read from device memory -- the same bodies on the same grids,
+ * so x, w and H are bit for bit those of the step-by-step calls -- synchronises ONCE and copies the records out.  After
+ * a stop (status 1 or 2) the remaining kernels of the call return at once: x, w, H and q_prev stay as the stop found
+ * them and the later records read status 3.  *nrun_host <- the number of records with status != 3.  A pivot outside
+ * [0, n) (status 2) applies no update and makes the call return ACCBPG_ERR_ARG with accbpg_fw_update's message; the
+ * records are filled in all the same.  May be mixed freely with accbpg_fw_probe_step / accbpg_fw_update. */
+#define ACCBPG_FW_RUN_MAX 1024   /* most iterations of one accbpg_fw_run call */
+typedef struct accbpg_fw_step {
+    int64_t i, j;  double w_i, w_j, x_j, q_prev;       /* the probe record, as accbpg_fw_probe */
+    int64_t p;     double xscale, xadd, hcoef, hdiv;   /* the update the device applied        */
+    int32_t kind;   /* 0 Frank-Wolfe step, 1 away step, -1 none */
+    int32_t status; /* 0 update applied; 1 stop test held; 2 pivot outside [0,n); 3 not run (after a stop) */
+} accbpg_fw_step;
+int accbpg_fw_run(accbpg_dopt* h, int away, double eps, int nsteps, accbpg_fw_step* steps_host, int* nrun_host);
+
 /* Lock-step Frank-Wolfe steps for the instances of a batch (accbpg_dopt_batch_create): ONE launch per step kernel
  * covers the active instances (active_host[i] != 0; NULL = all) and ONE synchronisation returns all probe records.
  * The state lives in the instance handles: after a batched step, x, w and H of instance i are bit for bit those of

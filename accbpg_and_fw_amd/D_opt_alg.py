@@ -605,3 +605,132 @@ def D_opt_FW_away_batch_steps(batch, x0, eps, maxitrs, logdet_refresh=None, logd
         F, SP, SN, T = runs[i].finish(lambda i=i: batch.fw_logdet_flush(i))
         out.append((batch.fw_x(i, as_numpy), F.copy(), SP.copy(), SN.copy(), T.copy()))
     return out
+
+
+# ---- lock-step batches that decide their steps on the device ---------------------------------------------------------
+def _guard_instance(batch, i, k, rec, upd):
+    """``_guard`` for instance i of a batch: a difference raises RuntimeError naming the instance as well as k and the
+    field; a pivot outside [0, n) raises what the sequential solver's update raises, the instance and k in front."""
+    try:
+        _guard(batch, k, rec, upd)
+    except (RuntimeError, ValueError) as err:
+        prefix = "instance %d: " % i if isinstance(err, RuntimeError) else "instance %d, iteration %d: " % (i, k)
+        raise type(err)(prefix + str(err)) from None
+
+
+def D_opt_FW_batch_device(batch, x0, eps, maxitrs, sync_every=SYNC_EVERY_DEFAULT):
+    """D_opt_FW_batch with ``sync_every`` iterations per host round trip: the K instances of a ``DOptimalBatch`` share
+    every launch, and the stop test, the step length and the rank-one coefficients of every instance are computed on
+    the device (accbpg_dopt_batch_fw_run), as D_opt_FW_device computes them for one.  ``x0`` and ``eps`` as
+    D_opt_FW_batch takes them.  The host replays every instance's records through ``_fw_decide`` and compares its own
+    update scalars with the device's bit for bit (RuntimeError naming the instance, k and the field on a difference).
+    An instance that stops inside a chunk idles through the rest of it and is dropped from the next one.  T[k] of all
+    iterations of a chunk is the time at which the chunk's records arrived.  Silent.  Returns a list of K tuples
+    (x, F, SP, SN, T), x, F, SP, SN and the iteration count bit-identical to
+    ``D_opt_FW(batch.instance(i), x0_i, eps_i, maxitrs, verbose=False)``."""
+    return _drain(D_opt_FW_batch_device_steps(batch, x0, eps, maxitrs, sync_every))
+
+
+def D_opt_FW_batch_device_steps(batch, x0, eps, maxitrs, sync_every=SYNC_EVERY_DEFAULT):
+    """Generator form of D_opt_FW_batch_device: yields the last k of each chunk, returns its list."""
+    start_time = time.time()
+    X0, as_numpy = _batch_x0(batch, x0)
+    epsv = _batch_eps(batch, eps)
+    logdet = batch.fw_init(X0)
+    return _fw_batch_device_steps(batch, logdet, epsv, maxitrs, sync_every, start_time, as_numpy)
+
+
+def _fw_batch_device_steps(batch, logdet, epsv, maxitrs, sync_every, start_time, as_numpy=True):
+    """D_opt_FW_batch_device_steps on an initialised batch object (``K``, ``m``, ``fw_run``, ``bad_pivot``, ``fw_x``)."""
+    K, m = batch.K, batch.m
+    F = np.zeros((K, maxitrs)); SP = np.zeros((K, maxitrs)); SN = np.zeros((K, maxitrs)); T = np.zeros((K, maxitrs))
+    detVXVT = [np.exp(ld) for ld in logdet]                     # :41
+    active = [True] * K
+    last = [-1] * K
+    k = 0                                                       # first iteration of the chunk: the running instances share it
+    while k < maxitrs and any(active):
+        S = _chunk(k, maxitrs, sync_every)
+        recs = batch.fw_run(0, epsv, S, active)
+        now = time.time() - start_time
+        for i in range(K):
+            if not active[i]:
+                continue
+            kk = k
+            for rec in recs[i]:
+                F[i, kk] = - np.log(detVXVT[i])                 # :52
+                T[i, kk] = now
+                SP[i, kk], SN[i, kk], upd, detmul = _fw_decide(m, rec.w_i, rec.w_j, epsv[i])
+                last[i] = kk
+                _guard_instance(batch, i, kk, rec, None if upd is None else (rec.i,) + upd)
+                if upd is None:                                 # :72
+                    active[i] = False
+                    break
+                detVXVT[i] *= detmul                            # :80
+                kk += 1
+        k += S
+        if any(active):
+            yield k - 1
+    out = []
+    for i in range(K):
+        e = last[i] + 1
+        out.append((batch.fw_x(i, as_numpy), F[i, :e].copy(), SP[i, :e].copy(), SN[i, :e].copy(), T[i, :e].copy()))
+    return out
+
+
+def D_opt_FW_away_batch_device(batch, x0, eps, maxitrs, sync_every=None, logdet_refresh=None, logdet_ring=None):
+    """D_opt_FW_away_batch with up to ``sync_every`` iterations per host round trip (see D_opt_FW_batch_device and
+    D_opt_FW_away_device).  The chunks are cut as D_opt_FW_away_device cuts them -- all running instances share k, a
+    chunk never spans a multiple of R = ``logdet_refresh`` -- and the snapshots of the running instances are issued
+    between chunks exactly where D_opt_FW_away_batch issues them, so F is formed by the same code from the same
+    anchors.  Returns a list of K tuples (x, F, SP, SN, T), x, F, SP, SN and the iteration count bit-identical to
+    ``D_opt_FW_away(batch.instance(i), x0_i, eps_i, maxitrs, verbose=False, logdet_refresh=..., logdet_ring=...)``."""
+    return _drain(D_opt_FW_away_batch_device_steps(batch, x0, eps, maxitrs, sync_every, logdet_refresh, logdet_ring))
+
+
+def D_opt_FW_away_batch_device_steps(batch, x0, eps, maxitrs, sync_every=None, logdet_refresh=None, logdet_ring=None):
+    """Generator form of D_opt_FW_away_batch_device: yields the last k of each chunk, returns its list."""
+    start_time = time.time()
+    X0, as_numpy = _batch_x0(batch, x0)
+    epsv = _batch_eps(batch, eps)
+    logdet = batch.fw_init(X0)
+    return _away_batch_device_steps(batch, logdet, epsv, maxitrs, sync_every, logdet_refresh, logdet_ring, start_time,
+                                    as_numpy)
+
+
+def _away_batch_device_steps(batch, logdet, epsv, maxitrs, sync_every, logdet_refresh, logdet_ring, start_time,
+                             as_numpy=True):
+    """D_opt_FW_away_batch_device_steps on an initialised batch object (as _fw_batch_device_steps, and
+    ``fw_logdet_ring``, ``fw_logdet_snapshot``, ``fw_logdet_flush``)."""
+    K, m = batch.K, batch.m
+    R, depth = _away_modes(logdet_refresh, logdet_ring)
+    batch.fw_logdet_ring(depth)
+    runs = [_AwayRun(m, maxitrs, R, depth) for _ in range(K)]
+    active = [True] * K
+    nan = float("nan")
+    k = 0
+    while k < maxitrs and any(active):
+        # anchors: a snapshot of H_k per running instance (:136); the chunk starts on the anchor, or holds none
+        collected = batch.fw_logdet_snapshot(active) if runs[0].refresh(k) else [nan] * K
+        S = _chunk(k, maxitrs, sync_every, R)
+        recs = batch.fw_run(1, epsv, S, active)                 # :145-147, :150-179
+        now = time.time() - start_time
+        for i in range(K):
+            if not active[i]:
+                continue
+            kk, coll = k, collected[i]
+            for rec in recs[i]:
+                upd = runs[i].iterate(kk, rec, coll, now, logdet[i], epsv[i])
+                coll = nan
+                _guard_instance(batch, i, kk, rec, upd)
+                if upd is None:                                 # :159
+                    active[i] = False
+                    break
+                kk += 1
+        k += S
+        if any(active):
+            yield k - 1
+    out = []
+    for i in range(K):
+        F, SP, SN, T = runs[i].finish(lambda i=i: batch.fw_logdet_flush(i))
+        out.append((batch.fw_x(i, as_numpy), F.copy(), SP.copy(), SN.copy(), T.copy()))
+    return out

@@ -103,6 +103,8 @@ _SIGS = {
     "accbpg_dopt_batch_fw_probe": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(FwProbe)]),
     "accbpg_dopt_batch_fw_update": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "accbpg_dopt_batch_fw_run": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int),
+                                           C.POINTER(FwStep), C.POINTER(C.c_int)]),
     "accbpg_poisson_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(_P)]),
     "accbpg_poisson_destroy": (C.c_int, [_P]),
     "accbpg_poisson_set_stream": (C.c_int, [_P, _P]),

@@ -52,6 +52,8 @@ class DOptimalBatch:
         # host arrays of the lock-step Frank-Wolfe calls (probe records; p, xscale, xadd, hcoef, hdiv of an update)
         self._fw_probes = (_lib.FwProbe * self.K)()
         self._fw_args = ((C.c_int64 * self.K)(),) + tuple((C.c_double * self.K)() for _ in range(4))
+        self._fw_steps = None                       # K x FW_RUN_MAX records of fw_run (allocated by the first call)
+        self._fw_bad_pivot = ""                     # the library's message of the last fw_run that returned a status 2
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -258,6 +260,36 @@ class DOptimalBatch:
             rc = self._lib.accbpg_dopt_batch_fw_update(self._h, mask, p, xs, xa, hc, hd)
         if rc:
             _lib.check(rc, "accbpg_dopt_batch_fw_update")
+
+    def fw_run(self, away, eps, nsteps, active=None):
+        """``nsteps`` iterations of the active instances decided on the device behind one synchronisation
+        (``accbpg_dopt_batch_fw_run``).  ``eps``: a scalar or one per instance.  Returns a list of K entries: for an active
+        instance the records of the iterations that ran (``_lib.FwStep`` with status != 3; they live in a buffer the
+        next call overwrites), None for an inactive one.  A record with status 2 (pivot outside [0, n)) is returned,
+        not raised: the replay reaches it in its turn and calls ``bad_pivot``."""
+        mask, idx = self._mask(active)
+        K, nsteps = self.K, int(nsteps)
+        if self._fw_steps is None:
+            self._fw_steps = (_lib.FwStep * (K * _lib.FW_RUN_MAX))()
+        epsv = (C.c_double * K)(*np.broadcast_to(np.asarray(eps, dtype=np.float64), (K,)))
+        nrun = (C.c_int * K)()
+        steps = self._fw_steps
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_dopt_batch_fw_run(self._h, int(away), epsv, nsteps, mask, steps, nrun)
+        if rc:
+            if not (rc == _lib.ERR_ARG and any(nrun[i] > 0 and steps[i * nsteps + nrun[i] - 1].status == _lib.FW_BAD_PIVOT
+                                               for i in idx)):
+                _lib.check(rc, "accbpg_dopt_batch_fw_run")
+            self._fw_bad_pivot = _lib.last_error()              # (names the instance; kept for bad_pivot)
+        out = [None] * K
+        for i in idx:
+            out[i] = steps[i * nsteps:i * nsteps + nrun[i]]
+        return out
+
+    def bad_pivot(self):
+        """The exception of the sequential solver's ``update`` with a pivot outside [0, n), with the message of the
+        ``fw_run`` call that returned the status-2 record (it names the instance)."""
+        raise ValueError("accbpg_fw_update: bad argument (%s)" % self._fw_bad_pivot)
 
     def fw_logdet_ring(self, depth, small_launches=2):
         """``accbpg_fw_logdet_ring`` on every instance handle."""

@@ -592,6 +592,93 @@ __global__ __launch_bounds__(FB) void fw_wupdate_probe_run_kernel(const FwRun* _
     fw_wupdate_probe_body(w, n, upart, nsplit, r.hcoef, r.hdiv, x, away, part);
 }
 
+// ---- the step kernels: several iterations per host round trip for the active instances of a batch ---------------
+// (accbpg_dopt_batch_fw_run)  The "batch-run" forms are the two families above at once: the instance is the grid
+// dimension of the lock-step forms and its pointers come from the batch's table; the scalars of its step come from its
+// own FwRunSlot, and a workgroup returns at once when ITS instance has stopped (one load per workgroup, the same for
+// all its threads) while the workgroups of the other instances go on.  blockIdx.x / gridDim.x, the row split, vec_ok,
+// the stage-1 area and AWAY_NB are the single launch's; thread 0 of an instance's final stage calls fw_run_decide with
+// that instance's eps and writes record k of that instance's row of the pinned array.
+__global__ __launch_bounds__(FB) void fw_probe_final_brun_kernel(const FwInst* __restrict__ tab, FwRunSlot* runs,
+                                                                FwProbeArgs pa, ::BatchVals eps, int64_t m, int64_t n,
+                                                                int away, accbpg_fw_step* steps, int k) {
+    const int a = blockIdx.y, i = pa.idx[a];
+    FwRunSlot* sl = runs + i;
+    if (fw_run_stop(&sl->run)) return;
+    const FwInst t = tab[i];
+    fw_probe_final_body(fw_part_of(t, m), pa.nblk[a], t.w, t.x, n, away, sl->rec + 4,
+                        reinterpret_cast<int64_t*>(sl->rec + 8), t.q);
+    if (threadIdx.x == 0)
+        fw_run_decide(&sl->run, sl->rec, m, n, away, eps.v[a], steps + (size_t)i * ACCBPG_FW_RUN_MAX + k);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_partial_brun_kernel(const FwInst* __restrict__ tab,
+                                                                       const FwRunSlot* runs, FwProbeArgs pa, int64_t m,
+                                                                       int64_t n) {
+    const int a = blockIdx.y, i = pa.idx[a];
+    if (fw_run_stop(&runs[i].run)) return;
+    const FwInst t = tab[i];
+    ValIdx* part = fw_part_of(t, m);
+    ValIdx* part2 = part + 2 * 512;
+    fw_probe_away_partial_body(part, pa.nblk[a], t.w, t.x, n, part2, part2 + AWAY_NB);
+}
+__global__ __launch_bounds__(FB) void fw_probe_away_final_brun_kernel(const FwInst* __restrict__ tab, FwRunSlot* runs,
+                                                                     BatchAct act, ::BatchVals eps, int nb2, int64_t m,
+                                                                     int64_t n, accbpg_fw_step* steps, int k) {
+    const int a = blockIdx.y, i = act.idx[a];
+    FwRunSlot* sl = runs + i;
+    if (fw_run_stop(&sl->run)) return;
+    const FwInst t = tab[i];
+    ValIdx* part2 = fw_part_of(t, m) + 2 * 512;
+    fw_probe_away_final_body(part2, nb2, part2 + AWAY_NB, t.w, t.x, n, sl->rec + 4,
+                             reinterpret_cast<int64_t*>(sl->rec + 8), t.q);
+    if (threadIdx.x == 0)
+        fw_run_decide(&sl->run, sl->rec, m, n, 1, eps.v[a], steps + (size_t)i * ACCBPG_FW_RUN_MAX + k);
+}
+__global__ __launch_bounds__(FB) void fw_xupdate_gather_brun_kernel(const FwInst* __restrict__ tab,
+                                                                   const FwRunSlot* __restrict__ runs, BatchAct act,
+                                                                   int64_t m, int64_t n, int64_t ldv) {
+    const int i = act.idx[blockIdx.y];
+    const FwRun r = runs[i].run;
+    if (r.stop) return;
+    const FwInst t = tab[i];
+    fw_xupdate_gather_body(t.x, n, r.p, r.xscale, r.xadd, t.V, ldv, m, t.hv + m);
+}
+__global__ __launch_bounds__(FB) void fw_gemv_h_brun_kernel(const FwInst* __restrict__ tab,
+                                                           const FwRunSlot* __restrict__ runs, BatchAct act, int64_t m) {
+    const int i = act.idx[blockIdx.y];
+    if (runs[i].run.stop) return;
+    const FwInst t = tab[i];
+    fw_gemv_h_body(t.H, m, t.hv + m, t.hv);
+}
+__global__ __launch_bounds__(FB) void fw_rank1_brun_kernel(const FwInst* __restrict__ tab,
+                                                          const FwRunSlot* __restrict__ runs, BatchAct act, int64_t m) {
+    const int i = act.idx[blockIdx.y];
+    const FwRun r = runs[i].run;
+    if (r.stop) return;
+    const FwInst t = tab[i];
+    fw_rank1_body(t.H, m, t.hv, r.hcoef, r.hdiv, t.hv + m, t.q);
+}
+__global__ __launch_bounds__(FB) void fw_vgemv_partial_brun_kernel(const FwInst* __restrict__ tab,
+                                                                  const FwRunSlot* __restrict__ runs, BatchAct act,
+                                                                  int64_t ldv, int64_t m, int64_t n, int nsplit) {
+    const int i = act.idx[blockIdx.z];
+    if (runs[i].run.stop) return;
+    const FwInst t = tab[i];
+    fw_vgemv_partial_body(t.V, ldv, m, n, t.hv, nsplit, t.vws, t.vec_ok != 0);
+}
+__global__ __launch_bounds__(FB) void fw_wupdate_probe_brun_kernel(const FwInst* __restrict__ tab,
+                                                                  const FwRunSlot* __restrict__ runs, BatchAct act,
+                                                                  int64_t m, int64_t n, int nsplit, int away) {
+    const int i = act.idx[blockIdx.y];
+    const FwRun r = runs[i].run;
+    if (r.stop) return;
+    const FwInst t = tab[i];
+    fw_wupdate_probe_body(t.w, n, t.vws, nsplit, r.hcoef, r.hdiv, t.x, away, fw_part_of(t, m));
+}
+// what a launch of the family carries by value at most: the active set, the stage-1 records of the first iteration
+// and eps, far inside the 4 KiB of kernel arguments at K = ACCBPG_BATCH_MAX
+static_assert(sizeof(FwProbeArgs) + sizeof(::BatchVals) + 64 <= 4096, "batch-run kernel arguments");
+
 // u = sum of the row-split partials (u = V^T q)
 __global__ __launch_bounds__(FB) void fw_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
                                                     double* __restrict__ u) {
@@ -1148,6 +1235,123 @@ extern "C" int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* acti
     fw_wupdate_probe_batch_kernel<<<dim3((unsigned)wb, na), FB, 0, s>>>(b->fw_table, ua, m, n, ns);
     for (int a = 0; a < ua.n; ++a) b->inst[ua.idx[a]]->fw_part_nblk = (int)wb;
     ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+
+// ---- several iterations per synchronisation for the active instances (accbpg_dopt_batch_fw_run) ------------------
+static int fw_batch_run_alloc(accbpg_dopt_batch* b) {
+    if (!b->fw_bsteps_pin) {
+        ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->fw_bsteps_pin),
+                              sizeof(accbpg_fw_step) * ACCBPG_FW_RUN_MAX * (size_t)b->K, hipHostMallocDefault));
+        ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->fw_bsteps_dev), b->fw_bsteps_pin, 0));
+    }
+    if (!b->fw_runs) ACC_HIP(hipMalloc(reinterpret_cast<void**>(&b->fw_runs), sizeof(FwRunSlot) * (size_t)b->K));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const double* eps_host, int nsteps,
+                                        const int* active_host, accbpg_fw_step* steps_host, int* nrun_host) {
+    if (!b || !eps_host || !steps_host || !nrun_host || nsteps < 1 || nsteps > ACCBPG_FW_RUN_MAX) return ACCBPG_ERR_ARG;
+    const int64_t m = b->inst[0]->m, n = b->inst[0]->n, ldv = b->inst[0]->ldv;
+    int nblk0 = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
+    if (nblk0 < 1) nblk0 = 1;
+    if (nblk0 > 512) nblk0 = 512;
+    FwProbeArgs pa;                                             // the active set, and each instance's nblk at iteration 0
+    BatchAct act, fresh;
+    ::BatchVals eps;
+    for (int i = 0; i < b->K; ++i) {
+        if (active_host && !active_host[i]) continue;
+        accbpg_dopt* h = b->inst[i];
+        if (!h->fw_ready || !b->fw_table) {
+            set_last_error("accbpg_dopt_batch_fw_run: instance %d has no Frank-Wolfe state (accbpg_dopt_batch_fw_init)", i);
+            return ACCBPG_ERR_ARG;                              // (nothing has been launched)
+        }
+        const int a = pa.n++;
+        pa.idx[a] = i;
+        act.idx[act.n++] = i;
+        eps.v[a] = eps_host[i];
+        if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
+            pa.nblk[a] = h->fw_part_nblk;                       // stage 1 came with the last update of w
+        } else {
+            pa.nblk[a] = nblk0;
+            fresh.idx[fresh.n++] = i;
+        }
+    }
+    if (pa.n == 0) return ACCBPG_OK;
+    ACC_TRY(fw_batch_run_alloc(b));
+    const unsigned na = (unsigned)pa.n;
+    hipStream_t s = b->stream;
+    for (int a = 0; a < pa.n; ++a) {                            // (nothing of an earlier call is in flight: it synchronised)
+        accbpg_fw_step* row = b->fw_bsteps_pin + (size_t)pa.idx[a] * ACCBPG_FW_RUN_MAX;
+        for (int k = 0; k < nsteps; ++k) {
+            row[k] = accbpg_fw_step{};
+            row[k].p = -1;
+            row[k].kind = -1;
+            row[k].status = 3;
+        }
+        b->inst[pa.idx[a]]->fw_part_nblk = 0;                   // (no claim of reuse survives an error return below)
+        b->inst[pa.idx[a]]->fw_part_away = (away != 0);
+    }
+    ACC_HIP(hipMemsetAsync(b->fw_runs, 0, sizeof(FwRunSlot) * (size_t)b->K, s));
+    // the grids of accbpg_fw_run, times the active instances
+    int nb2 = nblk0;
+    if (nb2 > AWAY_NB) nb2 = AWAY_NB;
+    int64_t gb = (std::max(n, m) + FB - 1) / FB;
+    if (gb > 1024) gb = 1024;
+    const int64_t pairs = (m + 1) / 2;
+    const unsigned hb = (unsigned)((pairs + FB / 64 - 1) / (FB / 64));
+    int64_t rb = m;
+    if (rb > 4096) rb = 4096;
+    const int ns = fw_nsplit(b->inst[0]);                       // one shape, one device: every instance's own partition
+    const dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns, na);
+    int64_t wb = (n + FB - 1) / FB;
+    if (wb > 512) wb = 512;
+    if (fresh.n > 0)
+        fw_probe_partial_batch_kernel<<<dim3((unsigned)nblk0, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, away);
+    for (int k = 0; k < nsteps; ++k) {
+        if (away && n >= 4096) {
+            fw_probe_away_partial_brun_kernel<<<dim3((unsigned)nb2, na), FB, 0, s>>>(b->fw_table, b->fw_runs, pa, m, n);
+            fw_probe_away_final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, eps, nb2, m, n,
+                                                                       b->fw_bsteps_dev, k);
+        } else {
+            fw_probe_final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, b->fw_runs, pa, eps, m, n, away,
+                                                                  b->fw_bsteps_dev, k);
+        }
+        fw_xupdate_gather_brun_kernel<<<dim3((unsigned)gb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m, n, ldv);
+        fw_gemv_h_brun_kernel<<<dim3(hb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m);
+        fw_rank1_brun_kernel<<<dim3((unsigned)rb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m);
+        fw_vgemv_partial_brun_kernel<<<vg, FB, 0, s>>>(b->fw_table, b->fw_runs, act, ldv, m, n, ns);
+        fw_wupdate_probe_brun_kernel<<<dim3((unsigned)wb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m, n, ns,
+                                                                          away ? 1 : 0);
+        if (k == 0)
+            for (int a = 0; a < pa.n; ++a) pa.nblk[a] = (int)wb;     // the next probe's stage 1 came with this update
+    }
+    const hipError_t launched = hipGetLastError();
+    ACC_HIP(hipStreamSynchronize(s));                           // (also behind a launch error: nothing stays in flight)
+    ACC_HIP(launched);
+    int bad_inst = -1;
+    long long bad_p = 0;
+    for (int a = 0; a < act.n; ++a) {
+        const int i = act.idx[a];
+        const accbpg_fw_step* row = b->fw_bsteps_pin + (size_t)i * ACCBPG_FW_RUN_MAX;
+        accbpg_fw_step* out = steps_host + (size_t)i * nsteps;
+        int nrun = 0;
+        for (int k = 0; k < nsteps; ++k) {
+            out[k] = row[k];
+            if (row[k].status != 3) ++nrun;
+            if (row[k].status == 2 && bad_inst < 0) {
+                bad_inst = i;
+                bad_p = (long long)row[k].p;
+            }
+        }
+        nrun_host[i] = nrun;
+        // what a later probe of this instance finds: as accbpg_fw_run leaves it on the handle
+        b->inst[i]->fw_part_nblk = (nrun == nsteps && out[nsteps - 1].status == 0) ? (int)wb : 0;
+    }
+    if (bad_inst >= 0) {
+        set_last_error("accbpg_dopt_batch_fw_run: instance %d: pivot index %lld outside [0, n)", bad_inst, bad_p);
+        return ACCBPG_ERR_ARG;
+    }
     return ACCBPG_OK;
 }
 

@@ -109,6 +109,14 @@ struct FwRun {
     double xscale, xadd, hcoef, hdiv;
 };
 
+// The same for one instance of a batch (accbpg_dopt_batch_fw_run): the batch owns K of these, entry i = instance i.  rec
+// is the scratch probe record of the final stage, laid out as the pinned one.  The lock-step kernels (FwInst) never
+// see them.
+struct FwRunSlot {
+    FwRun run;
+    double rec[16];
+};
+
 struct CholJob { int i, j; };                     // i == j: owner of the diagonal tile (and of (i, i-1))
 struct CholInst {                                  // one factorisation (one entry per instance of a batched launch)
     const double* src;      // matrix to factor (lower triangle significant), leading dimension ld
@@ -263,6 +271,11 @@ struct accbpg_dopt_batch {
     double* vws = nullptr;                  // workspace of the single-instance prox (long vectors, one instance at a time)
     double* vpin = nullptr;                 // pinned mirror (K * 8 doubles)
     accbpg::FwInst* fw_table = nullptr;     // device, K entries: Frank-Wolfe state of every instance (built by the first accbpg_dopt_batch_fw_init)
+    // accbpg_dopt_batch_fw_run (allocated by the first call): every instance's step scalars + scratch record on the
+    // device, and the records of a call in pinned host memory, row i (ACCBPG_FW_RUN_MAX records) = instance i
+    accbpg::FwRunSlot* fw_runs = nullptr;
+    accbpg_fw_step* fw_bsteps_pin = nullptr;
+    accbpg_fw_step* fw_bsteps_dev = nullptr;    // ... as the device addresses them
     // the evaluation in flight between _begin and _end
     accbpg::BatchAct pend_act;
     const double* pend_x = nullptr;

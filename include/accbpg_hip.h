@@ -332,6 +332,24 @@ int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* active_host, co
                                 const double* xscale_host, const double* xadd_host, const double* hcoef_host,
                                 const double* hdiv_host);
 
+/* accbpg_fw_run for the active instances of a batch in lock-step: ONE launch per step kernel covers the active
+ * instances (active_host[i] != 0; NULL = all; the set is fixed for the call), the decisions of every iteration are
+ * taken on the device per instance, as accbpg_fw_run takes them and with eps_host[i], and ONE synchronisation returns
+ * all records.  eps_host and nrun_host have K entries, steps_host K * nsteps: row i (nsteps records) belongs to
+ * instance i; entries of inactive instances are neither read nor written.  1 <= nsteps <= ACCBPG_FW_RUN_MAX.
+ * An instance that stops in mid-call (status 1 or 2) idles through the rest of the call while the others go on: its
+ * x, w, H, stage-1 records and q_prev stay as the stop found them and its later records read status 3, as after
+ * accbpg_fw_run.  Grids, row split and summation order of every instance are the single handle's, so x, w, H and the
+ * records of instance i are bit for bit those of accbpg_fw_run(accbpg_dopt_batch_instance(b, i), away, eps_host[i],
+ * nsteps, ...), and what the call leaves on the handle is what that call leaves: it may be mixed freely with
+ * accbpg_fw_run, accbpg_fw_probe_step / accbpg_fw_update on the instance handles and accbpg_dopt_batch_fw_probe /
+ * _fw_update.  An active instance without Frank-Wolfe state returns ACCBPG_ERR_ARG before anything is launched.  A
+ * pivot outside [0, n) (status 2) on any instance makes the call return ACCBPG_ERR_ARG with the (first such) instance
+ * named in the message; all records are filled in all the same.  Scratch is allocated by the first call and freed by
+ * accbpg_dopt_batch_destroy. */
+int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const double* eps_host, int nsteps, const int* active_host,
+                             accbpg_fw_step* steps_host, int* nrun_host);
+
 /* ---- Poisson linear inverse problem with Burg L1 / L2 kernels -------- */
 
 typedef struct accbpg_poisson accbpg_poisson;

@@ -80,9 +80,17 @@ def case(m, n, K, iters, routes):
                 r["sequential"] = K * iters / dt
                 finals["sequential"] = [float(t[1][-1]) for t in res]
             del objs, probs
-        vals = list(finals.values())
-        assert all(v == vals[0] for v in vals), "the routes disagree on F[-1]"
+        # threads and sequential run on the same kind of handle: bit for bit.  The batch's instances are planned for
+        # sharing the chip (256 x 128 Gram tiles also at m = 512, a capped stream-K grid), so their Gram matrices of x0
+        # are summed in another order than a DOptimalObj's: against those F[-1] is held to the bar the trajectory
+        # tests use between two summation orders (rtol 1e-9), and the distance is recorded.
+        single = [finals[k] for k in ("threads8", "sequential") if k in finals]
+        assert all(v == single[0] for v in single), "threads and sequential disagree on F[-1]"
         rec[name] = {k: round(v, 1) for k, v in r.items()}
+        if "batch" in finals and single:
+            rel = np.abs(np.array(finals["batch"]) - np.array(single[0])) / np.abs(np.array(single[0]))
+            assert np.all(rel <= 1e-9), "the batch and the single handles disagree on F[-1] (max rel %.3e)" % rel.max()
+            rec[name]["batch_F_last_max_rel_diff_to_single_handles"] = float(rel.max())
         finals.clear()
     return rec
 
@@ -99,7 +107,8 @@ def main():
         "cases": cases,
         "method": "wall clock around the whole solve of all K instances (initialisation included, no warm-up), eps = -1, "
                   "uniform x0, D_opt_design(m, n, randseed=11+i); D_opt_FW_away with its default logdet_refresh; every "
-                  "route's F[-1] compared bit for bit",
+                  "route's F[-1] compared (threads8 and sequential bit for bit; the batch, whose instances use the batch's Gram "
+                  "plan, within rtol 1e-9 of them)",
     }
     if ARGS.baseline:
         with open(ARGS.baseline) as fh:

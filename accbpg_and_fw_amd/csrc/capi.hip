@@ -455,3 +455,8 @@ extern "C" int accbpg_debug_gram_variant(accbpg_dopt* h, const double* x_dev, in
     if (!h || !x_dev || !ms_host || iters <= 0) return ACCBPG_ERR_ARG;
     return debug_gram_variant(h, x_dev, variant, iters, ms_host);
 }
+
+extern "C" int accbpg_debug_grad_variant(accbpg_dopt* h, double* g_dev, int variant, int iters, double* ms_host) {
+    if (!h || !g_dev || !ms_host || iters <= 0) return ACCBPG_ERR_ARG;
+    return debug_grad_variant(h, g_dev, variant, iters, ms_host);
+}

@@ -580,12 +580,155 @@ __global__ __launch_bounds__(NTHREADS, 1) void colnorm_kernel(
 }
 
 // Direct-to-LDS version of the gradient kernel for interior sizes.
-// CV: 32 = dealt-out schedule, 64 = its placement B (both development variants), 256 = loads four to an M0 write.
-constexpr int COLNORM_CV = 256; // the production gradient kernel: block schedule, loads four to an M0 write
-template <class T, int CV = 0>
-__device__ __forceinline__ void colnorm_glds_body(
+// CV: 32 = dealt-out schedule, 64 = its placement B (both development variants), 256 = loads four to an M0 write,
+// 512 = the production schedule before the k loop was split into phases (runtime triangular skip, pipeline restarted
+// per row block); with 512, bits 0..3 are timing ablations of that loop (wrong results): 1 = rectangular k-steps only,
+// 2 = diagonal k-steps only, 4 = MFMAs only (no loads, fragment reads, wait or barrier in the loop), 8 = no drain and
+// restart between row blocks (from the second row block on the stages are read without the barrier that orders them
+// behind their loads: a race by design, the variant is for timing only).
+constexpr int COLNORM_CV = 256; // the production gradient kernel: two phases per row block, one pipeline per workgroup
+
+// One k-step of the diagonal part of a row block: step j = 4 G + JJ of 16 (columns 16 j .. 16 j + 15 of the 256 x 256
+// diagonal block of W).  Fragment i of wave-row wm covers rows 16 (4 i + wm) .. + 15 of it, so its first live fragment
+// row is G + (JJ > wm ? 1 : 0): rows below G are dead for every wave, rows above G live for every wave, and row G is
+// live for the waves with wm >= JJ.  The loads of the step two ahead go out as in every step; for the last two steps of
+// the row block they are the first two stages of the NEXT row block (base `next_a`, k-steps 0 and 1), whose stage slots
+// are free by the rotation -- the pipeline does not drain between row blocks.
+template <class T, int G, int JJ, int RUN, int NLD>
+__device__ __forceinline__ void colnorm_diag_step(T& t, double* __restrict__ lds, int& cur, int wm, int64_t kdiag,
+                                                  int64_t ldv, const char* next_a) {
+    int nx1 = cur + 1;
+    if (nx1 >= 3) nx1 -= 3;
+    int nx2 = cur + 2;
+    if (nx2 >= 3) nx2 -= 3;
+    constexpr int J = 4 * G + JJ;
+    int64_t k2 = kdiag + J + 2;
+    if constexpr (J >= 14) {
+        if constexpr (J == 14) t.gbase_a = next_a;
+        k2 = J - 14;
+    }
+    constexpr int ILO_NEXT = JJ == 3 ? ((G + 1) & 3) : G;
+    t.template grad_step<RUN, G, ILO_NEXT, (JJ > 0), NLD>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE,
+                                                          k2 * BK, k2 * BK * ldv, wm >= JJ);
+    cur = nx1;
+}
+template <class T, int G, int RUN, int NLD>
+__device__ __forceinline__ void colnorm_diag_group(T& t, double* __restrict__ lds, int& cur, int wm, int64_t kdiag,
+                                                   int64_t ldv, const char* next_a) {
+    colnorm_diag_step<T, G, 0, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 1, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 2, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 3, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+}
+
+// The production loop.  Row block rb = 16 rb rectangular k-steps (every fragment row live: one basic block of 128 MFMAs
+// per step, no triangular skip in it) + 16 diagonal k-steps in four groups with the skip a template constant.  One
+// pipeline per workgroup: three stages rotate through all row blocks, the full-latency wait happens once, and the squares
+// of a row block and the zeroing of the accumulators run while the first two stages of the next one are in flight.
+// Every accumulator receives the MFMAs it received before, in the same k order, and colsum is added to in the same order.
+template <class T>
+__device__ __forceinline__ void colnorm_phases_body(
     const double* __restrict__ W, int64_t ldw, const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n,
     double* __restrict__ out, double sign) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* red = lds + 3 * T::G_STAGE;                         // [4][BN] behind the stages
+    constexpr int NLD = T::G_NA + T::G_NB;
+    constexpr int RUN = 4;                                      // loads per M0 write (mfma_tile.hpp: glds16_run4)
+    static_assert(T::WAVES_N == 1 && T::MI == 4 && T::BM == 16 * BK, "diagonal groups are laid out for the 256 x 128 tile");
+    const int64_t col0 = (int64_t)blockIdx.x * T::BN;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wm = wave / T::WAVES_N, wn = wave % T::WAVES_N;
+    const int lr = lane & 15;
+    double colsum[T::NI];
+#pragma unroll
+    for (int j = 0; j < T::NI; ++j) colsum[j] = 0.0;
+    T t;
+    const int nrb = (int)(m / T::BM);
+    // (the lane offsets do not depend on the row block: a row block changes the scalar base of the A loads only)
+    t.template glds_setup_A<RUN>(W, ldw, 0);
+    t.template glds_setup_B_km<RUN>(V, ldv, col0);
+    t.template glds_issue<RUN>(0, 0, lds);
+    t.template glds_issue<RUN>(BK, BK * ldv, lds + T::G_STAGE);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
+    __builtin_amdgcn_s_barrier();
+    int cur = 0;
+    t.template read_frag_lo<0, 0>(lds, 0);
+    t.zero();
+    t.pin_acc();
+    // The loop over the row blocks is rotated: a trip is the diagonal phase of row block rb, its squares, and the
+    // rectangular phase of row block rb + 1 (16 (rb + 1) >= 16 k-steps) -- row block 0 has no rectangular phase, and so
+    // no loop here ever runs zero times.
+    for (int rb = 0;;) {
+        const int64_t kdiag = (int64_t)rb * (T::BM / BK);       // W is lower triangular: k-steps [0, kdiag) are rectangular
+        // the row block whose first two stages the last two steps load (the last one loads its own again: every wave
+        // retires the same number of loads in every step)
+        const int rbn = rb + 1 < nrb ? rb + 1 : rb;
+        const char* next_a = reinterpret_cast<const char*>(W + (int64_t)rbn * T::BM * ldw);
+        colnorm_diag_group<T, 0, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 1, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 2, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 3, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+        // square and add this row block's Y into the per-column sums; the next row block's stages are in flight
+#pragma unroll
+        for (int j = 0; j < T::NI; ++j) {
+            t.pin_acc_col(j);
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < T::MI; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s += t.acc[i][j][r] * t.acc[i][j][r];
+            colsum[j] += s;
+            // (column by column, and finished here: read all at once and summed later, the tile would have to sit in the
+            //  other register file, which does not hold it)
+            asm volatile("" : "+v"(colsum[j]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (++rb == nrb) break;
+        t.zero();
+        t.pin_acc();
+        const int64_t krect = (int64_t)rb * (T::BM / BK);
+        int64_t ks = 0;
+#pragma unroll 1
+        do {
+            int nx1 = cur + 1;
+            if (nx1 >= 3) nx1 -= 3;
+            int nx2 = cur + 2;
+            if (nx2 >= 3) nx2 -= 3;
+            const int64_t k2 = (ks + 2) * BK;
+            t.template grad_step<RUN, 0, 0, false, NLD>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE,
+                                                        k2, k2 * ldv, true);
+            cur = nx1;
+        } while (++ks < krect);
+    }
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < T::NI; ++j) {
+        double s = colsum[j];
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        colsum[j] = s;
+    }
+    __syncthreads();
+    if (lane < 16) {
+#pragma unroll
+        for (int j = 0; j < T::NI; ++j) red[wm * T::BN + wn * T::WN + 16 * j + lr] = colsum[j];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < T::BN; c += NTHREADS) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < T::WAVES_M; ++w) s += red[w * T::BN + c];
+        if (col0 + c < n) out[col0 + c] = sign * s;
+    }
+}
+
+// The development variants and the production loop before the two phases: the triangular skip is a runtime value in every
+// k-step, and the pipeline drains and restarts per row block.
+template <class T, int CV>
+__device__ __forceinline__ void colnorm_restart_body(
+    const double* __restrict__ W, int64_t ldw, const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n,
+    double* __restrict__ out, double sign) {
+    constexpr int AB = (CV & 512) ? (CV & 15) : 0;              // timing ablations of the loop below
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* red = lds + 3 * T::G_STAGE;                         // [4][BN] behind the stages
     constexpr int NLD = T::G_NA + T::G_NB;
@@ -609,18 +752,21 @@ __device__ __forceinline__ void colnorm_glds_body(
         auto issue = [&](int64_t ks, int buf) {
             t.template glds_issue<RUN>(ks * BK, ks * BK * ldv, lds + buf * T::G_STAGE);
         };
-        __builtin_amdgcn_s_barrier();
-        issue(0, 0);
-        issue(min((int64_t)1, klast), 1);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-        __builtin_amdgcn_s_barrier();
+        const int64_t ks0 = (AB & 2) ? row0 / BK : 0, ks1 = (AB & 1) ? row0 / BK : ksteps;
+        if (!(AB & 8) || rb == 0) {
+            __builtin_amdgcn_s_barrier();
+            issue(ks0, 0);
+            issue(min(ks0 + 1, klast), 1);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
+            __builtin_amdgcn_s_barrier();
+        }
         int cur = 0;
         t.template read_frag_g<0, false>(lds, 0);
         if constexpr (CV & 32) {
             // dealt-out schedule, as in the Gram kernel (gram_streamk_glds_body, GV & 32)
             constexpr int NP = T::G_NA + T::G_NB;
 #pragma unroll 1
-            for (int64_t ks = 0; ks < ksteps; ++ks) {
+            for (int64_t ks = ks0; ks < ks1; ++ks) {
                 int nx2 = cur + 2;
                 if (nx2 >= 3) nx2 -= 3;
                 int nx1 = cur + 1;
@@ -673,7 +819,7 @@ __device__ __forceinline__ void colnorm_glds_body(
             }
         } else {
 #pragma unroll 1
-        for (int64_t ks = 0; ks < ksteps; ++ks) {
+        for (int64_t ks = ks0; ks < ks1; ++ks) {
             int nx2 = cur + 2;
             if (nx2 >= 3) nx2 -= 3;
             const double* st = lds + cur * T::G_STAGE;
@@ -690,35 +836,37 @@ __device__ __forceinline__ void colnorm_glds_body(
             static_assert(T::MI == 4, "group 0 is dealt out over four fragment rows");
             double* nst = lds + nx2 * T::G_STAGE;
             const int64_t k2 = min(ks + 2, klast) * BK;
-            t.template read_frag_g<1, false>(st, 1);
+            if constexpr (!(AB & 4)) t.template read_frag_g<1, false>(st, 1);
             __builtin_amdgcn_sched_barrier(0);
             t.template mma_row<0>(0, mi_lo);
-            t.template glds_issue_range<RUN>(k2, k2 * ldv, nst, 0, P1);
+            if constexpr (!(AB & 4)) t.template glds_issue_range<RUN>(k2, k2 * ldv, nst, 0, P1);
             t.template mma_row<0>(1, mi_lo);
-            t.template glds_issue_range<RUN>(k2, k2 * ldv, nst, P1, P2);
+            if constexpr (!(AB & 4)) t.template glds_issue_range<RUN>(k2, k2 * ldv, nst, P1, P2);
             t.template mma_row<0>(2, mi_lo);
-            t.template glds_issue_range<RUN>(k2, k2 * ldv, nst, P2, NP);
+            if constexpr (!(AB & 4)) t.template glds_issue_range<RUN>(k2, k2 * ldv, nst, P2, NP);
             t.template mma_row<0>(3, mi_lo);
             __builtin_amdgcn_sched_barrier(0);
-            t.template read_frag_g<0, false>(st, 2);
+            if constexpr (!(AB & 4)) t.template read_frag_g<0, false>(st, 2);
             __builtin_amdgcn_sched_barrier(0);
             t.template mma_frag<1>(mi_lo);
             __builtin_amdgcn_sched_barrier(0);
-            t.template read_frag_g<1, false>(st, 3);
+            if constexpr (!(AB & 4)) t.template read_frag_g<1, false>(st, 3);
             __builtin_amdgcn_sched_barrier(0);
             t.template mma_frag<0>(mi_lo);
             __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
-            __builtin_amdgcn_s_barrier();
+            if constexpr (!(AB & 4)) {
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
+                __builtin_amdgcn_s_barrier();
+            }
             cur = (cur + 1 == 3) ? 0 : cur + 1;
             // first fragments of the next stage land under the last group's MFMAs
-            t.template read_frag_g<0, false>(lds + cur * T::G_STAGE, 0);
+            if constexpr (!(AB & 4)) t.template read_frag_g<0, false>(lds + cur * T::G_STAGE, 0);
             __builtin_amdgcn_sched_barrier(0);
             t.template mma_frag<1>(mi_lo);
             __builtin_amdgcn_sched_barrier(0);
         }
         }
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+        if (!(AB & 8) || rb == nrb - 1) asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int j = 0; j < T::NI; ++j) {
             double s = 0.0;
@@ -748,6 +896,14 @@ __device__ __forceinline__ void colnorm_glds_body(
         for (int w = 0; w < T::WAVES_M; ++w) s += red[w * T::BN + c];
         if (col0 + c < n) out[col0 + c] = sign * s;
     }
+}
+
+template <class T, int CV = 0>
+__device__ __forceinline__ void colnorm_glds_body(
+    const double* __restrict__ W, int64_t ldw, const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n,
+    double* __restrict__ out, double sign) {
+    if constexpr (CV == COLNORM_CV) colnorm_phases_body<T>(W, ldw, V, ldv, m, n, out, sign);
+    else colnorm_restart_body<T, CV>(W, ldw, V, ldv, m, n, out, sign);
 }
 
 template <class T, int CV = 0>
@@ -2841,6 +2997,8 @@ int launch_colnorm(accbpg_dopt* h, const double* W, double* out, double sign) {
                 ACC_LAUNCH_LDS((colnorm_glds_kernel<T, COLNORM_CV ^ 256>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
             else if (h->kern_variant == 2)
                 ACC_LAUNCH_LDS((colnorm_glds_kernel<T, 96>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
+            else if (h->kern_variant == 3)        // the production schedule before the two phases: runtime skip, restart per row block
+                ACC_LAUNCH_LDS((colnorm_glds_kernel<T, COLNORM_CV | 512>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
             else
                 ACC_LAUNCH_LDS((colnorm_glds_kernel<T, COLNORM_CV>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
         } else if (interior) colnorm_launch_t<TileBig<true, false>>(h, W, out, sign, vw);
@@ -2936,6 +3094,55 @@ int launch_trtri_batch(accbpg_dopt_batch* b, const BatchAct& act) {
     prof_end(h0, PROF_TRTRI);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
+}
+
+// timing ablations of the gradient kernel (big interior tile, direct-to-LDS only); returns average ms over `iters`.
+// var: 0 = production, 3 = the schedule before the two phases, 10..13 = that schedule with rectangular k-steps only /
+// diagonal k-steps only / MFMAs only / no drain and restart between row blocks (10..13 write wrong results to `out`).
+int debug_grad_variant(accbpg_dopt* h, double* out, int var, int iters, double* ms_out) {
+    using T = TileBig<true, false>;
+    const bool vw = ((reinterpret_cast<uintptr_t>(h->Wbuf) & 15) == 0) && ((h->m & 1) == 0);
+    if (!h->big || !h->use_glds || !vw || !h->vec_ok || h->m % 256 != 0 || h->n % 128 != 0) return ACCBPG_ERR_ARG;
+    const int grid = (int)(h->n / T::BN), lds = T::G_LDS_BYTES + 4 * T::BN * 8;
+    if (var != 0 && var != 3 && (var < 10 || var > 13)) return ACCBPG_ERR_ARG;
+    hipEvent_t a, b;
+    ACC_HIP(hipEventCreate(&a));
+    if (hipEventCreate(&b) != hipSuccess) {
+        hipEventDestroy(a);
+        return ACCBPG_ERR_HIP;
+    }
+    auto launch = [&]() -> int {
+#define ACC_LAUNCH_C(CC) \
+    ACC_LAUNCH_LDS((colnorm_glds_kernel<T, CC>), grid, NTHREADS, lds, h->stream, h->Wbuf, h->m, h->V, h->ldv, h->m, h->n, out, -1.0)
+        switch (var) {
+            case 0: ACC_LAUNCH_C(COLNORM_CV); break;
+            case 3: ACC_LAUNCH_C(COLNORM_CV | 512); break;
+            case 10: ACC_LAUNCH_C(COLNORM_CV | 512 | 1); break;
+            case 11: ACC_LAUNCH_C(COLNORM_CV | 512 | 2); break;
+            case 12: ACC_LAUNCH_C(COLNORM_CV | 512 | 4); break;
+            case 13: ACC_LAUNCH_C(COLNORM_CV | 512 | 8); break;
+            default: return ACCBPG_ERR_ARG;
+        }
+#undef ACC_LAUNCH_C
+        return ACCBPG_OK;
+    };
+    // (the events are destroyed on every way out)
+    auto timed = [&]() -> int {
+        ACC_TRY(launch());
+        ACC_HIP(hipEventRecord(a, h->stream));
+        for (int i = 0; i < iters; ++i) ACC_TRY(launch());
+        ACC_HIP(hipEventRecord(b, h->stream));
+        ACC_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        ACC_HIP(hipEventElapsedTime(&ms, a, b));
+        *ms_out = ms / iters;
+        ACC_HIP(hipGetLastError());
+        return ACCBPG_OK;
+    };
+    const int rc = timed();
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    return rc;
 }
 
 int launch_colnorm_batch(accbpg_dopt_batch* b, const BatchAct& act, double* gbase, int64_t ldg, double sign) {

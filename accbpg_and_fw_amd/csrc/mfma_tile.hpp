@@ -87,6 +87,25 @@ struct Tile {
             for (int j = 0; j < NI; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
     }
 
+    // Names the accumulator file as the home of every accumulator at this point (an empty statement: no instruction).
+    // Between two loops that both run MFMAs on the whole tile the register allocator otherwise parks part of it in
+    // the other file and moves it over and back in every trip of the loop.
+    __device__ __forceinline__ void pin_acc() {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NI; ++j) asm volatile("" : "+a"(acc[i][j]));
+    }
+
+    // the same for column fragment j_rt only (right before a vector-pipe use of that column)
+    __device__ __forceinline__ void pin_acc_col(int j_rt) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NI; ++j)
+                if (j == j_rt) asm volatile("" : "+a"(acc[i][j]));
+    }
+
     // ---- global -> registers -------------------------------------------------------------
     // A: rows [row0, row0+BM) of a k-contiguous matrix (lda), columns [k0, k0+16).
     __device__ __forceinline__ void gload_A(const double* __restrict__ A, int64_t lda, int64_t row0, int64_t M,
@@ -476,6 +495,81 @@ struct Tile {
             acc[I][2 * P] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[SET][I], fb[SET][2 * P], acc[I][2 * P], 0, 0, 0);
             acc[I][2 * P + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[SET][I], fb[SET][2 * P + 1], acc[I][2 * P + 1], 0, 0, 0);
         }
+    }
+
+    // ---- gradient product: k-steps with the triangular skip resolved at compile time -------------
+    // ILO = first fragment row of the step that can be non-zero.  Rows below it do not exist in the step (no MFMAs, no
+    // A-fragment reads), rows above it are live for every wave, and row ILO itself is live for the waves that say so
+    // (COND; one wave-uniform condition per step) or for all of them (!COND: the rectangular part of a row block and
+    // the first step of a diagonal group).  Plain member templates on purpose: the same split through a generic lambda
+    // made the register allocator move accumulators between the register files inside the loop (tests/test_isa_cpu.py).
+    template <int SET, int ILO>
+    __device__ __forceinline__ void read_frag_lo(const double* __restrict__ stage, int kk) {
+        static_assert(BKM, "the gradient product reads a k-major B image");
+        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+        const int lr = lane & 15, lq = lane >> 4;
+        const int sw = (lr >> 1) & 7;
+        const int koff = 2 * ((2 * kk + (lq >> 1)) ^ sw) + (lq & 1);      // swizzled position of k = 4kk+lq
+        const double* as = stage + (16 * wm + lr) * BK + koff;
+#pragma unroll
+        for (int i = ILO; i < MI; ++i) fa[SET][i] = as[i * 16 * WAVES_M * BK];
+        const double* bs = stage + G_A + (4 * kk + lq) * BN + wn * WN + lr;
+#pragma unroll
+        for (int j = 0; j < NI; ++j) fb[SET][j] = bs[16 * (j ^ (lq & 1))];
+    }
+    template <int SET, int I, int ILO, bool COND>
+    __device__ __forceinline__ void mma_row_lo(bool live) {
+        if constexpr (I >= ILO) {
+            if (!(COND && I == ILO) || live) {
+#pragma unroll
+                for (int j = 0; j < NI; ++j)
+                    acc[I][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[SET][I], fb[SET][j], acc[I][j], 0, 0, 0);
+            }
+        }
+    }
+    template <int SET, int ILO, bool COND>
+    __device__ __forceinline__ void mma_frag_lo(bool live) {
+        static_assert(MI == 4, "four fragment rows");
+        mma_row_lo<SET, 0, ILO, COND>(live);
+        mma_row_lo<SET, 1, ILO, COND>(live);
+        mma_row_lo<SET, 2, ILO, COND>(live);
+        mma_row_lo<SET, 3, ILO, COND>(live);
+    }
+    // One k-step of the block schedule (colnorm_phases_body in dopt_kernels.hip): stage `st` is consumed, the NLD loads of the step two ahead
+    // (element offsets ka / kb from the current bases) go to `nst` between the fragment rows of group 0, and the first
+    // fragments of the next step (stage `st1`, first live row ILO_NEXT) are read under the last group's MFMAs.  The
+    // counted wait leaves the NLD newest loads in flight, so it carries from step to step and across row blocks.
+    template <int RUN, int ILO, int ILO_NEXT, bool COND, int NLD>
+    __device__ __forceinline__ void grad_step(const double* __restrict__ st, const double* __restrict__ st1,
+                                              double* __restrict__ nst, int64_t ka, int64_t kb, bool live) {
+        constexpr int NP = G_NA + G_NB;
+        constexpr int P1 = (NP + 2) / 3, P2 = 2 * P1 < NP ? 2 * P1 : NP;
+        static_assert(NLD == NP, "every wave retires the loads of one step per step");
+        read_frag_lo<1, ILO>(st, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_row_lo<0, 0, ILO, COND>(live);
+        glds_issue_range<RUN>(ka, kb, nst, 0, P1);
+        mma_row_lo<0, 1, ILO, COND>(live);
+        glds_issue_range<RUN>(ka, kb, nst, P1, P2);
+        mma_row_lo<0, 2, ILO, COND>(live);
+        glds_issue_range<RUN>(ka, kb, nst, P2, NP);
+        mma_row_lo<0, 3, ILO, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
+        read_frag_lo<0, ILO>(st, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_frag_lo<1, ILO, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
+        read_frag_lo<1, ILO>(st, 3);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_frag_lo<0, ILO, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
+        __builtin_amdgcn_s_barrier();
+        read_frag_lo<0, ILO_NEXT>(st1, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_frag_lo<1, ILO, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
     }
 
     // ---- "dual" diagonal tile (Gram matrix only) ---------------------------------------------

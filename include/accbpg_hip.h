@@ -525,6 +525,11 @@ int accbpg_test_gemm(const double* A_dev, int64_t lda, const double* B_dev, int6
  * others drop global loads / LDS staging / the barrier / fragment reads and produce wrong data
  * into scratch).  Average milliseconds per launch over `iters` launches. */
 int accbpg_debug_gram_variant(accbpg_dopt* h, const double* x_dev, int variant, int iters, double* ms_host);
+/* The same for the direct-to-LDS gradient kernel, on the inverse factor the handle holds from its last gradient
+ * evaluation: variant 0 = the product kernel, 3 = its schedule before the k loop was split into phases, 10..13 = that
+ * schedule with rectangular k-steps only / diagonal k-steps only / MFMAs only / no drain and restart between row
+ * blocks (wrong data).  g_dev (n doubles) receives what the launches write. */
+int accbpg_debug_grad_variant(accbpg_dopt* h, double* g_dev, int variant, int iters, double* ms_host);
 /* For a handle whose evaluations run BESIDE another stream's MFMA-bound launches (the value evaluation the solvers
  * start next to a gradient evaluation, accbpg/algorithms.py:135 beside :148): factor with one launch per 64-wide
  * block column -- a few workgroups at a time -- instead of the one-launch kernel, whose waiting workgroups would

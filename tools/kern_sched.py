@@ -5,7 +5,8 @@ last group; timing code 18, no longer in the table), 2 = dealt out with the read
 the first fragment row, one load per M0 write through the builtin; 3 / 4 = variant 2 with the loads of the k-loop two
 (production) / four to an M0 write.  The handle's switch, used for the bit-identity check and the gradient kernel's
 timings: Gram 0 = production, 1 = builtin loads, 2 = four to an M0 write, 3 = block schedule; gradient kernel 0 =
-production (block schedule, four loads to an M0 write), 1 = builtin loads, 2 = dealt out.
+production (rectangular and diagonal phase per row block, one pipeline per workgroup), 1 = builtin loads, 2 = dealt out,
+3 = the production schedule before the two phases (runtime triangular skip, pipeline restarted per row block).
 Checks first that value and gradient are bit-identical under every variant."""
 import argparse
 import ctypes as C
@@ -40,7 +41,7 @@ def main():
     f.overlap_values(False)
     base = f.func_grad(x, 2)
     same = {}
-    for v in (1, 2, 0):
+    for v in (1, 2, 3, 0):
         lib.accbpg_debug_chol_variant(f._h, v << 30)
         r = f.func_grad(x, 2)
         same[v] = bool(r[0] == base[0] and torch.equal(r[1], base[1]))
@@ -52,15 +53,15 @@ def main():
         for v, code in codes.items():
             _lib.check(lib.accbpg_debug_gram_variant(f._h, _ptr(x), code, args.iters, C.byref(ms)), "gram variant")
             out["gram_ms"].setdefault(v, []).append(ms.value)
-        for v in (0, 1, 2):
-            lib.accbpg_debug_chol_variant(f._h, v << 30)             # gradient kernel: 0 production, 1 builtin loads, 2 dealt out
+        for v in (0, 1, 2, 3):
+            lib.accbpg_debug_chol_variant(f._h, v << 30)             # gradient kernel: 0 production, 1 builtin loads, 2 dealt out, 3 before the phases
             f.profile(True)
             for _ in range(args.iters):
                 f.func_grad(x, 1)
             tot, cnt = f.profile_read()["grad"]
             f.profile(False)
             out["grad_ms"].setdefault(v, []).append(tot / cnt)
-        print(rnd, {v: round(out["gram_ms"][v][-1], 4) for v in codes}, {v: round(out["grad_ms"][v][-1], 4) for v in (0, 1, 2)},
+        print(rnd, {v: round(out["gram_ms"][v][-1], 4) for v in codes}, {v: round(out["grad_ms"][v][-1], 4) for v in (0, 1, 2, 3)},
               flush=True)
     lib.accbpg_debug_chol_variant(f._h, 0)
     for key in ("gram_ms", "grad_ms"):

@@ -45,6 +45,9 @@ _SIGS = {
     "accbpg_dopt_func_grad_begin": (C.c_int, [_P, _P, C.c_int, _P]),
     "accbpg_dopt_func_grad_end": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "accbpg_dopt_eval_gap_ms": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
+    "accbpg_dopt_value_reuse": (C.c_int, [_P, C.c_int]),
+    "accbpg_dopt_value_reuse_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "accbpg_dopt_value_peer": (C.c_int, [_P, _P]),
     "accbpg_dopt_gram": (C.c_int, [_P, _P, _P]),
     "accbpg_dopt_factor": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
     "accbpg_dopt_grad": (C.c_int, [_P, _P]),

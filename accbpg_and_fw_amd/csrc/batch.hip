@@ -40,6 +40,7 @@ static int batch_init(accbpg_dopt_batch* b, const double* const* V_host, int K, 
         h->force_big = true;                                    // the tuned 256 x 128 tile also at m = 512
         h->gram_grid_cap = std::max(1, prop.multiProcessorCount / b->chunk);   // the instances of a launch share the chip
         h->dscal_ext = b->dscal_all + 24 * (size_t)i;
+        h->val_reuse = false;                                   // batches keep no value records (every evaluation runs)
         ACC_TRY(dopt_init(h));
     }
     accbpg_dopt* h0 = b->inst[0];

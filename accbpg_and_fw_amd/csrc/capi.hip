@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <string.h>
 #include <stdlib.h>
+#include <algorithm>
 
 #include "internal.h"
 #include "reduce.hpp"
@@ -98,6 +99,12 @@ extern "C" int accbpg_dopt_create(const double* V_dev, int64_t m, int64_t n, int
 
 extern "C" int accbpg_dopt_destroy(accbpg_dopt* h) {
     if (!h) return ACCBPG_OK;
+    for (accbpg_dopt* l : h->val_linked) l->val_peer = nullptr;     // nobody keeps looking at this handle's record
+    if (h->val_peer) {
+        auto& lk = h->val_peer->val_linked;
+        lk.erase(std::remove(lk.begin(), lk.end(), h), lk.end());
+    }
+    hipFree(h->val_copy);
     hipFree(h->Vblk);
     hipFree(h->Lbuf); hipFree(h->Wbuf); hipFree(h->Tbuf); hipFree(h->slabs); hipFree(h->tiles); hipFree(h->wg_ranges); hipFree(h->gram_cstart); hipFree(h->gram_contrib);
     if (!h->dscal_ext) hipFree(h->dscal);
@@ -160,26 +167,148 @@ extern "C" int accbpg_dopt_grad(accbpg_dopt* h, double* g_dev) {
     return ACCBPG_OK;
 }
 
-/* Enqueue a whole func_grad on the handle's stream without waiting: Gram, Cholesky, (gradient),
- * and the copy of the scalars / flags to the pinned mirror.  accbpg_dopt_func_grad_end waits for it.
- * Two handles on the same V with different streams let independent evaluations overlap (the
- * latency-bound factorisation of one under the MFMA-bound products of the other). */
-extern "C" int accbpg_dopt_func_grad_begin(accbpg_dopt* h, const double* x_dev, int flag, double* g_dev) {
-    if (!h || !x_dev || flag < 0 || flag > 2) return ACCBPG_ERR_ARG;
-    if (flag != 0 && !g_dev) return ACCBPG_ERR_ARG;
+namespace accbpg {
+// word[0] <- stamp when the n 64-bit patterns of a and b differ anywhere (compared as integers: -0.0 is not +0.0, a NaN
+// equals itself); otherwise the word keeps whatever older stamp it held.  Scalar 8-byte loads: any 8-byte aligned a, b.
+__global__ __launch_bounds__(256) void value_compare_kernel(const unsigned long long* __restrict__ a,
+                                                           const unsigned long long* __restrict__ b, int64_t n, int stamp,
+                                                           int* __restrict__ word) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    bool differ = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) differ |= a[i] != b[i];
+    if (differ) *word = stamp;
+}
+
+static void value_forget(accbpg_dopt* h) {
+    h->val_valid = false;
+    h->val_pending = false;     // (an evaluation in flight completes no record either)
+}
+
+static int value_alloc(accbpg_dopt* h) {
+    if (h->val_copy) return ACCBPG_OK;
+    double* p = nullptr;
+    ACC_HIP(hipMalloc(&p, sizeof(double) * ((size_t)h->n + 2)));
+    if (hipMemsetAsync(p + h->n, 0, sizeof(double) * 2, h->stream) != hipSuccess) {
+        hipFree(p);
+        set_last_error("accbpg_dopt_func_grad: could not clear the compare word");
+        return ACCBPG_ERR_HIP;
+    }
+    h->val_copy = p;
+    return ACCBPG_OK;
+}
+
+// *same <- x (as h's stream sees it) equals the copy in rec's record bit for bit: one launch, one 4-byte readback, one
+// synchronisation of h's stream.  rec is h or its peer; its record is valid, so nothing is writing the copy.
+static int value_matches(accbpg_dopt* h, const accbpg_dopt* rec, const double* x, bool* same) {
+    ACC_TRY(value_alloc(h));
+    int* word = reinterpret_cast<int*>(h->val_copy + h->n);
+    int* pin = reinterpret_cast<int*>(h->hpin + 28);            // (the status mirror ends at hpin[20])
+    const int stamp = h->val_gen = h->val_gen % 1000000000 + 1;
+    const int64_t nb = std::min<int64_t>((h->n + 255) / 256, 1024);
+    value_compare_kernel<<<(unsigned)nb, 256, 0, h->stream>>>(reinterpret_cast<const unsigned long long*>(x),
+                                                             reinterpret_cast<const unsigned long long*>(rec->val_copy),
+                                                             h->n, stamp, word);
+    ACC_HIP(hipGetLastError());
+    ACC_HIP(hipMemcpyAsync(pin, word, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    ACC_HIP(hipStreamSynchronize(h->stream));
+    ++h->val_compares;
+    *same = *pin != stamp;
+    return ACCBPG_OK;
+}
+
+// accbpg_dopt_func_grad_begin; lookup = false for the redo of an abandoned evaluation, which always evaluates
+static int func_grad_begin(accbpg_dopt* h, const double* x_dev, int flag, double* g_dev, bool lookup) {
     h->last_x = x_dev; h->last_flag = flag; h->last_g = g_dev;
+    h->val_pending = false;
+    h->val_hit = false;
+    const bool record = flag == 0 && h->val_reuse;
+    if (record) {
+        accbpg_dopt* const recs[2] = {h, h->val_peer};
+        for (int r = 0; lookup && r < 2; ++r) {
+            const accbpg_dopt* rec = recs[r];
+            if (!rec || !rec->val_valid || rec->val_x != x_dev) continue;      // host only: no launch, no wait
+            bool same = false;
+            ACC_TRY(value_matches(h, rec, x_dev, &same));
+            if (!same) continue;
+            h->val_hit = true;                                  // answered: _end returns the recorded value
+            h->val_answer = rec->val_f;
+            ++h->val_answered;
+            ACC_HIP(hipEventRecord(h->ev_done, h->stream));
+            return ACCBPG_OK;
+        }
+        h->val_valid = false;                                   // until _end has seen this evaluation succeed
+    }
     // (with the one-launch Cholesky the Gram matrix gets a buffer of its own and stays intact for a redo)
     double* gram = chol_tiles_usable(h) ? h->Gbuf : h->Lbuf;
     ACC_TRY(launch_gram(h, x_dev, gram));
     // resets the scalars and flags first, and checks x >= 0 in the same launch (functions.py:45)
-    ACC_TRY(launch_cholesky(h, h->Lbuf, flag != 0 ? h->Wbuf : nullptr, x_dev, gram));
+    // ... and for a value record keeps x as it was evaluated, for the compare of a later lookup (no launch of its own:
+    // BPG at (80,200) ran 4.6 % slower with a copy kernel per value, profiles/history/value_reuse_rate_copy_kernel.json)
+    if (record) ACC_TRY(value_alloc(h));
+    ACC_TRY(launch_cholesky(h, h->Lbuf, flag != 0 ? h->Wbuf : nullptr, x_dev, gram, record ? h->val_copy : nullptr));
     if (flag != 0) {
         ACC_TRY(launch_trtri(h));
         ACC_TRY(launch_colnorm(h, h->Wbuf, g_dev, -1.0));
     }
+    h->val_pending = record;
     ACC_HIP(hipMemcpyAsync(h->hpin, h->dscal, sizeof(double) * STATUS_DOUBLES, hipMemcpyDeviceToHost, h->stream));   // scalars + flags
     ACC_HIP(hipEventRecord(h->ev_done, h->stream));            // when this evaluation's results are on the host
     return ACCBPG_OK;
+}
+
+static int func_grad_end(accbpg_dopt* h, double* f_host) {
+    if (h->val_hit) {           // answered in _begin: nothing of this evaluation is on the stream or in the status mirror
+        h->val_hit = false;
+        // (the stream was drained by the compare, so ev_done, recorded right behind it, is complete or about to be:
+        // accbpg_dopt_eval_gap_ms needs it complete)
+        ACC_HIP(hipEventSynchronize(h->ev_done));
+        if (f_host) *f_host = h->val_answer;
+        return ACCBPG_OK;
+    }
+    ACC_HIP(hipStreamSynchronize(h->stream));
+    const int* fl = reinterpret_cast<const int*>(h->hpin + 16);
+    if (fl[FLAG_ABORT] && !h->chol_tiles_off) {
+        // the one-launch factorisation gave up a wait (its workgroups were not all resident in time, e.g. another
+        // process shares the GPU): redo this evaluation with one launch per block column, and stay with that
+        h->chol_tiles_off = true;
+        note_tiles_fallback("accbpg_dopt_func_grad");
+        ACC_TRY(func_grad_begin(h, h->last_x, h->last_flag, h->last_g, false));
+        return func_grad_end(h, f_host);
+    }
+    if (fl[FLAG_NEG_X]) {
+        set_last_error("DOptimalObj: x needs to be nonnegative");
+        return ACCBPG_ERR_ASSERT;
+    }
+    if (fl[FLAG_NOT_PD]) {
+        set_last_error("HXHT is singular or not positive definite");
+        return ACCBPG_ERR_NOT_PD;
+    }
+    if (h->val_pending) {                                       // the flag-0 evaluation succeeded: its record is complete
+        h->val_pending = false;
+        h->val_x = h->last_x;
+        h->val_f = -h->hpin[0];
+        h->val_valid = true;
+    }
+    if (f_host) *f_host = -h->hpin[0];
+    return ACCBPG_OK;
+}
+}  // namespace accbpg
+
+/* Enqueue a whole func_grad on the handle's stream without waiting: Gram, Cholesky, (gradient),
+ * and the copy of the scalars / flags to the pinned mirror.  accbpg_dopt_func_grad_end waits for it.
+ * Two handles on the same V with different streams let independent evaluations overlap (the
+ * latency-bound factorisation of one under the MFMA-bound products of the other).
+ * A value-only evaluation (flag 0) at the device address and 64-bit content of the last one that succeeded on this
+ * handle or its peer is answered with that value instead (accbpg_dopt_value_reuse). */
+extern "C" int accbpg_dopt_func_grad_begin(accbpg_dopt* h, const double* x_dev, int flag, double* g_dev) {
+    if (!h || !x_dev || flag < 0 || flag > 2) return ACCBPG_ERR_ARG;
+    if (flag != 0 && !g_dev) return ACCBPG_ERR_ARG;
+    const int rc = func_grad_begin(h, x_dev, flag, g_dev, true);
+    if (rc != ACCBPG_OK) {
+        value_forget(h);
+        h->val_hit = false;
+    }
+    return rc;
 }
 
 /* Milliseconds from the completion of `first`'s last begin/end evaluation to the completion of `second`'s
@@ -205,31 +334,43 @@ extern "C" int accbpg_dopt_eval_gap_ms(accbpg_dopt* first, accbpg_dopt* second, 
 
 extern "C" int accbpg_dopt_func_grad_end(accbpg_dopt* h, double* f_host) {
     if (!h) return ACCBPG_ERR_ARG;
-    ACC_HIP(hipStreamSynchronize(h->stream));
-    const int* fl = reinterpret_cast<const int*>(h->hpin + 16);
-    if (fl[FLAG_ABORT] && !h->chol_tiles_off) {
-        // the one-launch factorisation gave up a wait (its workgroups were not all resident in time, e.g. another
-        // process shares the GPU): redo this evaluation with one launch per block column, and stay with that
-        h->chol_tiles_off = true;
-        note_tiles_fallback("accbpg_dopt_func_grad");
-        ACC_TRY(accbpg_dopt_func_grad_begin(h, h->last_x, h->last_flag, h->last_g));
-        return accbpg_dopt_func_grad_end(h, f_host);
-    }
-    if (fl[FLAG_NEG_X]) {
-        set_last_error("DOptimalObj: x needs to be nonnegative");
-        return ACCBPG_ERR_ASSERT;
-    }
-    if (fl[FLAG_NOT_PD]) {
-        set_last_error("HXHT is singular or not positive definite");
-        return ACCBPG_ERR_NOT_PD;
-    }
-    if (f_host) *f_host = -h->hpin[0];
-    return ACCBPG_OK;
+    const int rc = func_grad_end(h, f_host);
+    if (rc != ACCBPG_OK) value_forget(h);
+    return rc;
 }
 
 extern "C" int accbpg_dopt_func_grad(accbpg_dopt* h, const double* x_dev, int flag, double* f_host, double* g_dev) {
     ACC_TRY(accbpg_dopt_func_grad_begin(h, x_dev, flag, g_dev));
     return accbpg_dopt_func_grad_end(h, f_host);
+}
+
+extern "C" int accbpg_dopt_value_reuse(accbpg_dopt* h, int on) {
+    if (!h) return ACCBPG_ERR_ARG;
+    h->val_reuse = on != 0;
+    value_forget(h);
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_value_reuse_stats(accbpg_dopt* h, int64_t* compares_host, int64_t* answered_host) {
+    if (!h) return ACCBPG_ERR_ARG;
+    if (compares_host) *compares_host = h->val_compares;
+    if (answered_host) *answered_host = h->val_answered;
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_value_peer(accbpg_dopt* h, accbpg_dopt* peer) {
+    if (!h || peer == h) return ACCBPG_ERR_ARG;
+    if (peer && (peer->V != h->V || peer->m != h->m || peer->n != h->n || peer->ldv != h->ldv)) {
+        set_last_error("accbpg_dopt_value_peer: the two handles are not over the same matrix");
+        return ACCBPG_ERR_ARG;
+    }
+    if (h->val_peer) {
+        auto& lk = h->val_peer->val_linked;
+        lk.erase(std::remove(lk.begin(), lk.end(), h), lk.end());
+    }
+    h->val_peer = peer;
+    if (peer) peer->val_linked.push_back(h);
+    return ACCBPG_OK;
 }
 
 namespace accbpg {
@@ -399,6 +540,7 @@ extern "C" int accbpg_dopt_factor_in_small_launches(accbpg_dopt* h, int on) {
     // 2 = where it pays: only a factorisation with at least a workgroup per compute unit crowds the other stream out
     // (m > 1408 on 256 CUs); below that the single launch is the faster neighbour too ((512,8192): 1507 against 1464 it/s)
     const int64_t T = (h->m + NB - 1) / NB;
+    value_forget(h);                         // the next value is computed the way that was just asked for
     h->chol_tiles_off = on == 1 || (on == 2 && T * (T + 1) / 2 >= h->num_cu);
     return ACCBPG_OK;
 }
@@ -412,6 +554,7 @@ extern "C" int accbpg_debug_plan_flags(int flags) {
 
 extern "C" int accbpg_debug_chol_variant(accbpg_dopt* h, int bits) {
     if (!h) return ACCBPG_ERR_ARG;
+    value_forget(h);
     h->chol_dbg = bits & 63;
     h->chol_tiles_off = (bits & 64) != 0;       // bit 6: launch-per-block-column Cholesky instead of the one-launch kernel
     if (bits & 2048) h->chol_tiles_off = true;   // a forced scheme of the launch-per-column kernels
@@ -453,10 +596,12 @@ extern "C" int accbpg_debug_chol_trace(accbpg_dopt* h, const double* gram_dev, i
 
 extern "C" int accbpg_debug_gram_variant(accbpg_dopt* h, const double* x_dev, int variant, int iters, double* ms_host) {
     if (!h || !x_dev || !ms_host || iters <= 0) return ACCBPG_ERR_ARG;
+    value_forget(h);
     return debug_gram_variant(h, x_dev, variant, iters, ms_host);
 }
 
 extern "C" int accbpg_debug_grad_variant(accbpg_dopt* h, double* g_dev, int variant, int iters, double* ms_host) {
     if (!h || !g_dev || !ms_host || iters <= 0) return ACCBPG_ERR_ARG;
+    value_forget(h);
     return debug_grad_variant(h, g_dev, variant, iters, ms_host);
 }

@@ -2184,7 +2184,9 @@ __global__ __launch_bounds__(64) void trtri_diag_kernel(const double* __restrict
 
 // any entry of x that is not >= 0 (NaN counts)?  One workgroup, eight independent loads in flight per thread: the
 // check sits between the Gram kernel and the factorisation on every evaluation, so its latency is on the path.
-__device__ __forceinline__ bool xcheck_bad(const double* __restrict__ x, int64_t n) {
+// With COPY the entries also go to `keep` as they pass through the registers (the value record of capi.hip).
+template <bool COPY = false>
+__device__ __forceinline__ bool xcheck_bad(const double* __restrict__ x, int64_t n, double* __restrict__ keep = nullptr) {
     bool bad = false;
     const int64_t step = (int64_t)blockDim.x * 8;
     int64_t i = threadIdx.x;
@@ -2193,15 +2195,24 @@ __device__ __forceinline__ bool xcheck_bad(const double* __restrict__ x, int64_t
 #pragma unroll
         for (int u = 0; u < 8; ++u) v[u] = x[i + u * (int64_t)blockDim.x];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) bad |= !(v[u] >= 0.0);
+        for (int u = 0; u < 8; ++u) {
+            bad |= !(v[u] >= 0.0);
+            if (COPY) keep[i + u * (int64_t)blockDim.x] = v[u];
+        }
     }
-    for (; i < n; i += blockDim.x) bad |= !(x[i] >= 0.0);
+    for (; i < n; i += blockDim.x) {
+        const double v = x[i];
+        bad |= !(v >= 0.0);
+        if (COPY) keep[i] = v;
+    }
     return __syncthreads_or(bad ? 1 : 0) != 0;
 }
 
-// resets the scalars and the status flags; with x != NULL also the x >= 0 check of functions.py:45
+// resets the scalars and the status flags; with x != NULL also the x >= 0 check of functions.py:45, and with xkeep
+// != NULL a copy of x on the way
 __global__ __launch_bounds__(1024) void zero_scalars_kernel(double* dscal, int* dflag, const double* __restrict__ x,
-                                                          int64_t n, int* __restrict__ ready, int nready) {
+                                                          int64_t n, int* __restrict__ ready, int nready,
+                                                          double* __restrict__ xkeep) {
 #if defined(ACCBPG_PLAIN_LOGDET) && ACCBPG_PLAIN_LOGDET
     if (threadIdx.x < 8) dscal[threadIdx.x] = 0.0;
 #else
@@ -2210,7 +2221,8 @@ __global__ __launch_bounds__(1024) void zero_scalars_kernel(double* dscal, int* 
     if (threadIdx.x < 8) dflag[threadIdx.x] = 0;
     for (int i = threadIdx.x; i < nready; i += blockDim.x) ready[i] = 0;     // hand-off flags of the one-launch Cholesky
     if (x == nullptr) return;
-    if (xcheck_bad(x, n) && threadIdx.x == 0) dflag[FLAG_NEG_X] = 1;
+    const bool bad = xkeep ? xcheck_bad<true>(x, n, xkeep) : xcheck_bad<false>(x, n);
+    if (bad && threadIdx.x == 0) dflag[FLAG_NEG_X] = 1;
 }
 
 // the same reset for the active instances of a batch (one workgroup per instance)
@@ -2912,18 +2924,19 @@ static int launch_chol_tiles(accbpg_dopt* h, const double* src, double* A, doubl
     return ACCBPG_OK;
 }
 
-int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xcheck, const double* src) {
+int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xcheck, const double* src, double* xkeep) {
     const int64_t m = h->m;
     const int T = (int)((m + NB - 1) / NB);
     if (src == nullptr) src = A;
     const bool tiles = chol_tiles_usable(h);
     prof_begin(h, PROF_CHOL);
-    // 512 threads, not 1024: two waves of 32 registers per SIMD fit beside a wave of the Gram kernel (392 of the 512
-    // registers of a SIMD lane), four do not -- and this launch often meets the OTHER stream's Gram launch, which holds
+    // 512 threads, not 1024: two waves of 40 registers (26 before the copy of x joined the check) per SIMD fit beside a
+    // wave of the Gram kernel (392 of the 512 registers of a SIMD lane), four do not -- and this launch often meets the OTHER stream's Gram launch, which holds
     // every compute unit for 2 ms (its rocprofv3 average with 1024 threads in the steady state of ABPG_gain: 328 us,
     // nearly all of it waiting for a compute unit)
     zero_scalars_kernel<<<1, (xcheck || tiles) ? 512 : 64, 0, h->stream>>>(h->dscal, h->dflag, xcheck, h->n,
-                                                                         tiles ? h->chol_ready : nullptr, tiles ? T * T + 5 * T : 0);
+                                                                         tiles ? h->chol_ready : nullptr, tiles ? T * T + 5 * T : 0,
+                                                                         xcheck ? xkeep : nullptr);
     if (tiles) {
         ACC_TRY(launch_chol_tiles(h, src, A, Winv));
         h->diag_inv_ready = (Winv != nullptr);

@@ -243,6 +243,21 @@ struct accbpg_dopt {
     double* last_g = nullptr;
     int last_flag = 0;
     hipEvent_t ev_done = nullptr;   // recorded behind the result copy of every begin/end evaluation
+    // record of the last value-only (flag 0) begin/end evaluation that completed without error; a later flag-0 begin
+    // at the same device address whose 64-bit content equals the copy is answered with val_f (accbpg_dopt_value_reuse)
+    bool val_reuse = true;          // look up and keep the record
+    bool val_valid = false;         // the record is complete (host side; cleared while a flag-0 evaluation is in flight)
+    bool val_pending = false;       // a flag-0 evaluation is in flight whose _end completes the record
+    bool val_hit = false;           // the evaluation in flight was answered: _end returns val_answer
+    const double* val_x = nullptr;  // the caller's device address of x
+    double* val_copy = nullptr;     // n doubles: x as it was evaluated; behind them the compare kernel's result word
+                                    // (allocated by the first flag-0 evaluation or lookup)
+    double val_f = 0.0;             // f of the record
+    double val_answer = 0.0;        // f of the answered evaluation in flight (from this record or the peer's)
+    int val_gen = 0;                // stamp the next compare launch writes when it finds a difference
+    int64_t val_compares = 0, val_answered = 0;
+    accbpg_dopt* val_peer = nullptr;            // lookups consult this handle's record after the own (read-only)
+    std::vector<accbpg_dopt*> val_linked;       // the handles whose val_peer is this one (unlinked by destroy)
     bool prof_on = false;
     accbpg::ProfSlot prof[accbpg::PROF_COUNT];
 };
@@ -299,7 +314,8 @@ int dopt_init(accbpg_dopt* h);
 int launch_gram(accbpg_dopt* h, const double* x, double* gram);
 int launch_cholesky(accbpg_dopt* h, double* A /* m*m, factor goes here */, double* Winv = nullptr /* diagonal-block inverses */,
                     const double* xcheck = nullptr /* x >= 0 check folded into the reset launch */,
-                    const double* src = nullptr /* matrix to factor when it is not A itself */);
+                    const double* src = nullptr /* matrix to factor when it is not A itself */,
+                    double* xkeep = nullptr /* n doubles: receives a copy of xcheck in the same pass */);
 bool chol_tiles_usable(const accbpg_dopt* h);
 int launch_trtri(accbpg_dopt* h);
 int launch_colnorm(accbpg_dopt* h, const double* W, double* out, double sign);

@@ -141,6 +141,7 @@ class DOptimalObj(RSmoothFunction):
         self.gram_launches = 0
         self.gram_combos = 0
         self.value_hits = 0
+        self._reuse = True
 
     def __del__(self):
         for name in ("_h", "_h2"):
@@ -211,6 +212,28 @@ class DOptimalObj(RSmoothFunction):
         self._memo = None
         return self
 
+    # ---- f at a device vector whose value the library computed a moment ago (on by default) ----
+    def reuse_values(self, enable=True):
+        """ABPG_gain evaluates f at the accepted line-search point twice (accbpg/algorithms.py:387, then F[k+1] = f(x)
+        at :347).  The library keeps the last value-only evaluation of each handle -- device address, a copy of x, f --
+        and answers a value evaluation at the same address with the same 64-bit content from it: no Gram product, no
+        factorisation, the same number to the bit (accbpg_dopt_value_reuse in include/accbpg_hip.h).  On by default;
+        ``reuse_values(False)`` makes every evaluation run.  ``calls["value"]`` counts the values the solver asked
+        for either way, ``values_reused`` those that were answered."""
+        self._reuse = bool(enable)
+        for h in self._handles():
+            self._lib.accbpg_dopt_value_reuse(h, 1 if enable else 0)
+        return self
+
+    @property
+    def values_reused(self):
+        total = 0
+        for h in self._handles():
+            cmp_, ans = C.c_int64(0), C.c_int64(0)
+            self._lib.accbpg_dopt_value_reuse_stats(h, C.byref(cmp_), C.byref(ans))
+            total += ans.value
+        return total
+
     def _memo_get(self, x):
         memo = getattr(self, "_memo", None)
         if getattr(self, "_memo_on", False) and memo is not None and memo[0] is x and memo[1] == x._version:
@@ -235,6 +258,11 @@ class DOptimalObj(RSmoothFunction):
             # its evaluations run beside the gradient evaluation of the solver's own stream: a launch per block
             # column leaves that stream its compute units (bit-identical results)
             self._lib.accbpg_dopt_factor_in_small_launches(h2, 2)
+            # f(x) of the accepting test runs on one handle, F[k+1] = f(x) on the other: each may answer from the
+            # other's record (reuse_values)
+            self._lib.accbpg_dopt_value_reuse(h2, 1 if self._reuse else 0)
+            _lib.check(self._lib.accbpg_dopt_value_peer(h2, self._h), "accbpg_dopt_value_peer")
+            _lib.check(self._lib.accbpg_dopt_value_peer(self._h, h2), "accbpg_dopt_value_peer")
             if self._prof:
                 self._lib.accbpg_dopt_profile_enable(self._h2, 1)
         return self._h2

@@ -73,6 +73,32 @@ int accbpg_dopt_func_grad_end(accbpg_dopt* h, double* f_host);
  * 347-349) at the moment f(x) was known although it ran beside the gradient evaluation. */
 int accbpg_dopt_eval_gap_ms(accbpg_dopt* first, accbpg_dopt* second, double* ms_host);
 
+/* Repeated value evaluations.  ABPG_gain evaluates f at the accepted line-search point twice (accbpg/algorithms.py:387,
+ * then F[k+1] = f(x) at :347) with nothing in between; the kernels are deterministic, so the second result is the first,
+ * bit for bit.  Every handle therefore keeps a record of its last VALUE-ONLY evaluation (flag 0 through
+ * accbpg_dopt_func_grad_begin/_end or accbpg_dopt_func_grad) that returned ACCBPG_OK: the device address of x, a device
+ * copy of x, and f.  A later flag-0 `begin` is ANSWERED with the recorded f -- no Gram product, no factorisation -- when
+ *   - x_dev is the recorded device address (checked on the host: a different address costs nothing),
+ *   - the n doubles there equal the copy as 64-bit patterns (one small launch, one 4-byte readback, one
+ *     synchronisation of the handle's stream; -0.0 differs from +0.0, a NaN pattern equals itself),
+ *   - the record is that of the same handle or of its peer (accbpg_dopt_value_peer), and
+ *   - V is unchanged, as accbpg_dopt_create already requires.
+ * `end` of an answered evaluation returns the value without waiting for the stream; accbpg_dopt_eval_gap_ms sees it as
+ * completed when `begin` returned.  Gradient evaluations (flag 1, 2), the staged entry points (accbpg_dopt_gram,
+ * _factor, _eval_gram), the sharded objective and batches neither write nor consult records.  A record is dropped by any
+ * error return of begin/end, while a flag-0 evaluation of its handle is in flight, and by accbpg_dopt_value_reuse,
+ * accbpg_dopt_factor_in_small_launches and the accbpg_debug_*_variant switches; the redo of an abandoned one-launch
+ * factorisation always evaluates.
+ *   accbpg_dopt_value_reuse(h, on): on = 0 switches lookups and the record off for h, anything else on (the default).
+ *   accbpg_dopt_value_reuse_stats: compare launches made and evaluations answered on h since its creation.
+ *   accbpg_dopt_value_peer(h, peer): lookups on h consult peer's record after h's own (read-only: a handle writes its
+ *     own record only; peer's counts while none of ITS flag-0 evaluations is in flight).  Both handles must be over
+ *     the same V.  peer = NULL unlinks; destroying either handle unlinks too.  For the two handles of one objective
+ *     whose value evaluations alternate between two streams. */
+int accbpg_dopt_value_reuse(accbpg_dopt* h, int on);
+int accbpg_dopt_value_reuse_stats(accbpg_dopt* h, int64_t* compares_host, int64_t* answered_host);
+int accbpg_dopt_value_peer(accbpg_dopt* h, accbpg_dopt* peer);
+
 /* The same computation in three stages, for design-point sharding across GPUs
  * (SURVEY.md 8(e).2): each rank forms its local Gram contribution, the caller all-reduces
  * gram_dev (m*m doubles, lower triangle significant) over RCCL, every rank factors it and

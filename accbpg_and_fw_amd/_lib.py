@@ -92,6 +92,7 @@ _SIGS = {
     "accbpg_vec_argminmax": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), _P, _P]),
     "accbpg_dopt_vt_times": (C.c_int, [_P, _P, _P]),
     "accbpg_dopt_get_column": (C.c_int, [_P, C.c_int64, _P]),
+    "accbpg_dopt_kyinit": (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P]),
     "accbpg_fw_init": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
     "accbpg_fw_probe_step": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(FwProbe)]),
     "accbpg_fw_logdet_flush": (C.c_int, [_P, C.POINTER(C.c_double)]),

@@ -61,6 +61,38 @@ def D_opt_KYinit(V):
     return x0
 
 
+def D_opt_KYinit_device(V, return_picked=False):
+    """D_opt_KYinit with all m steps decided on the device (accbpg_dopt_kyinit): the Gram-Schmidt recurrences, the pass
+    over V, the arg-extrema and the column reads are enqueued in one call and the host waits once.  ``V`` is the design
+    matrix or a DOptimalObj over it.  The directions are drawn here, m calls of np.random.rand(m) in step order
+    (accbpg/applications.py:74), so the legacy generator ends in the state the reference leaves it in; for n <= 2m the
+    uniform point is returned without touching it (:67).  x0 is formed on the host as in :91-94.
+    ``return_picked=True`` returns (x0, picked) with picked[2i] = kmax, picked[2i+1] = kmin of step i.
+
+    The result equals D_opt_KYinit's for the same RNG state whenever no arg-max or arg-min decision lies within rounding
+    of a tie: the device sums each Gram-Schmidt dot product in its own fixed order, not in np.dot's.  Such ties are
+    not exotic -- q is orthogonal to every earlier v = V[:,kmin] - V[:,kmax], so the two members of every earlier pair
+    have equal q^T V by construction, and when such a pair is the extreme any two summation orders may pick
+    differently (DESIGN.md)."""
+    obj = V if isinstance(V, DOptimalObj) else None
+    m, n = (obj.m, obj.n) if obj is not None else V.shape
+    if n <= 2 * m:
+        x0 = (1.0 / n) * np.ones(n)
+        return (x0, np.zeros(0, dtype=np.int64)) if return_picked else x0
+    if obj is None:
+        obj = DOptimalObj(V)
+
+    B = np.empty((m, m))
+    for i in range(m):
+        B[i] = np.random.rand(m)                                # :74
+    picked = obj.kyinit_picks(B)
+
+    x0 = np.zeros(n)
+    x0[picked] = np.ones(len(picked)) / len(picked)             # fancy assignment, not accumulation (:92)
+    x0 /= x0.sum()                                              # :93-94
+    return (x0, picked) if return_picked else x0
+
+
 def D_opt_design(m, n, randseed=-1):
     """Random Gaussian instance: returns (f, h, L, x0) with f = DOptimalObj(H),
     h = BurgEntropySimplex(), L = 1, x0 = centre of the simplex.  As in the reference

@@ -92,6 +92,65 @@ inline int ew_blocks(int64_t n) {
     return (int)(b > 2048 ? 2048 : b);
 }
 
+// First-index arg-minimum and arg-maximum over RED_THREADS-wide blocks (accbpg_vec_argminmax and the Kumar-Yildirim
+// start).  An arg-extremum is exact in any merge order, so these follow the tree's shape without being part of it.
+struct MinMaxRec {
+    double vmin, vmax;
+    int64_t imin, imax;
+};
+__device__ __forceinline__ MinMaxRec mm_merge(MinMaxRec a, MinMaxRec b) {
+    // np.argmin / np.argmax: a NaN is the extremum; among equals (or among NaNs) the first index wins
+    MinMaxRec r = a;
+    const bool an = a.vmin != a.vmin, bn = b.vmin != b.vmin;
+    if ((bn && !an) || (!an && b.vmin < a.vmin) || ((b.vmin == a.vmin || (an && bn)) && b.imin < a.imin)) {
+        r.vmin = b.vmin; r.imin = b.imin;
+    }
+    const bool ax = a.vmax != a.vmax, bx = b.vmax != b.vmax;
+    if ((bx && !ax) || (!ax && b.vmax > a.vmax) || ((b.vmax == a.vmax || (ax && bx)) && b.imax < a.imax)) {
+        r.vmax = b.vmax; r.imax = b.imax;
+    }
+    return r;
+}
+// the records of a block's RED_THREADS threads merged; every thread returns the block's record
+__device__ __forceinline__ MinMaxRec mm_block(MinMaxRec a, MinMaxRec* sh) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        MinMaxRec o;
+        o.vmin = __shfl_down(a.vmin, off); o.vmax = __shfl_down(a.vmax, off);
+        o.imin = __shfl_down((long long)a.imin, off); o.imax = __shfl_down((long long)a.imax, off);
+        a = mm_merge(a, o);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sh[w] = a;
+    __syncthreads();
+    MinMaxRec r = sh[0];
+    for (int i = 1; i < RED_THREADS / 64; ++i) r = mm_merge(r, sh[i]);
+    return r;
+}
+// stage 1: block b's record of the entries b*RED_THREADS + t + k*gridDim.x*RED_THREADS, into part[b]
+__device__ __forceinline__ void minmax_partial_body(const double* __restrict__ x, int64_t n,
+                                                    MinMaxRec* __restrict__ part) {
+    __shared__ MinMaxRec sh[RED_THREADS / 64];
+    const double inf = __builtin_inf();
+    MinMaxRec a{inf, -inf, INT64_MAX, INT64_MAX};
+    const int64_t stride = (int64_t)gridDim.x * RED_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * RED_THREADS + threadIdx.x; i < n; i += stride) {
+        const double v = x[i];
+        a = mm_merge(a, MinMaxRec{v, v, i, i});
+    }
+    a = mm_block(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+// stage 2 (one block): the nblk stage-1 records merged; every thread returns the result
+__device__ __forceinline__ MinMaxRec minmax_final_body(const MinMaxRec* __restrict__ part, int nblk) {
+    __shared__ MinMaxRec sh[RED_THREADS / 64];
+    const double inf = __builtin_inf();
+    MinMaxRec a{inf, -inf, INT64_MAX, INT64_MAX};
+    for (int b = threadIdx.x; b < nblk; b += RED_THREADS) a = mm_merge(a, part[b]);
+    return mm_block(a, sh);
+}
+
 // Host tail of a reduction on stream s.  Launches `final_kernel` over the nb block records at part into red_out --
 // unless it is null: a pass of a single block has written its result itself -- checks the launches, copies `count`
 // doubles from dout (the device scratch of vec_scratch) to pin + 8, waits, and returns pin + 8; null after a HIP error

@@ -500,60 +500,14 @@ __global__ __launch_bounds__(RB) void burg_reg_prox_kernel(int kind, const doubl
     if (bad_g) flags[FLAG_BAD_G] = 1;
 }
 
-struct MinMaxRec {
-    double vmin, vmax;
-    int64_t imin, imax;
-};
-__device__ __forceinline__ MinMaxRec mm_merge(MinMaxRec a, MinMaxRec b) {
-    // np.argmin / np.argmax: a NaN is the extremum; among equals (or among NaNs) the first index wins
-    MinMaxRec r = a;
-    const bool an = a.vmin != a.vmin, bn = b.vmin != b.vmin;
-    if ((bn && !an) || (!an && b.vmin < a.vmin) || ((b.vmin == a.vmin || (an && bn)) && b.imin < a.imin)) {
-        r.vmin = b.vmin; r.imin = b.imin;
-    }
-    const bool ax = a.vmax != a.vmax, bx = b.vmax != b.vmax;
-    if ((bx && !ax) || (!ax && b.vmax > a.vmax) || ((b.vmax == a.vmax || (ax && bx)) && b.imax < a.imax)) {
-        r.vmax = b.vmax; r.imax = b.imax;
-    }
-    return r;
-}
-__device__ __forceinline__ MinMaxRec mm_block(MinMaxRec a, MinMaxRec* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        MinMaxRec o;
-        o.vmin = __shfl_down(a.vmin, off); o.vmax = __shfl_down(a.vmax, off);
-        o.imin = __shfl_down((long long)a.imin, off); o.imax = __shfl_down((long long)a.imax, off);
-        a = mm_merge(a, o);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[w] = a;
-    __syncthreads();
-    MinMaxRec r = sh[0];
-    for (int i = 1; i < RB / 64; ++i) r = mm_merge(r, sh[i]);
-    return r;
-}
 // first-index argmin and argmax (np.argmin / np.argmax / np.where(g == g.min())[0][0])
 __global__ __launch_bounds__(RB) void minmax_partial_kernel(const double* __restrict__ x, int64_t n,
                                                            MinMaxRec* __restrict__ part) {
-    __shared__ MinMaxRec sh[RB / 64];
-    const double inf = __builtin_inf();
-    MinMaxRec a{inf, -inf, INT64_MAX, INT64_MAX};
-    const int64_t stride = (int64_t)gridDim.x * RB;
-    for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
-        const double v = x[i];
-        a = mm_merge(a, MinMaxRec{v, v, i, i});
-    }
-    a = mm_block(a, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = a;
+    minmax_partial_body(x, n, part);
 }
 __global__ __launch_bounds__(RB) void minmax_final_kernel(const MinMaxRec* __restrict__ part, int nblk,
                                                          MinMaxRec* __restrict__ out) {
-    __shared__ MinMaxRec sh[RB / 64];
-    const double inf = __builtin_inf();
-    MinMaxRec a{inf, -inf, INT64_MAX, INT64_MAX};
-    for (int b = threadIdx.x; b < nblk; b += RB) a = mm_merge(a, part[b]);
-    a = mm_block(a, sh);
+    const MinMaxRec a = minmax_final_body(part, nblk);
     if (threadIdx.x == 0) *out = a;
 }
 

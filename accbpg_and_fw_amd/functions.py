@@ -471,6 +471,23 @@ class DOptimalObj(RSmoothFunction):
         _lib.check(rc, "accbpg_dopt_get_column")
         return out.cpu().numpy()
 
+    def kyinit_picks(self, B, Q_out=None):
+        """The 2m indices of the Kumar-Yildirim start for the m directions B[i] (accbpg_dopt_kyinit): all m steps on the
+        device, one synchronisation.  ``Q_out``: optional m x m fp64 device tensor that receives the orthonormal
+        directions, row j = Q[:, j]."""
+        Bd, _ = to_dev(B)
+        assert Bd.shape == (self.m, self.m), "kyinit_picks: B must be m x m"
+        if Q_out is not None:
+            assert Q_out.is_cuda and Q_out.dtype == torch.float64 and Q_out.is_contiguous() \
+                and Q_out.shape == (self.m, self.m), "kyinit_picks: Q_out must be a contiguous m x m fp64 device tensor"
+        picked = np.empty(2 * self.m, dtype=np.int64)
+        with torch.cuda.device(self._V.device):
+            self._lib.accbpg_dopt_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_dopt_kyinit(self._h, _ptr(Bd), picked.ctypes.data_as(C.POINTER(C.c_int64)),
+                                              _ptr(Q_out))
+        _lib.check(rc, "accbpg_dopt_kyinit")
+        return picked
+
     # ---- kernel-time accounting used by bench.py ----
     def _handles(self):
         return [h for h in (self._h, getattr(self, "_h2", None)) if h]

@@ -259,6 +259,17 @@ int accbpg_dopt_vt_times(accbpg_dopt* h, const double* q_dev, double* u_dev);
 /* out <- V[:, j] (length m): the column reads of D_opt_KYinit (accbpg/applications.py:84). */
 int accbpg_dopt_get_column(accbpg_dopt* h, int64_t j, double* out_dev);
 
+/* Kumar-Yildirim start (accbpg/applications.py:59-95): all m steps on h's stream, one synchronisation at the end.
+ * B_dev: m*m doubles, row i = the random direction b of step i (drawn by the caller, applications.py:74).
+ * picked_host: 2m indices, [2i] = kmax, [2i+1] = kmin of step i (:80-83).
+ * Q_dev: optional m*m doubles, column j contiguous at Q_dev + j*m, receives the orthonormal directions (:89);
+ *        NULL = the call allocates and frees its own.
+ * Per step: the Gram-Schmidt coefficients from the un-deflated vector (:77, :87), each dot summed in one fixed order;
+ * the deflation in coefficient order (:78, :88); q^T V as accbpg_dopt_vt_times computes it (:79); first-index argmax /
+ * argmin as accbpg_vec_argminmax (:80-81), clamped to [0, n); v = V[:,kmin] - V[:,kmax] (:84); Q[:,i] = q / ||q|| (:89).
+ * Leaves the handle's solver state as it was (it uses the workspace of accbpg_dopt_vt_times only). */
+int accbpg_dopt_kyinit(accbpg_dopt* h, const double* B_dev, int64_t* picked_host, double* Q_dev);
+
 /* ---- Frank-Wolfe / Wolfe-Atwood state: replaces the bodies of D_opt_FW and --------------
  * D_opt_FW_away (accbpg/D_opt_alg.py:9-88, 91-185).  State (x, inverse H = (V X V^T)^-1,
  * w_i = v_i^T H v_i) lives in the handle. */

@@ -18,9 +18,10 @@ from .algorithms_fw import FW_alg_div_step, FW_alg_descent_step
 from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball, lmo_l2_ball_positive_orthant
 from .D_opt_alg import (D_opt_FW, D_opt_FW_away, D_opt_FW_batch, D_opt_FW_away_batch, D_opt_FW_device,
                         D_opt_FW_away_device, D_opt_FW_batch_device, D_opt_FW_away_batch_device)
-from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, D_opt_KYinit_device, Poisson_regrL1,
-                           Poisson_regrL2, KL_nonneg_regr, FrobeniusSymLossExL2Ball, FrobeniusSymLossExLInfBall,
-                           FrobeniusSymLossResMeasEx, Poisson_regr_simplex, Poisson_regr_simplex_acc)
+from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, D_opt_KYinit_device, D_opt_KYinit_batch,
+                           Poisson_regrL1, Poisson_regrL2, KL_nonneg_regr, FrobeniusSymLossExL2Ball,
+                           FrobeniusSymLossExLInfBall, FrobeniusSymLossResMeasEx, Poisson_regr_simplex,
+                           Poisson_regr_simplex_acc)
 from .utils import (load_libsvm_file, random_point_on_simplex, edge_point_on_simplex, get_random_float,
                     get_random_vector)
 from .batched import DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, solve_batch, solve_instances
@@ -36,5 +37,6 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "Poisson_regr_simplex", "Poisson_regr_simplex_acc", "lmo_l2_ball_positive_orthant",
            "random_point_on_simplex", "edge_point_on_simplex", "get_random_float", "get_random_vector",
            "D_opt_FW_batch", "D_opt_FW_away_batch", "D_opt_FW_device", "D_opt_FW_away_device",
-           "D_opt_FW_batch_device", "D_opt_FW_away_batch_device", "D_opt_KYinit_device"]
+           "D_opt_FW_batch_device", "D_opt_FW_away_batch_device", "D_opt_KYinit_device",
+           "D_opt_KYinit_batch"]
 __version__ = "0.1.0"

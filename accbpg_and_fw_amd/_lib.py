@@ -109,6 +109,7 @@ _SIGS = {
                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "accbpg_dopt_batch_fw_run": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int),
                                            C.POINTER(FwStep), C.POINTER(C.c_int)]),
+    "accbpg_dopt_batch_kyinit": (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P]),
     "accbpg_poisson_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(_P)]),
     "accbpg_poisson_destroy": (C.c_int, [_P]),
     "accbpg_poisson_set_stream": (C.c_int, [_P, _P]),

@@ -93,6 +93,44 @@ def D_opt_KYinit_device(V, return_picked=False):
     return (x0, picked) if return_picked else x0
 
 
+def D_opt_KYinit_batch(batch, return_picked=False):
+    """D_opt_KYinit_device for the K instances of a ``DOptimalBatch`` in lock-step (accbpg_dopt_batch_kyinit): every
+    launch of a step covers all instances, and the host waits once for all K starts.  ``batch`` is a DOptimalBatch or a
+    sequence of K matrices of one shape, from which one is built.  The directions are drawn here instance by instance,
+    m calls of np.random.rand(m) each in step order, so the legacy generator ends exactly where the loop
+    ``for i: D_opt_KYinit_device(batch.instance(i))`` leaves it; for n <= 2m the K x n uniform array is returned without
+    touching the generator, without building a batch and without a GPU.  Returns the K x n array of starts (what
+    D_opt_FW_batch and its variants take as x0), row i bit for bit ``D_opt_KYinit_device(batch.instance(i))``; with
+    ``return_picked=True`` also the K x 2m indices, [i, 2s] = kmax, [i, 2s+1] = kmin of instance i's step s."""
+    from .batched import DOptimalBatch
+    if isinstance(batch, DOptimalBatch):
+        K, m, n = batch.K, batch.m, batch.n
+    else:
+        K = len(batch)
+        assert K > 0, "D_opt_KYinit_batch: no instances"
+        m, n = batch[0].shape
+        assert all(tuple(V.shape) == (m, n) for V in batch), "D_opt_KYinit_batch: instances must have one shape"
+    if n <= 2 * m:
+        X0 = (1.0 / n) * np.ones((K, n))
+        return (X0, np.zeros((K, 0), dtype=np.int64)) if return_picked else X0
+    if not isinstance(batch, DOptimalBatch):
+        batch = DOptimalBatch(batch)
+
+    B = np.empty((K, m, m))
+    for i in range(K):
+        for s in range(m):
+            B[i, s] = np.random.rand(m)                         # :74
+    picked = batch.kyinit_picks(B)
+
+    X0 = np.empty((K, n))
+    for i in range(K):
+        x0 = np.zeros(n)
+        x0[picked[i]] = np.ones(2 * m) / (2 * m)                # fancy assignment, not accumulation (:92)
+        x0 /= x0.sum()                                          # :93-94
+        X0[i] = x0
+    return (X0, picked) if return_picked else X0
+
+
 def D_opt_design(m, n, randseed=-1):
     """Random Gaussian instance: returns (f, h, L, x0) with f = DOptimalObj(H),
     h = BurgEntropySimplex(), L = 1, x0 = centre of the simplex.  As in the reference

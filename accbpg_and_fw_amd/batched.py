@@ -221,6 +221,25 @@ class DOptimalBatch:
         _lib.check(rc, "accbpg_dopt_batch_axpby")
         return out
 
+    def kyinit_picks(self, B, Q_out=None):
+        """Row i: the 2m indices of instance i's Kumar-Yildirim start for its m directions B[i] (K x m x m;
+        accbpg_dopt_batch_kyinit): the K instances in lock-step, all m steps on the device, one synchronisation.
+        ``Q_out``: optional K x m x m fp64 device tensor that receives the orthonormal directions, Q_out[i, j] =
+        instance i's Q[:, j].  Bit for bit ``self.instance(i).kyinit_picks(B[i], Q_out[i])``."""
+        Bd, _ = to_dev(B)
+        assert Bd.shape == (self.K, self.m, self.m), "kyinit_picks: B must be K x m x m"
+        if Q_out is not None:
+            assert Q_out.is_cuda and Q_out.dtype == torch.float64 and Q_out.is_contiguous() \
+                and Q_out.shape == (self.K, self.m, self.m), \
+                "kyinit_picks: Q_out must be a contiguous K x m x m fp64 device tensor"
+        picked = np.empty((self.K, 2 * self.m), dtype=np.int64)
+        with torch.cuda.device(self.device):
+            self._lib.accbpg_dopt_batch_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_dopt_batch_kyinit(self._h, _ptr(Bd), picked.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    _ptr(Q_out))
+        _lib.check(rc, "accbpg_dopt_batch_kyinit")
+        return picked
+
 
     # ---- Frank-Wolfe steps in lock-step (C-ABI ``accbpg_dopt_batch_fw_*``); the state lives in the instance handles ----
     def _inst_h(self, i):

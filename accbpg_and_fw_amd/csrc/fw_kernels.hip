@@ -680,14 +680,29 @@ __global__ __launch_bounds__(FB) void fw_wupdate_probe_brun_kernel(const FwInst*
 static_assert(sizeof(FwProbeArgs) + sizeof(::BatchVals) + 64 <= 4096, "batch-run kernel arguments");
 
 // u = sum of the row-split partials (u = V^T q)
-__global__ __launch_bounds__(FB) void fw_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
-                                                    double* __restrict__ u) {
+__device__ __forceinline__ void fw_usum_body(const double* __restrict__ upart, int nsplit, int64_t n,
+                                             double* __restrict__ u) {
     const int64_t stride = (int64_t)gridDim.x * FB;
     for (int64_t k = (int64_t)blockIdx.x * FB + threadIdx.x; k < n; k += stride) {
         double a = 0.0;
         for (int s = 0; s < nsplit; ++s) a += upart[(int64_t)s * n + k];
         u[k] = a;
     }
+}
+__global__ __launch_bounds__(FB) void fw_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
+                                                    double* __restrict__ u) {
+    fw_usum_body(upart, nsplit, n, u);
+}
+// u = V^T q of the instances of a Kumar-Yildirim table in lock-step (launch_vt_times_batch): the instance is
+// blockIdx.z of the pass over V and blockIdx.y of the sum, the other grid dimensions are the single launch's
+__global__ __launch_bounds__(FB) void vt_partial_batch_kernel(const KyInst* __restrict__ tab, int64_t ldv, int64_t m,
+                                                             int64_t n, int first, int nsplit) {
+    const KyInst t = tab[blockIdx.z];
+    fw_vgemv_partial_body(t.V, ldv, m, n, first ? t.B : t.q, nsplit, t.vws, t.vec_ok != 0);
+}
+__global__ __launch_bounds__(FB) void vt_usum_batch_kernel(const KyInst* __restrict__ tab, int nsplit, int64_t n) {
+    const KyInst t = tab[blockIdx.y];
+    fw_usum_body(t.vws, nsplit, n, t.w);
 }
 __global__ __launch_bounds__(FB) void column_kernel(const double* __restrict__ V, int64_t ldv, int64_t m, int64_t j,
                                                    double* __restrict__ out) {
@@ -1377,6 +1392,18 @@ int launch_vt_times(const double* V, int64_t ldv, int64_t m, int64_t n, const do
     int64_t wb = (n + FB - 1) / FB;
     if (wb > 2048) wb = 2048;
     fw_usum_kernel<<<(int)wb, FB, 0, s>>>(upart, nsplit, n, u);
+    ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+
+// the two launches above with an instance dimension on their grids; every instance keeps the single launch's partition
+int launch_vt_times_batch(const KyInst* tab, int K, int64_t ldv, int64_t m, int64_t n, bool first, int nsplit,
+                          hipStream_t s) {
+    dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)nsplit, (unsigned)K);
+    vt_partial_batch_kernel<<<vg, FB, 0, s>>>(tab, ldv, m, n, first ? 1 : 0, nsplit);
+    int64_t wb = (n + FB - 1) / FB;
+    if (wb > 2048) wb = 2048;
+    vt_usum_batch_kernel<<<dim3((unsigned)wb, (unsigned)K), FB, 0, s>>>(tab, nsplit, n);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }

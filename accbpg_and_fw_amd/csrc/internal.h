@@ -100,6 +100,24 @@ struct FwUpdArgs {          // active instances of an update and their scalars, 
     double xscale[BATCH_MAX] = {}, xadd[BATCH_MAX] = {}, hcoef[BATCH_MAX] = {}, hdiv[BATCH_MAX] = {};
 };
 
+// One instance of a batched Kumar-Yildirim start (accbpg_dopt_batch_kyinit) as its lock-step kernels address it: the
+// instance's matrix and vt_times workspace, its m directions, and its slices of the call's scratch.  The table lives
+// for one call.
+struct MinMaxRec;
+struct KyInst {
+    const double* V;
+    double* vws;            // row-split partials of the pass over V (the handle's)
+    int64_t vec_ok;         // V rows are 16-byte aligned
+    const double* B;        // m*m: row r = the direction of step r
+    double* Q;              // m*m: column j at Q + j*m
+    double* w;              // n: q^T V of the step
+    double* q;              // m: deflated direction
+    double* v;              // m: V[:,kmin] - V[:,kmax]
+    double* c;              // m: Gram-Schmidt coefficients
+    MinMaxRec* part;        // 128 stage-1 records of the arg-extremum
+    int64_t* picked;        // 2m
+};
+
 // One handle's step as its "run" kernels read it (accbpg_fw_run): written by thread 0 of the probe's final stage, read
 // by the update kernels of that step; once stop != 0 every later kernel of the call returns at once
 struct FwRun {
@@ -340,6 +358,9 @@ int vec_scratch(double** pin, int** flags, double** out);
 int vt_nsplit(int64_t m, int64_t n, int num_cu);
 int launch_vt_times(const double* V, int64_t ldv, int64_t m, int64_t n, const double* q, double* upart, int nsplit,
                     double* u, bool vec_ok, hipStream_t s);
+// the same for the K instances of a table in lock-step: w_i = V_i^T q_i (first: V_i^T B_i[0], the direction of step 0)
+int launch_vt_times_batch(const KyInst* tab, int K, int64_t ldv, int64_t m, int64_t n, bool first, int nsplit,
+                          hipStream_t s);
 constexpr int VT_MAXSPLIT = 64;
 
 // device-to-device copy as a kernel on the stream (no copy-engine hand-off between producer and consumer kernels)

@@ -387,6 +387,21 @@ int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* active_host, co
 int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const double* eps_host, int nsteps, const int* active_host,
                              accbpg_fw_step* steps_host, int* nrun_host);
 
+/* accbpg_dopt_kyinit for all K instances of a batch in lock-step on the batch's stream: every launch of a step covers
+ * the K instances (8 launches per step, 4 at step 0, whatever K is), all m steps are enqueued, one copy returns the
+ * indices and the host waits once.
+ * B_dev: K*m*m doubles, instance i's directions at B_dev + i*m*m, row r = the direction of step r.
+ * picked_host: K*2m indices, instance i at picked_host + 2m*i, [2s] = kmax, [2s+1] = kmin of step s.
+ * Q_dev: optional K*m*m doubles, instance i's block at Q_dev + i*m*m, row j of the block = Q[:, j]; NULL = the call's own.
+ * Grids, row split and summation order of every instance are the single handle's: picked and Q of instance i are bit for
+ * bit those of accbpg_dopt_kyinit(accbpg_dopt_batch_instance(b, i), B_dev + i*m*m, ...).
+ * The call owns its scratch, one device allocation freed before it returns: per instance
+ * [m*m for Q unless Q_dev is given] + n + 3m doubles + 128 arg-extremum records (32 bytes each) + 2m indices, and one
+ * table entry (88 bytes).  Of the instances' handles it writes the workspace of accbpg_dopt_vt_times only: Gram /
+ * Cholesky state, Frank-Wolfe state and value records stay as they were.  Works with or without the fused Gram path
+ * (accbpg_dopt_batch_is_fused).  NULL b, B_dev or picked_host: ACCBPG_ERR_ARG. */
+int accbpg_dopt_batch_kyinit(accbpg_dopt_batch* b, const double* B_dev, int64_t* picked_host, double* Q_dev);
+
 /* ---- Poisson linear inverse problem with Burg L1 / L2 kernels -------- */
 
 typedef struct accbpg_poisson accbpg_poisson;

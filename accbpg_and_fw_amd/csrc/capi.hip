@@ -552,6 +552,13 @@ extern "C" int accbpg_debug_plan_flags(int flags) {
     return ACCBPG_OK;
 }
 
+/* Development switch, process wide, read at every launch: the k-loop of the 64x64 tile products (inverse merges, their
+ * batched form, the m > 2048 Cholesky trailing updates, accbpg_test_gemm config 0).  0 = production, 1 = the loop with
+ * one k-step of look-ahead that production had before, 2..4 = that many k-steps of loads in flight.  Same bits from all. */
+extern "C" int accbpg_debug_gemm_loop(int variant) {
+    return set_gemm_loop(variant);
+}
+
 extern "C" int accbpg_debug_chol_variant(accbpg_dopt* h, int bits) {
     if (!h) return ACCBPG_ERR_ARG;
     value_forget(h);

@@ -7,6 +7,7 @@
 //   :48  np.linalg.slogdet           -> Cholesky (potrf_diag / trsm_panel / trailing GEMM), logdet = 2*sum log L_ii
 //   :57  np.linalg.solve(HXHT, H)    -> W = L^-1 (trtri_diag + merge GEMMs), Y = W V never stored
 //   :58  -sum(H * HXHTinvH, axis=0)  -> -colsum(Y*Y) fused into the product (colnorm_kernel)
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 #include <type_traits>
@@ -925,7 +926,13 @@ __global__ __launch_bounds__(NTHREADS, 1) void colnorm_glds_batch_kernel(
 // Batched small GEMM on the 64x64 tile: C = alpha*A*op(B) + beta*C for a table of products.
 // grid = (tiles_n, tiles_m, nops).  Used by the Cholesky trailing update and the inverse merges.
 // =========================================================================================
-template <class T>
+// LOOP = 0: the global loads of k-step ks+1 are issued before the MFMAs of k-step ks and stored to LDS after them (one
+// step of look-ahead).  LOOP = D >= 2: the loads of D k-steps are in flight in registers.  A k-step of this tile is 16
+// MFMAs per wave, far shorter than a global load, so with one step of look-ahead every step waits for its load; with D
+// of them the wait is for a load issued D - 1 steps earlier.  Every step in flight has registers of its own (the
+// rotation is unrolled D times), so the compiler counts the loads it may leave outstanding.  LDS stays at two stages.
+// Both loops run the same MFMAs on the same operands in the same k order.
+template <class T, int LOOP>
 __device__ __forceinline__ void gemm_ops_body(const GemmOp op) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int64_t row0 = (int64_t)blockIdx.y * T::BM, col0 = (int64_t)blockIdx.x * T::BN;
@@ -943,37 +950,105 @@ __device__ __forceinline__ void gemm_ops_body(const GemmOp op) {
         t.store_C(op.C, op.ldc, row0, col0, op.M, op.N, op.alpha, op.beta, op.lower_only != 0);
         return;
     }
-    auto gload = [&](int64_t ks) {
-        t.gload_A(op.A, op.lda, row0, op.M, ks * BK, op.K, va);
-        if constexpr (T::BKM) t.gload_B_km(op.B, op.ldb, col0, op.N, ks * BK, op.K, vb);
-        else t.gload_B_kc(op.B, op.ldb, col0, op.N, ks * BK, op.K, vb);
-    };
-    gload(ks0);
-    t.sstore(lds);
-    __syncthreads();
-    int cur = 0;
-    for (int64_t ks = ks0; ks < ksteps; ++ks) {
-        const bool more = ks + 1 < ksteps;
-        if (more) gload(ks + 1);
-        t.compute(lds + cur * T::STAGE_ELEMS);
-        if (more) t.sstore(lds + (cur ^ 1) * T::STAGE_ELEMS);
+    if constexpr (LOOP == 0) {
+        auto gload = [&](int64_t ks) {
+            t.gload_A(op.A, op.lda, row0, op.M, ks * BK, op.K, va);
+            if constexpr (T::BKM) t.gload_B_km(op.B, op.ldb, col0, op.N, ks * BK, op.K, vb);
+            else t.gload_B_kc(op.B, op.ldb, col0, op.N, ks * BK, op.K, vb);
+        };
+        gload(ks0);
+        t.sstore(lds);
         __syncthreads();
-        cur ^= 1;
+        int cur = 0;
+        for (int64_t ks = ks0; ks < ksteps; ++ks) {
+            const bool more = ks + 1 < ksteps;
+            if (more) gload(ks + 1);
+            t.compute(lds + cur * T::STAGE_ELEMS);
+            if (more) t.sstore(lds + (cur ^ 1) * T::STAGE_ELEMS);
+            __syncthreads();
+            cur ^= 1;
+        }
+    } else {
+        constexpr int D = LOOP;
+        // Two things keep the compiler from counting the loads it may leave in flight, and make it wait for all of them:
+        //  - flat loads.  The operand pointers come out of the op table, so it cannot tell that they are global memory;
+        //    hence as_global();
+        //  - loads under branches (load2_guard).  A tile that lies inside both operands and whose rows are 16-byte
+        //    aligned -- every tile of the merges at the sizes that matter -- takes the loop with unguarded loads.
+        // Both loops load the same values.
+        const bool inside = va && vb && row0 + T::BM <= op.M && col0 + T::BN <= op.N && ksteps * BK <= op.K;
+        // slot (ks - ks0) % D holds the staged chunks of k-step ks from its load to its LDS store
+        d2 pa[D][T::A_PASS], pb[D][T::B_PASS];
+        auto sstore_from = [&](auto slot, double* __restrict__ stage) {
+            constexpr int S = decltype(slot)::value;
+#pragma unroll
+            for (int p = 0; p < T::A_PASS; ++p) t.ra[p] = pa[S][p];
+#pragma unroll
+            for (int p = 0; p < T::B_PASS; ++p) t.rb[p] = pb[S][p];
+            t.sstore(stage);
+        };
+        auto run = [&](auto guard) {
+            constexpr bool GUARD = decltype(guard)::value;
+            auto gload_to = [&](auto slot, int64_t ks) {
+                constexpr int S = decltype(slot)::value;
+                t.template gload_A<GUARD>(as_global(op.A), op.lda, row0, op.M, ks * BK, op.K, va);
+                if constexpr (T::BKM) t.template gload_B_km<GUARD>(as_global(op.B), op.ldb, col0, op.N, ks * BK, op.K, vb);
+                else t.template gload_B_kc<GUARD>(as_global(op.B), op.ldb, col0, op.N, ks * BK, op.K, vb);
+#pragma unroll
+                for (int p = 0; p < T::A_PASS; ++p) pa[S][p] = t.ra[p];
+#pragma unroll
+                for (int p = 0; p < T::B_PASS; ++p) pb[S][p] = t.rb[p];
+            };
+            // prologue: k-steps ks0 .. ks0+D-1 requested, the first of them stored, its slot refilled with k-step ks0+D
+            static_for<0, D>([&](auto j) {
+                if (ks0 + decltype(j)::value < ksteps) gload_to(j, ks0 + decltype(j)::value);
+            });
+            sstore_from(std::integral_constant<int, 0>{}, lds);
+            if (ks0 + D < ksteps) gload_to(std::integral_constant<int, 0>{}, ks0 + D);
+            __syncthreads();
+            int cur = 0;
+            // k-step ks (slot J) is in LDS stage `cur`: store k-step ks+1 to the other stage, refill its slot with
+            // k-step ks+1+D, run the MFMAs of ks.  FULL = both exist for every step of the group (no tests in the
+            // steady state).
+            auto group = [&](int64_t ks, auto full) {
+                constexpr bool FULL = decltype(full)::value;
+                static_for<0, D>([&](auto j) {
+                    constexpr int J = decltype(j)::value;
+                    const int64_t s = ks + J;
+                    if (FULL || s < ksteps) {
+                        std::integral_constant<int, (J + 1) % D> next;
+                        if (FULL || s + 1 < ksteps) sstore_from(next, lds + (cur ^ 1) * T::STAGE_ELEMS);
+                        if (FULL || s + 1 + D < ksteps) gload_to(next, s + 1 + D);
+                        t.compute(lds + cur * T::STAGE_ELEMS);
+                        __syncthreads();
+                        cur ^= 1;
+                    }
+                });
+            };
+            int64_t ks = ks0;
+            if constexpr (!GUARD)
+                for (; ks + 2 * D < ksteps; ks += D) group(ks, std::true_type{});
+            for (; ks < ksteps; ks += D) group(ks, std::false_type{});
+        };
+        if (inside) run(std::false_type{});
+        else run(std::true_type{});
     }
     t.store_C(op.C, op.ldc, row0, col0, op.M, op.N, op.alpha, op.beta, op.lower_only != 0);
 }
 
-template <class T>
+// LOOP as in gemm_ops_body; GEMM_LOOP_DEPTH is what production launches
+constexpr int GEMM_LOOP_DEPTH = 3;
+template <class T, int LOOP = GEMM_LOOP_DEPTH>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_ops_kernel(const GemmOp* __restrict__ ops) {
-    gemm_ops_body<T>(ops[blockIdx.z]);
+    gemm_ops_body<T, LOOP>(ops[blockIdx.z]);
 }
 // products of the ACTIVE instances of a batch: `ops` holds the op tables of all instances one after the other
 // (`per_inst` ops each, the same stage of every instance at the same offset)
-template <class T>
+template <class T, int LOOP = GEMM_LOOP_DEPTH>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_ops_batch_kernel(const GemmOp* __restrict__ ops, int per_inst, int begin,
                                                                     int count, BatchAct act) {
     const int a = blockIdx.z / count, o = blockIdx.z - a * count;
-    gemm_ops_body<T>(ops[(int64_t)act.idx[a] * per_inst + begin + o]);
+    gemm_ops_body<T, LOOP>(ops[(int64_t)act.idx[a] * per_inst + begin + o]);
 }
 
 // split-K reduction: C = sum of the ns partial products (fixed order)
@@ -2347,6 +2422,40 @@ void prof_end(accbpg_dopt* h, ProfKind k) {
 static int g_plan_flags = 0;
 void set_plan_flags(int flags) { g_plan_flags = flags; }
 
+// development switch of the 64x64 tile loop (gemm_ops_body), read at every launch: 0 = production (GEMM_LOOP_DEPTH
+// k-steps of loads in flight), 1 = the loop with one step of look-ahead, 2..4 = that many k-steps in flight (A/B
+// measurements of the depth).  All of them give the same bits.
+static std::atomic<int> g_gemm_loop{0};
+int set_gemm_loop(int variant) {
+    if (variant < 0 || variant > 4) return ACCBPG_ERR_ARG;
+    g_gemm_loop.store(variant);
+    return ACCBPG_OK;
+}
+template <int LOOP>
+static int set_lds_gemm_loop() {
+    ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<true>, LOOP>, TileSmall<true>::LDS_BYTES));
+    ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<false>, LOOP>, TileSmall<false>::LDS_BYTES));
+    return ACCBPG_OK;
+}
+static int set_lds_gemm_ops() {
+    ACC_TRY(set_lds_gemm_loop<0>());
+    ACC_TRY(set_lds_gemm_loop<2>());
+    ACC_TRY(set_lds_gemm_loop<3>());
+    ACC_TRY(set_lds_gemm_loop<4>());
+    return ACCBPG_OK;
+}
+// f(std::integral_constant<int, LOOP>) for the LOOP that the switch selects
+template <class F>
+static int with_gemm_loop(F&& f) {
+    switch (g_gemm_loop.load()) {
+        case 0: return f(std::integral_constant<int, GEMM_LOOP_DEPTH>{});
+        case 1: return f(std::integral_constant<int, 0>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
 int build_plans(accbpg_dopt* h) {
     const int64_t m = h->m;
     // ---- Gram tile list (lower tiles) and stream-K partition
@@ -2701,8 +2810,7 @@ int build_plans(accbpg_dopt* h) {
     ACC_TRY(set_lds(colnorm_kernel<TileBig<true, false>>, TileBig<true>::LDS_BYTES));
     ACC_TRY(set_lds(colnorm_kernel<TileSmall<true, true>>, TileSmall<true>::LDS_BYTES));
     ACC_TRY(set_lds(colnorm_kernel<TileSmall<true, false>>, TileSmall<true>::LDS_BYTES));
-    ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<true>>, TileSmall<true>::LDS_BYTES));
-    ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<false>>, TileSmall<false>::LDS_BYTES));
+    ACC_TRY(set_lds_gemm_ops());
     ACC_TRY(set_lds(chol_step_kernel, CHOL_LDS_BYTES));
     ACC_TRY(set_lds(chol_syrk_kernel, SYRK_LDS_BYTES));
     ACC_TRY(set_lds(gemm_big_kernel<TileBig<true>>, TileBig<true>::LDS_BYTES));
@@ -2859,12 +2967,15 @@ int device_copy(double* dst, const double* src, size_t ndoubles, hipStream_t s) 
 int launch_gemm_ops(const GemmOp* ops_dev, int nops, int maxM, int maxN, bool b_kmajor, hipStream_t s) {
     if (nops <= 0 || maxM <= 0 || maxN <= 0) return ACCBPG_OK;
     dim3 grid((maxN + 63) / 64, (maxM + 63) / 64, nops);
-    if (b_kmajor)
-        gemm_ops_kernel<TileSmall<true>><<<grid, NTHREADS, TileSmall<true>::LDS_BYTES, s>>>(ops_dev);
-    else
-        gemm_ops_kernel<TileSmall<false>><<<grid, NTHREADS, TileSmall<false>::LDS_BYTES, s>>>(ops_dev);
-    ACC_HIP(hipGetLastError());
-    return ACCBPG_OK;
+    return with_gemm_loop([&](auto loop) -> int {
+        constexpr int LOOP = decltype(loop)::value;
+        if (b_kmajor)
+            gemm_ops_kernel<TileSmall<true>, LOOP><<<grid, NTHREADS, TileSmall<true>::LDS_BYTES, s>>>(ops_dev);
+        else
+            gemm_ops_kernel<TileSmall<false>, LOOP><<<grid, NTHREADS, TileSmall<false>::LDS_BYTES, s>>>(ops_dev);
+        ACC_HIP(hipGetLastError());
+        return ACCBPG_OK;
+    });
 }
 
 // In-place Cholesky of the lower triangle of A (m x m, ld m).  Resets and fills dscal[0] (log det)
@@ -3097,8 +3208,11 @@ int launch_trtri_batch(accbpg_dopt_batch* b, const BatchAct& act) {
         if (count <= 0) continue;
         if (st.kind == 0) {
             dim3 grid((st.maxn + 63) / 64, (st.maxm + 63) / 64, count * act.n);
-            gemm_ops_batch_kernel<TileSmall<true>><<<grid, NTHREADS, TileSmall<true>::LDS_BYTES, b->stream>>>(
-                b->ops_all, b->ops_per_inst, st.begin, count, act);
+            ACC_TRY(with_gemm_loop([&](auto loop) -> int {
+                gemm_ops_batch_kernel<TileSmall<true>, decltype(loop)::value><<<grid, NTHREADS, TileSmall<true>::LDS_BYTES, b->stream>>>(
+                    b->ops_all, b->ops_per_inst, st.begin, count, act);
+                return ACCBPG_OK;
+            }));
         } else {
             int gx = (int)std::min<int64_t>(1024, ((int64_t)st.maxm / 2 + 255) / 256);
             gemm_reduce_batch_kernel<<<dim3(gx, count * act.n), 256, 0, b->stream>>>(b->red_all, b->red_per_inst, st.begin, count, act);
@@ -3195,8 +3309,7 @@ int launch_test_gemm(const double* A, int64_t lda, const double* B, int64_t ldb,
         GemmOp* d = nullptr;
         ACC_HIP(hipMalloc(&d, sizeof(GemmOp)));
         ACC_HIP(hipMemcpyAsync(d, &op, sizeof(GemmOp), hipMemcpyHostToDevice, s));
-        ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<true>>, TileSmall<true>::LDS_BYTES));
-        ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<false>>, TileSmall<false>::LDS_BYTES));
+        ACC_TRY(set_lds_gemm_ops());
         int rc = launch_gemm_ops(d, 1, (int)M, (int)N, b_kmajor != 0, s);
         hipStreamSynchronize(s);
         hipFree(d);

@@ -343,6 +343,7 @@ int launch_test_gemm(const double* A, int64_t lda, const double* B, int64_t ldb,
                      hipStream_t s);
 int build_plans(accbpg_dopt* h);
 void set_plan_flags(int flags);
+int set_gemm_loop(int variant);
 int debug_gram_variant(accbpg_dopt* h, const double* x, int var, int iters, double* ms_out);
 int debug_grad_variant(accbpg_dopt* h, double* out, int var, int iters, double* ms_out);
 int mfma_peak(int iters, double* tflops, hipStream_t s);

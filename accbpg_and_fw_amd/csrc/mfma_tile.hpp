@@ -32,11 +32,20 @@ constexpr int BK = 16;
 constexpr int SK = BK + 2;          // LDS row stride (doubles) of a k-contiguous image
 constexpr int NTHREADS = 256;
 
-__device__ __forceinline__ d2 load2_guard(const double* __restrict__ p, bool row_ok, int64_t k, int64_t K,
-                                          bool vec_ok) {
+// A pointer that is known to be global memory.  The register-staged loads (gload_*) take either kind: through a generic
+// pointer whose origin the compiler cannot see (one read from a table in memory) they are flat loads, and a wait for a
+// flat load is a wait for every load in flight; through a gptr they are global loads, which retire in order and can be
+// waited for by count.
+typedef const __attribute__((address_space(1))) double* gptr;
+__device__ __forceinline__ gptr as_global(const double* p) { return (gptr)p; }
+__device__ __forceinline__ d2 ld2(const double* p) { return *reinterpret_cast<const d2*>(p); }
+__device__ __forceinline__ d2 ld2(gptr p) { return *(const __attribute__((address_space(1))) d2*)p; }
+
+template <class P>
+__device__ __forceinline__ d2 load2_guard(P p, bool row_ok, int64_t k, int64_t K, bool vec_ok) {
     d2 v;
     if (row_ok && vec_ok && k + 1 < K) {
-        v = *reinterpret_cast<const d2*>(p);
+        v = ld2(p);
     } else {
         v.x = (row_ok && k < K) ? p[0] : 0.0;
         v.y = (row_ok && k + 1 < K) ? p[1] : 0.0;
@@ -107,16 +116,18 @@ struct Tile {
     }
 
     // ---- global -> registers -------------------------------------------------------------
+    // GUARD = false is the caller's promise for THIS call of what EDGE = false promises for the whole tile type.
     // A: rows [row0, row0+BM) of a k-contiguous matrix (lda), columns [k0, k0+16).
-    __device__ __forceinline__ void gload_A(const double* __restrict__ A, int64_t lda, int64_t row0, int64_t M,
+    template <bool GUARD = EDGE_, class P>
+    __device__ __forceinline__ void gload_A(P __restrict__ A, int64_t lda, int64_t row0, int64_t M,
                                             int64_t k0, int64_t K, bool vec_ok) {
         const int tid = threadIdx.x;
         const int c = tid & 7, r = tid >> 3;
         const int64_t k = k0 + 2 * c;
-        if constexpr (!EDGE) {
-            const double* __restrict__ base = A + (row0 + r) * lda + k;
+        if constexpr (!GUARD) {
+            P __restrict__ base = A + (row0 + r) * lda + k;
 #pragma unroll
-            for (int p = 0; p < A_PASS; ++p) ra[p] = *reinterpret_cast<const d2*>(base + (int64_t)(32 * p) * lda);
+            for (int p = 0; p < A_PASS; ++p) ra[p] = ld2(base + (int64_t)(32 * p) * lda);
         } else {
 #pragma unroll
             for (int p = 0; p < A_PASS; ++p) {
@@ -144,15 +155,16 @@ struct Tile {
         }
     }
     // B k-contiguous: rows (= output columns) [col0, col0+BN) of B[col][k].
-    __device__ __forceinline__ void gload_B_kc(const double* __restrict__ B, int64_t ldb, int64_t col0, int64_t N,
+    template <bool GUARD = EDGE_, class P>
+    __device__ __forceinline__ void gload_B_kc(P __restrict__ B, int64_t ldb, int64_t col0, int64_t N,
                                                int64_t k0, int64_t K, bool vec_ok) {
         const int tid = threadIdx.x;
         const int c = tid & 7, r = tid >> 3;
         const int64_t k = k0 + 2 * c;
-        if constexpr (!EDGE) {
-            const double* __restrict__ base = B + (col0 + r) * ldb + k;
+        if constexpr (!GUARD) {
+            P __restrict__ base = B + (col0 + r) * ldb + k;
 #pragma unroll
-            for (int p = 0; p < B_PASS; ++p) rb[p] = *reinterpret_cast<const d2*>(base + (int64_t)(32 * p) * ldb);
+            for (int p = 0; p < B_PASS; ++p) rb[p] = ld2(base + (int64_t)(32 * p) * ldb);
         } else {
 #pragma unroll
             for (int p = 0; p < B_PASS; ++p) {
@@ -162,16 +174,17 @@ struct Tile {
         }
     }
     // B k-major: rows [k0, k0+16) of B[k][col], columns [col0, col0+BN).
-    __device__ __forceinline__ void gload_B_km(const double* __restrict__ B, int64_t ldb, int64_t col0, int64_t N,
+    template <bool GUARD = EDGE_, class P>
+    __device__ __forceinline__ void gload_B_km(P __restrict__ B, int64_t ldb, int64_t col0, int64_t N,
                                                int64_t k0, int64_t K, bool vec_ok) {
         const int tid = threadIdx.x;
         const int c = 2 * (tid % BKM_TPR), r = tid / BKM_TPR;
         const int64_t col = col0 + c;
-        if constexpr (!EDGE) {
-            const double* __restrict__ base = B + (k0 + r) * ldb + col;
+        if constexpr (!GUARD) {
+            P __restrict__ base = B + (k0 + r) * ldb + col;
 #pragma unroll
             for (int p = 0; p < B_PASS; ++p)
-                rb[p] = *reinterpret_cast<const d2*>(base + (int64_t)(BKM_RPP * p) * ldb);
+                rb[p] = ld2(base + (int64_t)(BKM_RPP * p) * ldb);
         } else {
 #pragma unroll
             for (int p = 0; p < B_PASS; ++p) {

@@ -594,6 +594,12 @@ int accbpg_dopt_factor_in_small_launches(accbpg_dopt* h, int on);
  * tile list is longer than the grid (m >= 4096), instead of whole tiles per workgroup (A/B measurements). */
 int accbpg_debug_plan_flags(int flags);
 
+/* Development switch, process wide, read at every launch: the k-loop of the products on the 64x64 tile (the merges of
+ * the triangular inverse, their batched form, the trailing updates of the m > 2048 Cholesky, accbpg_test_gemm config 0).
+ * 0 = production (the global loads of three k-steps in flight), 1 = the loop with one k-step of look-ahead that
+ * production had before, 2..4 = that many k-steps in flight (A/B measurements).  Bit-identical results from all. */
+int accbpg_debug_gemm_loop(int variant);
+
 /* Timing ablation bits for the Cholesky step kernel (development aid; 0 = product behaviour):
  * 1 skip the diagonal-block factorisation, 2 skip the panel solve, 4 skip the MFMA products; 8, 16, 32 switch
  * off the row solves / MFMA updates / 16x16 factor inside the 64x64 factorisation.  256 / 512 select the

@@ -12,11 +12,6 @@ constexpr int FB = 256;
 constexpr int VG_COLS = 2 * FB;      // columns of V per workgroup in the V^T Hv pass
 constexpr int VG_MAXSPLIT = 64;
 
-struct ValIdx {
-    double v;
-    int64_t i;
-};
-
 // first-index-on-ties argmax / argmin, the NumPy convention (D_opt_alg.py:59,61,145,147); a NaN is the
 // extremum for both (np.argmax / np.argmin return the first NaN)
 __device__ __forceinline__ ValIdx better_max(ValIdx a, ValIdx b) {
@@ -125,7 +120,6 @@ __device__ __forceinline__ void fw_probe_final_body(const ValIdx* __restrict__ p
 // every workgroup combines the stage-1 maxima itself (at most 512 records: the same w_i everywhere), then takes the
 // first-index minimum of d_k = (w_k - w_i) * [x_k > 1e-8] -- formed exactly as the reference forms it, D_opt_alg.py:146-147
 // -- over its slice; workgroup 0 leaves (w_i, i) for the final stage.
-constexpr int AWAY_NB = 128;        // at most this many slices
 __device__ __forceinline__ void fw_probe_away_partial_body(const ValIdx* __restrict__ part, int nblk,
                                                                   const double* __restrict__ w,
                                                                   const double* __restrict__ x, int64_t n,
@@ -422,10 +416,8 @@ __global__ __launch_bounds__(FB) void fw_wupdate_probe_kernel(double* __restrict
 // The instance is a grid dimension (blockIdx.z for the pass over V, whose blockIdx.y is the row split; blockIdx.y
 // elsewhere); blockIdx.x and gridDim.x are what the single launch of that instance has, so the bodies partition and
 // sum as they do there.  Pointers come from the batch's device table (FwInst), the active set and the per-instance
-// scalars travel by value in the kernel arguments: no second synchronisation per step.
-__device__ __forceinline__ ValIdx* fw_part_of(const FwInst& t, int64_t m) {
-    return reinterpret_cast<ValIdx*>(t.hv + 2 * m);             // 2*512 stage-1 records behind Hv / vp
-}
+// scalars travel by value in the kernel arguments: no second synchronisation per step.  What lies behind t.hv and the
+// layout of a probe record are the accessors next to FwInst (internal.h), here and on the host.
 __global__ __launch_bounds__(FB) void fw_probe_partial_batch_kernel(const FwInst* __restrict__ tab, BatchAct act,
                                                                    int64_t m, int64_t n, int away) {
     const FwInst t = tab[act.idx[blockIdx.y]];
@@ -434,37 +426,34 @@ __global__ __launch_bounds__(FB) void fw_probe_partial_batch_kernel(const FwInst
 __global__ __launch_bounds__(FB) void fw_probe_final_batch_kernel(const FwInst* __restrict__ tab, FwProbeArgs pa,
                                                                  int64_t m, int64_t n, int away) {
     const FwInst t = tab[pa.idx[blockIdx.y]];
-    fw_probe_final_body(fw_part_of(t, m), pa.nblk[blockIdx.y], t.w, t.x, n, away, t.rec + 4,
-                        reinterpret_cast<int64_t*>(t.rec + 8), t.q);
+    fw_probe_final_body(fw_part_of(t, m), pa.nblk[blockIdx.y], t.w, t.x, n, away, fw_rec_d(t.rec),
+                        fw_rec_i(t.rec), t.q);
 }
 __global__ __launch_bounds__(FB) void fw_probe_away_partial_batch_kernel(const FwInst* __restrict__ tab, FwProbeArgs pa,
                                                                         int64_t m, int64_t n) {
     const FwInst t = tab[pa.idx[blockIdx.y]];
-    ValIdx* part = fw_part_of(t, m);
-    ValIdx* part2 = part + 2 * 512;
-    fw_probe_away_partial_body(part, pa.nblk[blockIdx.y], t.w, t.x, n, part2, part2 + AWAY_NB);
+    fw_probe_away_partial_body(fw_part_of(t, m), pa.nblk[blockIdx.y], t.w, t.x, n, fw_part2_of(t, m), fw_mxslot_of(t, m));
 }
 __global__ __launch_bounds__(FB) void fw_probe_away_final_batch_kernel(const FwInst* __restrict__ tab, FwProbeArgs pa,
                                                                       int nb2, int64_t m, int64_t n) {
     const FwInst t = tab[pa.idx[blockIdx.y]];
-    ValIdx* part2 = fw_part_of(t, m) + 2 * 512;
-    fw_probe_away_final_body(part2, nb2, part2 + AWAY_NB, t.w, t.x, n, t.rec + 4, reinterpret_cast<int64_t*>(t.rec + 8),
+    fw_probe_away_final_body(fw_part2_of(t, m), nb2, fw_mxslot_of(t, m), t.w, t.x, n, fw_rec_d(t.rec), fw_rec_i(t.rec),
                              t.q);
 }
 __global__ __launch_bounds__(FB) void fw_xupdate_gather_batch_kernel(const FwInst* __restrict__ tab, FwUpdArgs ua,
                                                                     int64_t m, int64_t n, int64_t ldv) {
     const int a = blockIdx.y;
     const FwInst t = tab[ua.idx[a]];
-    fw_xupdate_gather_body(t.x, n, ua.p[a], ua.xscale[a], ua.xadd[a], t.V, ldv, m, t.hv + m);
+    fw_xupdate_gather_body(t.x, n, ua.p[a], ua.xscale[a], ua.xadd[a], t.V, ldv, m, fw_vp_of(t, m));
 }
 __global__ __launch_bounds__(FB) void fw_gemv_h_batch_kernel(const FwInst* __restrict__ tab, BatchAct act, int64_t m) {
     const FwInst t = tab[act.idx[blockIdx.y]];
-    fw_gemv_h_body(t.H, m, t.hv + m, t.hv);
+    fw_gemv_h_body(t.H, m, fw_vp_of(t, m), t.hv);
 }
 __global__ __launch_bounds__(FB) void fw_rank1_batch_kernel(const FwInst* __restrict__ tab, FwUpdArgs ua, int64_t m) {
     const int a = blockIdx.y;
     const FwInst t = tab[ua.idx[a]];
-    fw_rank1_body(t.H, m, t.hv, ua.hcoef[a], ua.hdiv[a], t.hv + m, t.q);
+    fw_rank1_body(t.H, m, t.hv, ua.hcoef[a], ua.hdiv[a], fw_vp_of(t, m), t.q);
 }
 __global__ __launch_bounds__(FB) void fw_vgemv_partial_batch_kernel(const FwInst* __restrict__ tab, BatchAct act,
                                                                    int64_t ldv, int64_t m, int64_t n, int nsplit) {
@@ -534,7 +523,7 @@ __global__ __launch_bounds__(FB) void fw_probe_final_run_kernel(FwRun* run, cons
                                                                const double* __restrict__ qsrc,
                                                                accbpg_fw_step* __restrict__ out) {
     if (fw_run_stop(run)) return;
-    fw_probe_final_body(part, nblk, w, x, n, away, rec + 4, reinterpret_cast<int64_t*>(rec + 8), qsrc);
+    fw_probe_final_body(part, nblk, w, x, n, away, fw_rec_d(rec), fw_rec_i(rec), qsrc);
     if (threadIdx.x == 0) fw_run_decide(run, rec, m, n, away, eps, out);
 }
 __global__ __launch_bounds__(FB) void fw_probe_away_partial_run_kernel(const FwRun* run, const ValIdx* __restrict__ part,
@@ -553,7 +542,7 @@ __global__ __launch_bounds__(FB) void fw_probe_away_final_run_kernel(FwRun* run,
                                                                     const double* __restrict__ qsrc,
                                                                     accbpg_fw_step* __restrict__ out) {
     if (fw_run_stop(run)) return;
-    fw_probe_away_final_body(part2, nb2, mxslot, w, x, n, rec + 4, reinterpret_cast<int64_t*>(rec + 8), qsrc);
+    fw_probe_away_final_body(part2, nb2, mxslot, w, x, n, fw_rec_d(rec), fw_rec_i(rec), qsrc);
     if (threadIdx.x == 0) fw_run_decide(run, rec, m, n, 1, eps, out);
 }
 __global__ __launch_bounds__(FB) void fw_xupdate_gather_run_kernel(const FwRun* __restrict__ run, double* __restrict__ x,
@@ -606,8 +595,8 @@ __global__ __launch_bounds__(FB) void fw_probe_final_brun_kernel(const FwInst* _
     FwRunSlot* sl = runs + i;
     if (fw_run_stop(&sl->run)) return;
     const FwInst t = tab[i];
-    fw_probe_final_body(fw_part_of(t, m), pa.nblk[a], t.w, t.x, n, away, sl->rec + 4,
-                        reinterpret_cast<int64_t*>(sl->rec + 8), t.q);
+    fw_probe_final_body(fw_part_of(t, m), pa.nblk[a], t.w, t.x, n, away, fw_rec_d(sl->rec),
+                        fw_rec_i(sl->rec), t.q);
     if (threadIdx.x == 0)
         fw_run_decide(&sl->run, sl->rec, m, n, away, eps.v[a], steps + (size_t)i * ACCBPG_FW_RUN_MAX + k);
 }
@@ -617,9 +606,7 @@ __global__ __launch_bounds__(FB) void fw_probe_away_partial_brun_kernel(const Fw
     const int a = blockIdx.y, i = pa.idx[a];
     if (fw_run_stop(&runs[i].run)) return;
     const FwInst t = tab[i];
-    ValIdx* part = fw_part_of(t, m);
-    ValIdx* part2 = part + 2 * 512;
-    fw_probe_away_partial_body(part, pa.nblk[a], t.w, t.x, n, part2, part2 + AWAY_NB);
+    fw_probe_away_partial_body(fw_part_of(t, m), pa.nblk[a], t.w, t.x, n, fw_part2_of(t, m), fw_mxslot_of(t, m));
 }
 __global__ __launch_bounds__(FB) void fw_probe_away_final_brun_kernel(const FwInst* __restrict__ tab, FwRunSlot* runs,
                                                                      BatchAct act, ::BatchVals eps, int nb2, int64_t m,
@@ -628,9 +615,8 @@ __global__ __launch_bounds__(FB) void fw_probe_away_final_brun_kernel(const FwIn
     FwRunSlot* sl = runs + i;
     if (fw_run_stop(&sl->run)) return;
     const FwInst t = tab[i];
-    ValIdx* part2 = fw_part_of(t, m) + 2 * 512;
-    fw_probe_away_final_body(part2, nb2, part2 + AWAY_NB, t.w, t.x, n, sl->rec + 4,
-                             reinterpret_cast<int64_t*>(sl->rec + 8), t.q);
+    fw_probe_away_final_body(fw_part2_of(t, m), nb2, fw_mxslot_of(t, m), t.w, t.x, n, fw_rec_d(sl->rec),
+                             fw_rec_i(sl->rec), t.q);
     if (threadIdx.x == 0)
         fw_run_decide(&sl->run, sl->rec, m, n, 1, eps.v[a], steps + (size_t)i * ACCBPG_FW_RUN_MAX + k);
 }
@@ -641,14 +627,14 @@ __global__ __launch_bounds__(FB) void fw_xupdate_gather_brun_kernel(const FwInst
     const FwRun r = runs[i].run;
     if (r.stop) return;
     const FwInst t = tab[i];
-    fw_xupdate_gather_body(t.x, n, r.p, r.xscale, r.xadd, t.V, ldv, m, t.hv + m);
+    fw_xupdate_gather_body(t.x, n, r.p, r.xscale, r.xadd, t.V, ldv, m, fw_vp_of(t, m));
 }
 __global__ __launch_bounds__(FB) void fw_gemv_h_brun_kernel(const FwInst* __restrict__ tab,
                                                            const FwRunSlot* __restrict__ runs, BatchAct act, int64_t m) {
     const int i = act.idx[blockIdx.y];
     if (runs[i].run.stop) return;
     const FwInst t = tab[i];
-    fw_gemv_h_body(t.H, m, t.hv + m, t.hv);
+    fw_gemv_h_body(t.H, m, fw_vp_of(t, m), t.hv);
 }
 __global__ __launch_bounds__(FB) void fw_rank1_brun_kernel(const FwInst* __restrict__ tab,
                                                           const FwRunSlot* __restrict__ runs, BatchAct act, int64_t m) {
@@ -656,7 +642,7 @@ __global__ __launch_bounds__(FB) void fw_rank1_brun_kernel(const FwInst* __restr
     const FwRun r = runs[i].run;
     if (r.stop) return;
     const FwInst t = tab[i];
-    fw_rank1_body(t.H, m, t.hv, r.hcoef, r.hdiv, t.hv + m, t.q);
+    fw_rank1_body(t.H, m, t.hv, r.hcoef, r.hdiv, fw_vp_of(t, m), t.q);
 }
 __global__ __launch_bounds__(FB) void fw_vgemv_partial_brun_kernel(const FwInst* __restrict__ tab,
                                                                   const FwRunSlot* __restrict__ runs, BatchAct act,
@@ -743,13 +729,81 @@ static int fw_alloc(accbpg_dopt* h) {
     ACC_HIP(hipMalloc(&h->fw_x, sizeof(double) * h->n));
     ACC_HIP(hipMalloc(&h->fw_w, sizeof(double) * h->n));
     ACC_HIP(hipMalloc(&h->fw_H, sizeof(double) * h->m * h->m));
-    // Hv, vp, 2 * 512 stage-1 probe records, AWAY_NB stage-2 records + (w_i, i) of the away variant
-    ACC_HIP(hipMalloc(&h->fw_hv, sizeof(double) * (2 * h->m + 2 * 1024 + 16 + 2 * AWAY_NB + 4)));
+    ACC_HIP(hipMalloc(&h->fw_hv, sizeof(double) * fw_scratch_doubles(h->m)));
+    h->fw = FwInst{h->fw_x, h->fw_w, h->fw_H, h->fw_hv, h->V, h->vws, h->dscal + 10, h->fw_hpin_dev, h->vec_ok ? 1 : 0};
     return ACCBPG_OK;
 }
 
 namespace accbpg { int vt_nsplit(int64_t m, int64_t n, int num_cu); }
 static int fw_nsplit(const accbpg_dopt* h) { return vt_nsplit(h->m, h->n, h->num_cu); }
+
+// Every grid of a step at one shape on one device, without the instance dimension.  All four families of entry points
+// launch on these, so an instance of a batch gets the single handle's partition and summation order.
+struct FwGrids {
+    unsigned nblk;          // stage 1 of a probe that finds no records waiting
+    bool away2;             // the away search runs in two stages
+    unsigned nb2;           // ... on this many slices
+    unsigned gb, hb, rb;    // fw_xupdate_gather, fw_gemv_h, fw_rank1
+    int ns;                 // row splits of the pass over V
+    unsigned vgx;           // ... and its column blocks
+    unsigned wb;            // fw_wupdate_probe: the stage-1 records the next probe finds
+};
+static FwGrids fw_grids(int64_t m, int64_t n, int num_cu) {
+    const auto capped = [](int64_t v, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min(v, cap)); };
+    FwGrids g;
+    g.nblk = capped((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8), FW_PART_MAX);    // eight elements per thread
+    g.away2 = n >= 4096;    // (one workgroup scanning 2n doubles took 40 us of a 170 us step at n = 32768)
+    g.nb2 = std::min(g.nblk, (unsigned)AWAY_NB);
+    g.gb = capped((std::max(n, m) + FB - 1) / FB, 1024);
+    g.hb = (unsigned)(((m + 1) / 2 + FB / 64 - 1) / (FB / 64));                     // one wave per pair of rows
+    g.rb = capped(m, 4096);                                                         // a row per workgroup pass
+    g.ns = vt_nsplit(m, n, num_cu);
+    g.vgx = (unsigned)((n + VG_COLS - 1) / VG_COLS);
+    g.wb = capped((n + FB - 1) / FB, FW_PART_MAX);                                  // one record pair per workgroup
+    return g;
+}
+// the stage-1 records the last update of w left for a probe with this support threshold (0: none, run stage 1)
+static int fw_part_waiting(const accbpg_dopt* h, int away) {
+    return (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) ? h->fw_part_nblk : 0;
+}
+
+// the pinned probe record of a handle, as accbpg_fw_probe
+static void fw_read_probe(const accbpg_dopt* h, double logdet, accbpg_fw_probe* out) {
+    const int64_t* ih = fw_rec_i(h->hpin);
+    out->i = ih[0];
+    out->j = ih[1];
+    out->w_i = fw_rec_d(h->hpin)[0];
+    out->w_j = fw_rec_d(h->hpin)[1];
+    out->x_j = fw_rec_d(h->hpin)[2];
+    out->logdet_H = logdet;
+    out->q_prev = fw_rec_d(h->hpin)[6];
+}
+
+// a row of pinned step records before a run: "not reached"
+static void fw_steps_reset(accbpg_fw_step* row, int nsteps) {
+    for (int k = 0; k < nsteps; ++k) {
+        row[k] = accbpg_fw_step{};
+        row[k].p = -1;
+        row[k].kind = -1;
+        row[k].status = 3;
+    }
+}
+// ... and after it: copy the row out, count the iterations that ran, leave on the handle what a later probe finds -- the
+// stage-1 records of the last update if the run ended on one (as accbpg_fw_update leaves them); after a stop none, as
+// after accbpg_fw_probe_step (x and w are as that probe read them).  Returns the record whose pivot lay outside [0, n).
+static const accbpg_fw_step* fw_steps_harvest(accbpg_dopt* h, const accbpg_fw_step* row, int nsteps, unsigned wb,
+                                              accbpg_fw_step* out, int* nrun_host) {
+    const accbpg_fw_step* bad = nullptr;
+    int nrun = 0;
+    for (int k = 0; k < nsteps; ++k) {
+        out[k] = row[k];
+        if (row[k].status != 3) ++nrun;
+        if (row[k].status == 2 && !bad) bad = row + k;
+    }
+    *nrun_host = nrun;
+    h->fw_part_nblk = (nrun == nsteps && out[nsteps - 1].status == 0) ? (int)wb : 0;
+    return bad;
+}
 
 static int read_scalars(accbpg_dopt* h, int nd, int ni) {
     (void)nd; (void)ni;
@@ -934,41 +988,31 @@ extern "C" int accbpg_fw_probe_step(accbpg_dopt* h, int away, int refresh_logdet
         logdet = h->hpin[0];
         if (fl[FLAG_NOT_PD]) logdet = __builtin_nan("");
     }
-    double* dout = h->fw_hpin_dev + 4;
-    int64_t* iout = reinterpret_cast<int64_t*>(h->fw_hpin_dev + 8);
-    int nblk = (int)((h->n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
-    if (nblk < 1) nblk = 1;
-    if (nblk > 512) nblk = 512;
-    ValIdx* part = reinterpret_cast<ValIdx*>(h->fw_hv + 2 * h->m);      // 2*512 records behind Hv / vp
-    if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
-        nblk = h->fw_part_nblk;                                 // stage 1 came with the last update of w
-    } else {
-        fw_probe_partial_kernel<<<nblk, FB, 0, h->stream>>>(h->fw_w, h->fw_x, h->n, away, part);
+    const FwGrids g = fw_grids(h->m, h->n, h->num_cu);
+    const FwInst& t = h->fw;
+    const int64_t n = h->n;
+    ValIdx* part = fw_part_of(t, h->m);
+    int nblk = fw_part_waiting(h, away);
+    if (!nblk) {                                                // (else stage 1 came with the last update of w)
+        nblk = (int)g.nblk;
+        fw_probe_partial_kernel<<<g.nblk, FB, 0, h->stream>>>(t.w, t.x, n, away, part);
     }
     h->fw_part_nblk = 0;
     h->fw_part_away = (away != 0);
-    if (away && h->n >= 4096) {
-        ValIdx* part2 = part + 2 * 512;
-        ValIdx* mxslot = part2 + AWAY_NB;
-        int nb2 = (int)((h->n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
-        if (nb2 > AWAY_NB) nb2 = AWAY_NB;
-        fw_probe_away_partial_kernel<<<nb2, FB, 0, h->stream>>>(part, nblk, h->fw_w, h->fw_x, h->n, part2, mxslot);
-        fw_probe_away_final_kernel<<<1, FB, 0, h->stream>>>(part2, nb2, mxslot, h->fw_w, h->fw_x, h->n, dout, iout, h->dscal + 10);
+    double* dout = fw_rec_d(t.rec);
+    int64_t* iout = fw_rec_i(t.rec);
+    if (away && g.away2) {
+        ValIdx *part2 = fw_part2_of(t, h->m), *mxslot = fw_mxslot_of(t, h->m);
+        fw_probe_away_partial_kernel<<<g.nb2, FB, 0, h->stream>>>(part, nblk, t.w, t.x, n, part2, mxslot);
+        fw_probe_away_final_kernel<<<1, FB, 0, h->stream>>>(part2, (int)g.nb2, mxslot, t.w, t.x, n, dout, iout, t.q);
     } else {
-        fw_probe_final_kernel<<<1, FB, 0, h->stream>>>(part, nblk, h->fw_w, h->fw_x, h->n, away, dout, iout, h->dscal + 10);
+        fw_probe_final_kernel<<<1, FB, 0, h->stream>>>(part, nblk, t.w, t.x, n, away, dout, iout, t.q);
     }
     ACC_HIP(hipGetLastError());
     // (the final stage wrote its record straight into the pinned host buffer: the copy operation that used to follow it
     //  was 4 us of every 0.12 ms step)
     ACC_HIP(hipStreamSynchronize(h->stream));
-    const int64_t* ih = reinterpret_cast<const int64_t*>(h->hpin + 8);
-    out->i = ih[0];
-    out->j = ih[1];
-    out->w_i = h->hpin[4];
-    out->w_j = h->hpin[5];
-    out->x_j = h->hpin[6];
-    out->logdet_H = logdet;
-    out->q_prev = h->hpin[10];
+    fw_read_probe(h, logdet, out);
     return ACCBPG_OK;
 }
 
@@ -978,28 +1022,20 @@ extern "C" int accbpg_fw_update(accbpg_dopt* h, int64_t p, double xscale, double
                        (long long)p);
         return ACCBPG_ERR_ARG;
     }
+    const FwGrids g = fw_grids(h->m, h->n, h->num_cu);
+    const FwInst& t = h->fw;
     const int64_t m = h->m, n = h->n;
-    double* vp = h->fw_hv + m;
-    int64_t gb = (std::max(n, m) + FB - 1) / FB;
-    if (gb > 1024) gb = 1024;
-    fw_xupdate_gather_kernel<<<(int)gb, FB, 0, h->stream>>>(h->fw_x, n, p, xscale, xadd, h->V, h->ldv, m, vp);
-    const int64_t pairs = (m + 1) / 2;
-    fw_gemv_h_kernel<<<(int)((pairs + FB / 64 - 1) / (FB / 64)), FB, 0, h->stream>>>(h->fw_H, m, vp, h->fw_hv);
-    int64_t rb = m;
-    if (rb > 4096) rb = 4096;
-    fw_rank1_kernel<<<(int)rb, FB, 0, h->stream>>>(h->fw_H, m, h->fw_hv, hcoef, hdiv, vp, h->dscal + 10);
-    const int ns = fw_nsplit(h);
-    dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns);
+    double* vp = fw_vp_of(t, m);
+    fw_xupdate_gather_kernel<<<g.gb, FB, 0, h->stream>>>(t.x, n, p, xscale, xadd, t.V, h->ldv, m, vp);
+    fw_gemv_h_kernel<<<g.hb, FB, 0, h->stream>>>(t.H, m, vp, t.hv);
+    fw_rank1_kernel<<<g.rb, FB, 0, h->stream>>>(t.H, m, t.hv, hcoef, hdiv, vp, t.q);
     prof_begin(h, PROF_FWV);
-    fw_vgemv_partial_kernel<<<vg, FB, 0, h->stream>>>(h->V, h->ldv, m, n, h->fw_hv, ns, h->vws, h->vec_ok);
+    fw_vgemv_partial_kernel<<<dim3(g.vgx, (unsigned)g.ns), FB, 0, h->stream>>>(t.V, h->ldv, m, n, t.hv, g.ns, t.vws, h->vec_ok);
     prof_end(h, PROF_FWV);
     // w update fused with stage 1 of the next probe (same support threshold as the last probe call)
-    int64_t wb = (n + FB - 1) / FB;
-    if (wb > 512) wb = 512;                                     // 2*512 probe records behind Hv / vp
-    ValIdx* part = reinterpret_cast<ValIdx*>(h->fw_hv + 2 * h->m);
-    fw_wupdate_probe_kernel<<<(int)wb, FB, 0, h->stream>>>(h->fw_w, n, h->vws, ns, hcoef, hdiv, h->fw_x,
-                                                          h->fw_part_away ? 1 : 0, part);
-    h->fw_part_nblk = (int)wb;
+    fw_wupdate_probe_kernel<<<g.wb, FB, 0, h->stream>>>(t.w, n, t.vws, g.ns, hcoef, hdiv, t.x, h->fw_part_away ? 1 : 0,
+                                                     fw_part_of(t, m));
+    h->fw_part_nblk = (int)g.wb;
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
@@ -1011,8 +1047,7 @@ static int fw_run_alloc(accbpg_dopt* h) {
                               hipHostMallocDefault));
         ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_steps_dev), h->fw_steps_pin, 0));
     }
-    // FwRun, then a scratch probe record laid out as the pinned one (16 doubles)
-    if (!h->fw_run) ACC_HIP(hipMalloc(reinterpret_cast<void**>(&h->fw_run), sizeof(FwRun) + sizeof(double) * 16));
+    if (!h->fw_run) ACC_HIP(hipMalloc(reinterpret_cast<void**>(&h->fw_run), sizeof(FwRunSlot)));
     return ACCBPG_OK;
 }
 
@@ -1020,82 +1055,43 @@ extern "C" int accbpg_fw_run(accbpg_dopt* h, int away, double eps, int nsteps, a
                              int* nrun_host) {
     if (!h || !h->fw_ready || !steps_host || !nrun_host || nsteps < 1 || nsteps > ACCBPG_FW_RUN_MAX) return ACCBPG_ERR_ARG;
     ACC_TRY(fw_run_alloc(h));
-    const int64_t m = h->m, n = h->n;
     hipStream_t s = h->stream;
-    FwRun* run = h->fw_run;
-    double* rec = reinterpret_cast<double*>(run + 1);
-    for (int k = 0; k < nsteps; ++k) {                          // (nothing of an earlier call is in flight: it synchronised)
-        accbpg_fw_step& st = h->fw_steps_pin[k];
-        st = accbpg_fw_step{};
-        st.p = -1;
-        st.kind = -1;
-        st.status = 3;
-    }
-    ACC_HIP(hipMemsetAsync(run, 0, sizeof(FwRun), s));
-    // the grids of accbpg_fw_probe_step and accbpg_fw_update
-    ValIdx* part = reinterpret_cast<ValIdx*>(h->fw_hv + 2 * m);
-    ValIdx* part2 = part + 2 * 512;
-    ValIdx* mxslot = part2 + AWAY_NB;
-    int nblk = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
-    if (nblk < 1) nblk = 1;
-    if (nblk > 512) nblk = 512;
-    int nb2 = nblk;
-    if (nb2 > AWAY_NB) nb2 = AWAY_NB;
-    int64_t gb = (std::max(n, m) + FB - 1) / FB;
-    if (gb > 1024) gb = 1024;
-    const int64_t pairs = (m + 1) / 2;
-    const int hb = (int)((pairs + FB / 64 - 1) / (FB / 64));
-    int64_t rb = m;
-    if (rb > 4096) rb = 4096;
-    const int ns = fw_nsplit(h);
-    const dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns);
-    int64_t wb = (n + FB - 1) / FB;
-    if (wb > 512) wb = 512;
-    double* vp = h->fw_hv + m;
-    double* q = h->dscal + 10;
-    if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
-        nblk = h->fw_part_nblk;                                 // stage 1 came with the last update of w
-    } else {
-        fw_probe_partial_kernel<<<nblk, FB, 0, s>>>(h->fw_w, h->fw_x, n, away, part);
+    fw_steps_reset(h->fw_steps_pin, nsteps);                    // (nothing of an earlier call is in flight: it synchronised)
+    ACC_HIP(hipMemsetAsync(&h->fw_run->run, 0, sizeof(FwRun), s));
+    const FwGrids g = fw_grids(h->m, h->n, h->num_cu);
+    const FwInst& t = h->fw;
+    const int64_t m = h->m, n = h->n;
+    FwRun* run = &h->fw_run->run;
+    double* rec = h->fw_run->rec;
+    ValIdx *part = fw_part_of(t, m), *part2 = fw_part2_of(t, m), *mxslot = fw_mxslot_of(t, m);
+    double* vp = fw_vp_of(t, m);
+    int nblk = fw_part_waiting(h, away);
+    if (!nblk) {                                                // (else stage 1 came with the last update of w)
+        nblk = (int)g.nblk;
+        fw_probe_partial_kernel<<<g.nblk, FB, 0, s>>>(t.w, t.x, n, away, part);
     }
     h->fw_part_nblk = 0;                                        // (no claim of reuse survives an error return below)
     h->fw_part_away = (away != 0);
     for (int k = 0; k < nsteps; ++k) {
         accbpg_fw_step* out = h->fw_steps_dev + k;
-        if (away && n >= 4096) {
-            fw_probe_away_partial_run_kernel<<<nb2, FB, 0, s>>>(run, part, nblk, h->fw_w, h->fw_x, n, part2, mxslot);
-            fw_probe_away_final_run_kernel<<<1, FB, 0, s>>>(run, part2, nb2, mxslot, h->fw_w, h->fw_x, m, n, eps, rec, q, out);
+        if (away && g.away2) {
+            fw_probe_away_partial_run_kernel<<<g.nb2, FB, 0, s>>>(run, part, nblk, t.w, t.x, n, part2, mxslot);
+            fw_probe_away_final_run_kernel<<<1, FB, 0, s>>>(run, part2, (int)g.nb2, mxslot, t.w, t.x, m, n, eps, rec, t.q, out);
         } else {
-            fw_probe_final_run_kernel<<<1, FB, 0, s>>>(run, part, nblk, h->fw_w, h->fw_x, m, n, away, eps, rec, q, out);
+            fw_probe_final_run_kernel<<<1, FB, 0, s>>>(run, part, nblk, t.w, t.x, m, n, away, eps, rec, t.q, out);
         }
-        fw_xupdate_gather_run_kernel<<<(int)gb, FB, 0, s>>>(run, h->fw_x, n, h->V, h->ldv, m, vp);
-        fw_gemv_h_run_kernel<<<hb, FB, 0, s>>>(run, h->fw_H, m, vp, h->fw_hv);
-        fw_rank1_run_kernel<<<(int)rb, FB, 0, s>>>(run, h->fw_H, m, h->fw_hv, vp, q);
-        fw_vgemv_partial_run_kernel<<<vg, FB, 0, s>>>(run, h->V, h->ldv, m, n, h->fw_hv, ns, h->vws, h->vec_ok);
-        fw_wupdate_probe_run_kernel<<<(int)wb, FB, 0, s>>>(run, h->fw_w, n, h->vws, ns, h->fw_x, away ? 1 : 0, part);
-        nblk = (int)wb;                                         // the next probe's stage 1 came with this update
+        fw_xupdate_gather_run_kernel<<<g.gb, FB, 0, s>>>(run, t.x, n, t.V, h->ldv, m, vp);
+        fw_gemv_h_run_kernel<<<g.hb, FB, 0, s>>>(run, t.H, m, vp, t.hv);
+        fw_rank1_run_kernel<<<g.rb, FB, 0, s>>>(run, t.H, m, t.hv, vp, t.q);
+        fw_vgemv_partial_run_kernel<<<dim3(g.vgx, (unsigned)g.ns), FB, 0, s>>>(run, t.V, h->ldv, m, n, t.hv, g.ns, t.vws, h->vec_ok);
+        fw_wupdate_probe_run_kernel<<<g.wb, FB, 0, s>>>(run, t.w, n, t.vws, g.ns, t.x, away ? 1 : 0, part);
+        nblk = (int)g.wb;                                       // the next probe's stage 1 came with this update
     }
     ACC_HIP(hipGetLastError());
     ACC_HIP(hipStreamSynchronize(s));
-    int nrun = 0;
-    bool bad_pivot = false;
-    long long bad_p = 0;
-    for (int k = 0; k < nsteps; ++k) {
-        const accbpg_fw_step& st = h->fw_steps_pin[k];
-        steps_host[k] = st;
-        if (st.status != 3) ++nrun;
-        if (st.status == 2) {
-            bad_pivot = true;
-            bad_p = (long long)st.p;
-        }
-    }
-    *nrun_host = nrun;
-    // what a later probe finds: the stage-1 records of the last update, if the call ended on one (as accbpg_fw_update
-    // leaves them); after a stop none, as after accbpg_fw_probe_step (x and w are as that probe read them)
-    h->fw_part_nblk = (nrun == nsteps && steps_host[nsteps - 1].status == 0) ? (int)wb : 0;
-    if (bad_pivot) {
+    if (const accbpg_fw_step* bad = fw_steps_harvest(h, h->fw_steps_pin, nsteps, g.wb, steps_host, nrun_host)) {
         set_last_error("accbpg_fw_update: no Frank-Wolfe state (call accbpg_fw_init) or pivot index %lld outside [0, n)",
-                       bad_p);
+                       (long long)bad->p);
         return ACCBPG_ERR_ARG;
     }
     return ACCBPG_OK;
@@ -1121,8 +1117,7 @@ static int fw_batch_table(accbpg_dopt_batch* b) {
     for (int i = 0; i < b->K; ++i) {
         accbpg_dopt* h = b->inst[i];
         ACC_TRY(fw_alloc(h));
-        tab[i] = FwInst{h->fw_x, h->fw_w, h->fw_H, h->fw_hv, h->V, h->vws, h->dscal + 10, h->fw_hpin_dev,
-                        h->vec_ok ? 1 : 0};
+        tab[i] = h->fw;
     }
     ACC_HIP(hipMalloc(&b->fw_table, sizeof(FwInst) * (size_t)b->K));
     ACC_HIP(hipMemcpy(b->fw_table, tab.data(), sizeof(FwInst) * (size_t)b->K, hipMemcpyHostToDevice));
@@ -1150,10 +1145,9 @@ extern "C" int accbpg_dopt_batch_fw_init(accbpg_dopt_batch* b, const double* x0_
 extern "C" int accbpg_dopt_batch_fw_probe(accbpg_dopt_batch* b, int away, const int* active_host,
                                           accbpg_fw_probe* probes_host) {
     if (!b || !probes_host) return ACCBPG_ERR_ARG;
-    const int64_t m = b->inst[0]->m, n = b->inst[0]->n;
-    int nblk = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
-    if (nblk < 1) nblk = 1;
-    if (nblk > 512) nblk = 512;
+    const accbpg_dopt* h0 = b->inst[0];                         // one shape, one device: every instance's own partition
+    const FwGrids g = fw_grids(h0->m, h0->n, h0->num_cu);
+    const int64_t m = h0->m, n = h0->n;
     FwProbeArgs pa;
     BatchAct fresh;                                             // instances without stage-1 records for this threshold
     for (int i = 0; i < b->K; ++i) {
@@ -1164,25 +1158,23 @@ extern "C" int accbpg_dopt_batch_fw_probe(accbpg_dopt_batch* b, int away, const 
             return ACCBPG_ERR_ARG;
         }
         pa.idx[pa.n] = i;
-        if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
-            pa.nblk[pa.n] = h->fw_part_nblk;                    // stage 1 came with the last update of w
-        } else {
-            pa.nblk[pa.n] = nblk;
+        pa.nblk[pa.n] = fw_part_waiting(h, away);               // stage 1 came with the last update of w
+        if (!pa.nblk[pa.n]) {
+            pa.nblk[pa.n] = (int)g.nblk;
             fresh.idx[fresh.n++] = i;
         }
         ++pa.n;
     }
     if (pa.n == 0) return ACCBPG_OK;
     hipStream_t s = b->stream;
+    const unsigned na = (unsigned)pa.n;
     if (fresh.n > 0)
-        fw_probe_partial_batch_kernel<<<dim3((unsigned)nblk, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, away);
-    if (away && n >= 4096) {
-        int nb2 = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
-        if (nb2 > AWAY_NB) nb2 = AWAY_NB;
-        fw_probe_away_partial_batch_kernel<<<dim3((unsigned)nb2, (unsigned)pa.n), FB, 0, s>>>(b->fw_table, pa, m, n);
-        fw_probe_away_final_batch_kernel<<<dim3(1, (unsigned)pa.n), FB, 0, s>>>(b->fw_table, pa, nb2, m, n);
+        fw_probe_partial_batch_kernel<<<dim3(g.nblk, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, away);
+    if (away && g.away2) {
+        fw_probe_away_partial_batch_kernel<<<dim3(g.nb2, na), FB, 0, s>>>(b->fw_table, pa, m, n);
+        fw_probe_away_final_batch_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, pa, (int)g.nb2, m, n);
     } else {
-        fw_probe_final_batch_kernel<<<dim3(1, (unsigned)pa.n), FB, 0, s>>>(b->fw_table, pa, m, n, away);
+        fw_probe_final_batch_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, pa, m, n, away);
     }
     ACC_HIP(hipGetLastError());
     ACC_HIP(hipStreamSynchronize(s));                           // every record is in its instance's pinned buffer
@@ -1190,15 +1182,7 @@ extern "C" int accbpg_dopt_batch_fw_probe(accbpg_dopt_batch* b, int away, const 
         accbpg_dopt* h = b->inst[pa.idx[a]];
         h->fw_part_nblk = 0;
         h->fw_part_away = (away != 0);
-        const int64_t* ih = reinterpret_cast<const int64_t*>(h->hpin + 8);
-        accbpg_fw_probe* out = probes_host + pa.idx[a];
-        out->i = ih[0];
-        out->j = ih[1];
-        out->w_i = h->hpin[4];
-        out->w_j = h->hpin[5];
-        out->x_j = h->hpin[6];
-        out->logdet_H = __builtin_nan("");
-        out->q_prev = h->hpin[10];
+        fw_read_probe(h, __builtin_nan(""), probes_host + pa.idx[a]);
     }
     return ACCBPG_OK;
 }
@@ -1207,7 +1191,8 @@ extern "C" int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* acti
                                            const double* xscale_host, const double* xadd_host,
                                            const double* hcoef_host, const double* hdiv_host) {
     if (!b || !p_host || !xscale_host || !xadd_host || !hcoef_host || !hdiv_host) return ACCBPG_ERR_ARG;
-    const int64_t m = b->inst[0]->m, n = b->inst[0]->n, ldv = b->inst[0]->ldv;
+    accbpg_dopt* h0 = b->inst[0];                               // one shape, one device: every instance's own partition
+    const int64_t m = h0->m, n = h0->n, ldv = h0->ldv;
     FwUpdArgs ua;
     BatchAct act;
     for (int i = 0; i < b->K; ++i) {
@@ -1229,26 +1214,17 @@ extern "C" int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* acti
         act.idx[act.n++] = i;
     }
     if (ua.n == 0) return ACCBPG_OK;
+    const FwGrids g = fw_grids(h0->m, h0->n, h0->num_cu);
     const unsigned na = (unsigned)ua.n;
     hipStream_t s = b->stream;
-    accbpg_dopt* h0 = b->inst[0];
-    int64_t gb = (std::max(n, m) + FB - 1) / FB;
-    if (gb > 1024) gb = 1024;
-    fw_xupdate_gather_batch_kernel<<<dim3((unsigned)gb, na), FB, 0, s>>>(b->fw_table, ua, m, n, ldv);
-    const int64_t pairs = (m + 1) / 2;
-    fw_gemv_h_batch_kernel<<<dim3((unsigned)((pairs + FB / 64 - 1) / (FB / 64)), na), FB, 0, s>>>(b->fw_table, act, m);
-    int64_t rb = m;
-    if (rb > 4096) rb = 4096;
-    fw_rank1_batch_kernel<<<dim3((unsigned)rb, na), FB, 0, s>>>(b->fw_table, ua, m);
-    const int ns = fw_nsplit(h0);                               // one shape, one device: every instance's own partition
-    dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns, na);
+    fw_xupdate_gather_batch_kernel<<<dim3(g.gb, na), FB, 0, s>>>(b->fw_table, ua, m, n, ldv);
+    fw_gemv_h_batch_kernel<<<dim3(g.hb, na), FB, 0, s>>>(b->fw_table, act, m);
+    fw_rank1_batch_kernel<<<dim3(g.rb, na), FB, 0, s>>>(b->fw_table, ua, m);
     prof_begin(h0, PROF_FWV);
-    fw_vgemv_partial_batch_kernel<<<vg, FB, 0, s>>>(b->fw_table, act, ldv, m, n, ns);
+    fw_vgemv_partial_batch_kernel<<<dim3(g.vgx, (unsigned)g.ns, na), FB, 0, s>>>(b->fw_table, act, ldv, m, n, g.ns);
     prof_end(h0, PROF_FWV);
-    int64_t wb = (n + FB - 1) / FB;
-    if (wb > 512) wb = 512;                                     // 2*512 probe records behind Hv / vp
-    fw_wupdate_probe_batch_kernel<<<dim3((unsigned)wb, na), FB, 0, s>>>(b->fw_table, ua, m, n, ns);
-    for (int a = 0; a < ua.n; ++a) b->inst[ua.idx[a]]->fw_part_nblk = (int)wb;
+    fw_wupdate_probe_batch_kernel<<<dim3(g.wb, na), FB, 0, s>>>(b->fw_table, ua, m, n, g.ns);
+    for (int a = 0; a < ua.n; ++a) b->inst[ua.idx[a]]->fw_part_nblk = (int)g.wb;
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
@@ -1267,10 +1243,9 @@ static int fw_batch_run_alloc(accbpg_dopt_batch* b) {
 extern "C" int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const double* eps_host, int nsteps,
                                         const int* active_host, accbpg_fw_step* steps_host, int* nrun_host) {
     if (!b || !eps_host || !steps_host || !nrun_host || nsteps < 1 || nsteps > ACCBPG_FW_RUN_MAX) return ACCBPG_ERR_ARG;
-    const int64_t m = b->inst[0]->m, n = b->inst[0]->n, ldv = b->inst[0]->ldv;
-    int nblk0 = (int)((n + (int64_t)FB * 8 - 1) / ((int64_t)FB * 8));
-    if (nblk0 < 1) nblk0 = 1;
-    if (nblk0 > 512) nblk0 = 512;
+    const accbpg_dopt* h0 = b->inst[0];                         // one shape, one device: every instance's own partition
+    const FwGrids g = fw_grids(h0->m, h0->n, h0->num_cu);
+    const int64_t m = h0->m, n = h0->n, ldv = h0->ldv;
     FwProbeArgs pa;                                             // the active set, and each instance's nblk at iteration 0
     BatchAct act, fresh;
     ::BatchVals eps;
@@ -1285,10 +1260,9 @@ extern "C" int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const do
         pa.idx[a] = i;
         act.idx[act.n++] = i;
         eps.v[a] = eps_host[i];
-        if (h->fw_part_nblk > 0 && h->fw_part_away == (away != 0)) {
-            pa.nblk[a] = h->fw_part_nblk;                       // stage 1 came with the last update of w
-        } else {
-            pa.nblk[a] = nblk0;
+        pa.nblk[a] = fw_part_waiting(h, away);                  // stage 1 came with the last update of w
+        if (!pa.nblk[a]) {
+            pa.nblk[a] = (int)g.nblk;
             fresh.idx[fresh.n++] = i;
         }
     }
@@ -1297,49 +1271,29 @@ extern "C" int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const do
     const unsigned na = (unsigned)pa.n;
     hipStream_t s = b->stream;
     for (int a = 0; a < pa.n; ++a) {                            // (nothing of an earlier call is in flight: it synchronised)
-        accbpg_fw_step* row = b->fw_bsteps_pin + (size_t)pa.idx[a] * ACCBPG_FW_RUN_MAX;
-        for (int k = 0; k < nsteps; ++k) {
-            row[k] = accbpg_fw_step{};
-            row[k].p = -1;
-            row[k].kind = -1;
-            row[k].status = 3;
-        }
+        fw_steps_reset(b->fw_bsteps_pin + (size_t)pa.idx[a] * ACCBPG_FW_RUN_MAX, nsteps);
         b->inst[pa.idx[a]]->fw_part_nblk = 0;                   // (no claim of reuse survives an error return below)
         b->inst[pa.idx[a]]->fw_part_away = (away != 0);
     }
     ACC_HIP(hipMemsetAsync(b->fw_runs, 0, sizeof(FwRunSlot) * (size_t)b->K, s));
-    // the grids of accbpg_fw_run, times the active instances
-    int nb2 = nblk0;
-    if (nb2 > AWAY_NB) nb2 = AWAY_NB;
-    int64_t gb = (std::max(n, m) + FB - 1) / FB;
-    if (gb > 1024) gb = 1024;
-    const int64_t pairs = (m + 1) / 2;
-    const unsigned hb = (unsigned)((pairs + FB / 64 - 1) / (FB / 64));
-    int64_t rb = m;
-    if (rb > 4096) rb = 4096;
-    const int ns = fw_nsplit(b->inst[0]);                       // one shape, one device: every instance's own partition
-    const dim3 vg((unsigned)((n + VG_COLS - 1) / VG_COLS), (unsigned)ns, na);
-    int64_t wb = (n + FB - 1) / FB;
-    if (wb > 512) wb = 512;
     if (fresh.n > 0)
-        fw_probe_partial_batch_kernel<<<dim3((unsigned)nblk0, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, away);
+        fw_probe_partial_batch_kernel<<<dim3(g.nblk, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, away);
     for (int k = 0; k < nsteps; ++k) {
-        if (away && n >= 4096) {
-            fw_probe_away_partial_brun_kernel<<<dim3((unsigned)nb2, na), FB, 0, s>>>(b->fw_table, b->fw_runs, pa, m, n);
-            fw_probe_away_final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, eps, nb2, m, n,
+        if (away && g.away2) {
+            fw_probe_away_partial_brun_kernel<<<dim3(g.nb2, na), FB, 0, s>>>(b->fw_table, b->fw_runs, pa, m, n);
+            fw_probe_away_final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, eps, (int)g.nb2, m, n,
                                                                        b->fw_bsteps_dev, k);
         } else {
             fw_probe_final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, b->fw_runs, pa, eps, m, n, away,
                                                                   b->fw_bsteps_dev, k);
         }
-        fw_xupdate_gather_brun_kernel<<<dim3((unsigned)gb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m, n, ldv);
-        fw_gemv_h_brun_kernel<<<dim3(hb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m);
-        fw_rank1_brun_kernel<<<dim3((unsigned)rb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m);
-        fw_vgemv_partial_brun_kernel<<<vg, FB, 0, s>>>(b->fw_table, b->fw_runs, act, ldv, m, n, ns);
-        fw_wupdate_probe_brun_kernel<<<dim3((unsigned)wb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m, n, ns,
-                                                                          away ? 1 : 0);
+        fw_xupdate_gather_brun_kernel<<<dim3(g.gb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m, n, ldv);
+        fw_gemv_h_brun_kernel<<<dim3(g.hb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m);
+        fw_rank1_brun_kernel<<<dim3(g.rb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m);
+        fw_vgemv_partial_brun_kernel<<<dim3(g.vgx, (unsigned)g.ns, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, ldv, m, n, g.ns);
+        fw_wupdate_probe_brun_kernel<<<dim3(g.wb, na), FB, 0, s>>>(b->fw_table, b->fw_runs, act, m, n, g.ns, away ? 1 : 0);
         if (k == 0)
-            for (int a = 0; a < pa.n; ++a) pa.nblk[a] = (int)wb;     // the next probe's stage 1 came with this update
+            for (int a = 0; a < pa.n; ++a) pa.nblk[a] = (int)g.wb;   // the next probe's stage 1 came with this update
     }
     const hipError_t launched = hipGetLastError();
     ACC_HIP(hipStreamSynchronize(s));                           // (also behind a launch error: nothing stays in flight)
@@ -1348,20 +1302,12 @@ extern "C" int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const do
     long long bad_p = 0;
     for (int a = 0; a < act.n; ++a) {
         const int i = act.idx[a];
-        const accbpg_fw_step* row = b->fw_bsteps_pin + (size_t)i * ACCBPG_FW_RUN_MAX;
-        accbpg_fw_step* out = steps_host + (size_t)i * nsteps;
-        int nrun = 0;
-        for (int k = 0; k < nsteps; ++k) {
-            out[k] = row[k];
-            if (row[k].status != 3) ++nrun;
-            if (row[k].status == 2 && bad_inst < 0) {
-                bad_inst = i;
-                bad_p = (long long)row[k].p;
-            }
+        const accbpg_fw_step* bad = fw_steps_harvest(b->inst[i], b->fw_bsteps_pin + (size_t)i * ACCBPG_FW_RUN_MAX, nsteps,
+                                                     g.wb, steps_host + (size_t)i * nsteps, nrun_host + i);
+        if (bad && bad_inst < 0) {
+            bad_inst = i;
+            bad_p = (long long)bad->p;
         }
-        nrun_host[i] = nrun;
-        // what a later probe of this instance finds: as accbpg_fw_run leaves it on the handle
-        b->inst[i]->fw_part_nblk = (nrun == nsteps && out[nsteps - 1].status == 0) ? (int)wb : 0;
     }
     if (bad_inst >= 0) {
         set_last_error("accbpg_dopt_batch_fw_run: instance %d: pivot index %lld outside [0, n)", bad_inst, bad_p);

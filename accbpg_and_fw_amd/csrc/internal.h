@@ -75,7 +75,8 @@ struct BatchInst {
     int* chol_ready;
 };
 
-// Frank-Wolfe state of one instance as the lock-step step kernels (fw_kernels.hip) address it
+// Frank-Wolfe state of one instance as the step kernels (fw_kernels.hip) address it: the handle keeps its own
+// (accbpg_dopt::fw, filled where the buffers are made), a batch keeps a device table of its instances
 struct FwInst {
     double* x;              // fw_x
     double* w;              // fw_w
@@ -87,6 +88,25 @@ struct FwInst {
     double* rec;            // the instance's pinned host record, as the device addresses it
     int64_t vec_ok;         // V rows are 16-byte aligned
 };
+// What lies behind FwInst::hv: Hv (m doubles), vp (m), 2 * FW_PART_MAX stage-1 probe records (the maximum and the masked
+// minimum of each block), then, for the two-stage away search, AWAY_NB stage-2 records and (w_i, i).  Every kernel and
+// the allocation go through these.
+struct ValIdx {
+    double v;
+    int64_t i;
+};
+constexpr int FW_PART_MAX = 512;    // at most this many workgroups write stage-1 records
+constexpr int AWAY_NB = 128;        // at most this many slices of the away variant's second stage
+__host__ __device__ inline double* fw_vp_of(const FwInst& t, int64_t m) { return t.hv + m; }
+__host__ __device__ inline ValIdx* fw_part_of(const FwInst& t, int64_t m) { return reinterpret_cast<ValIdx*>(t.hv + 2 * m); }
+__host__ __device__ inline ValIdx* fw_part2_of(const FwInst& t, int64_t m) { return fw_part_of(t, m) + 2 * FW_PART_MAX; }
+__host__ __device__ inline ValIdx* fw_mxslot_of(const FwInst& t, int64_t m) { return fw_part2_of(t, m) + AWAY_NB; }
+constexpr size_t fw_scratch_doubles(int64_t m) { return (size_t)(2 * m + 2 * (2 * FW_PART_MAX) + 16 + 2 * AWAY_NB + 4); }
+// A probe record (the pinned host record, or the scratch one of a device-decided run) holds w_i, w_j, x_j in doubles
+// 4..6, q of the last update in double 10, and i, j as two 64-bit integers at double 8: dout / iout of the final stage
+__host__ __device__ inline double* fw_rec_d(double* rec) { return rec + 4; }
+__host__ __device__ inline int64_t* fw_rec_i(double* rec) { return reinterpret_cast<int64_t*>(rec + 8); }
+
 struct FwProbeArgs {        // active instances of a probe and the stage-1 records each has waiting
     int n = 0;
     int idx[BATCH_MAX] = {};
@@ -128,8 +148,7 @@ struct FwRun {
 };
 
 // The same for one instance of a batch (accbpg_dopt_batch_fw_run): the batch owns K of these, entry i = instance i.  rec
-// is the scratch probe record of the final stage, laid out as the pinned one.  The lock-step kernels (FwInst) never
-// see them.
+// is the scratch probe record of the final stage, laid out as the pinned one.  A single handle's accbpg_fw_run owns one.
 struct FwRunSlot {
     FwRun run;
     double rec[16];
@@ -215,6 +234,7 @@ struct accbpg_dopt {
     // Frank-Wolfe state
     double *fw_x = nullptr, *fw_w = nullptr, *fw_H = nullptr, *fw_hv = nullptr;
     double* fw_hpin_dev = nullptr;  // device address of the pinned host record hpin (the probe's final stage writes there)
+    accbpg::FwInst fw{};            // the above as the step kernels address them (filled by the allocation)
     bool fw_ready = false;
     // log det(H) of the away-step variant (D_opt_alg.py:136) factored beside the steps: a ring of snapshot slots, each an
     // auxiliary handle (own buffers, own stream) that factors a copy of H_k while the main stream goes on
@@ -233,7 +253,7 @@ struct accbpg_dopt {
     bool fw_part_away = false;  // support threshold they were computed for
     // accbpg_fw_run: the step's scalars and a scratch probe record on the device, the records of a call in pinned host
     // memory (allocated by the first call, freed with the handle)
-    accbpg::FwRun* fw_run = nullptr;
+    accbpg::FwRunSlot* fw_run = nullptr;
     accbpg_fw_step* fw_steps_pin = nullptr;     // ACCBPG_FW_RUN_MAX records
     accbpg_fw_step* fw_steps_dev = nullptr;     // ... as the device addresses them
 

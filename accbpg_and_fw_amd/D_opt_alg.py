@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .functions import DOptimalObj, _ptr, _stream, from_dev, to_dev
+from .algorithms_fw import _SLOPE_FLOOR, _check_options, _step_length
+from .functions import DOptimalObj, _ptr, _stream, from_dev, to_dev, vec_axpby, vec_vertex
 
 
 class _FWState:
@@ -734,3 +735,208 @@ def _away_batch_device_steps(batch, logdet, epsv, maxitrs, sync_every, logdet_re
         F, SP, SN, T = runs[i].finish(lambda i=i: batch.fw_logdet_flush(i))
         out.append((batch.fw_x(i, as_numpy), F.copy(), SP.copy(), SN.copy(), T.copy()))
     return out
+
+
+# ---- Frank-Wolfe with a Bregman step on the maintained state ------------------------------------------
+# FW_alg_div_step / FW_alg_descent_step (algorithms_fw.py) on the D-optimal objective with the Burg kernel and the
+# simplex LMO, without an O(m^2 n) evaluation per iteration or per line-search trial: the gradient is -w, the step
+# x+ = x + a (s - x) towards s = fill + (radius - fill) e_i is a scaling plus a rank-one change of the Gram matrix, and
+# every trial value follows from the matrix determinant lemma in host scalars.
+_LMO_FILL = 1e-15       # lmo_simplex's entry away from the vertex (functions_lmo.py)
+REFRESH_DEFAULT = 256   # steps between two re-initialisations of (H, w, log det) from x
+
+
+class _FWDivState(_FWState):
+    """The Frank-Wolfe state plus what the Bregman-step solvers keep beside it: ``ld`` the log det of the tracked Gram
+    matrix, ``q`` the floor mass not in it, ``since`` the steps since the last initialisation."""
+
+    def __init__(self, f, x0, radius, refresh):
+        super().__init__(f, x0)
+        self.radius = float(radius)
+        self.refresh = int(refresh)
+        self.ld, self.q, self.since = self.logdet_gram, 0.0, 0
+
+    def x_dev(self):
+        out = torch.empty(self.n, dtype=torch.float64, device=self.obj.device)
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_get_state(self.h, _ptr(out), None, None)
+        _lib.check(rc, "accbpg_fw_get_state")
+        return out
+
+    def x(self):
+        return from_dev(self.x_dev(), self.as_numpy)
+
+    def reinit(self, xd):
+        """(H, w, log det) afresh from the device vector xd; a singular Gram matrix is DOptimalObj's ValueError."""
+        logdet = C.c_double(0.0)
+        with torch.cuda.device(self.obj.device):
+            self.lib.accbpg_dopt_set_stream(self.h, _stream())
+            rc = self.lib.accbpg_fw_init(self.h, _ptr(xd), C.byref(logdet))
+        _lib.check(rc, "accbpg_fw_init")
+        self.ld, self.q, self.since = logdet.value, 0.0, 0
+
+    def refresh_if_due(self):
+        if self.refresh and self.since == self.refresh:
+            self.reinit(self.x_dev())
+
+    def probe_div(self):
+        rec = _lib.FwDivProbe()
+        if self._on_device():
+            rc = self.lib.accbpg_fw_div_probe_step(self.h, _LMO_FILL, self.radius, C.byref(rec))
+        else:
+            with torch.cuda.device(self.obj.device):
+                rc = self.lib.accbpg_fw_div_probe_step(self.h, _LMO_FILL, self.radius, C.byref(rec))
+        if rc:
+            _lib.check(rc, "accbpg_fw_div_probe_step")
+        return rec
+
+    def value(self, rec):
+        """f(x) = -log det(V X V^T): the tracked part, and the dense floor term q V V^T to first order (tr(H V V^T) =
+        sum w)."""
+        return -self.ld - self.q * rec.sum_w
+
+    def scalars(self, a, rec):
+        """(hcoef, hdiv, ld1, q1, f1) of a step of length a < 1 towards the vertex of ``rec``."""
+        fill = _LMO_FILL
+        tau = a * (self.radius - fill) / (1 - a)
+        den = 1 + tau * rec.w_i
+        hcoef = -tau / den
+        hdiv = 1 - a
+        ld1 = self.ld + self.m * math.log(hdiv) + math.log(den)
+        q1 = self.q + a * (fill - self.q)
+        sw1 = (rec.sum_w + hcoef * rec.sum_u2) / hdiv
+        f1 = -ld1 - q1 * sw1
+        return hcoef, hdiv, ld1, q1, f1
+
+    def apply(self, rec, a, hcoef, hdiv, ld1, q1):
+        if self._on_device():
+            rc = self.lib.accbpg_fw_div_apply(self.h, rec.i, a, _LMO_FILL, self.radius, hcoef, hdiv)
+        else:
+            with torch.cuda.device(self.obj.device):
+                rc = self.lib.accbpg_fw_div_apply(self.h, rec.i, a, _LMO_FILL, self.radius, hcoef, hdiv)
+        if rc:
+            _lib.check(rc, "accbpg_fw_div_apply")
+        self.ld, self.q = ld1, q1
+        self.since += 1
+
+    def full_step(self, rec):
+        """x + 1.0 * (s - x) with the vector kernels of the generic solver (the capped step a == 1)."""
+        xd = self.x_dev()
+        vertex = vec_vertex(rec.i, self.radius, _LMO_FILL, self.n, xd.device)
+        towards = vec_axpby(1.0, vertex, -1.0, xd)
+        return vec_axpby(1.0, xd, 1.0, towards)
+
+
+def D_opt_FW_div_step(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2,
+                      verbose=True, verbskip=1, radius=1, refresh=REFRESH_DEFAULT):
+    """FW_alg_div_step(f, BurgEntropy(), L, x0, maxitrs, gamma, lmo_simplex(radius), ...) on the D-optimal objective
+    at O(mn) per iteration: the state of D_opt_FW (H, w) is kept by rank-one updates, the gradient is -w and every
+    line-search trial is a few host scalars.  ``f`` is a matrix or a DOptimalObj.  ``refresh``: the state
+    is recomputed from x every that many steps (0: never).  Returns (x, F, Ls, T)."""
+    return _drain(D_opt_FW_div_step_steps(f, L, x0, maxitrs, gamma, epsilon, linesearch, ls_ratio, verbose, verbskip,
+                                          radius, refresh))
+
+
+def D_opt_FW_div_step_steps(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2,
+                            verbose=True, verbskip=1, radius=1, refresh=REFRESH_DEFAULT):
+    """Generator form: yields k after each outer iteration, returns D_opt_FW_div_step's tuple."""
+    _check_options(L, epsilon, ls_ratio)
+    if verbose:
+        print("\nFW adaptive algorithm")
+        print("     k      F(x)         Lk       time")
+
+    t_start = time.time()
+    F = np.zeros(maxitrs)
+    Ls = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+
+    st = _FWDivState(f, x0, radius, refresh)
+    done = 0
+    for k in range(maxitrs):
+        st.refresh_if_due()
+        rec = st.probe_div()
+        fx = st.value(rec)
+        F[k] = fx
+        T[k] = time.time() - t_start
+
+        div = rec.div if rec.div != 0 else _SLOPE_FLOOR
+        slope = rec.slope
+        if 0 < slope <= _SLOPE_FLOOR:
+            slope = 0.0
+        if slope > 0:
+            raise ValueError("grad_d_prod must be non-positive")
+        assert rec.min_x > 0, "Entries of x or y not positive."
+
+        if linesearch:
+            L = L / ls_ratio
+        while True:
+            a = _step_length(slope, L, div, gamma)
+            trial = None
+            if a < 1:
+                hcoef, hdiv, ld1, q1, f1 = st.scalars(a, rec)
+            else:                                               # the cap: a full evaluation, as the generic solver's
+                trial = st.full_step(rec)
+                f1 = st.obj.func_grad(trial, flag=0) if linesearch else None
+            if not linesearch:
+                break
+            assert not math.isinf(L), "L is infinite"
+            if f1 <= fx + a * slope + a ** gamma * L * div:
+                break
+            L = L * ls_ratio
+
+        if trial is None:
+            st.apply(rec, a, hcoef, hdiv, ld1, q1)
+        else:
+            st.reinit(trial)
+        Ls[k] = L
+        done = k + 1
+        if verbose and k % verbskip == 0:
+            print(f"{k:6d}  {F[k]:10.3e}  {L:10.3e}  {T[k]:6.1f}")
+        if k > 0 and abs(F[k] - F[k - 1]) < epsilon:
+            break
+        yield k
+
+    return st.x(), F[:done], Ls[:done], T[:done]
+
+
+def D_opt_FW_descent_step(f, x0, maxitrs, epsilon=1e-14, verbose=True, verbskip=1, radius=1, refresh=REFRESH_DEFAULT):
+    """FW_alg_descent_step(f, BurgEntropy(), x0, maxitrs, lmo_simplex(radius), ...) on the D-optimal objective at
+    O(mn) per iteration, on the state of D_opt_FW_div_step.  Returns (x, F, T, G) with G all zeros."""
+    return _drain(D_opt_FW_descent_step_steps(f, x0, maxitrs, epsilon, verbose, verbskip, radius, refresh))
+
+
+def D_opt_FW_descent_step_steps(f, x0, maxitrs, epsilon=1e-14, verbose=True, verbskip=1, radius=1,
+                                refresh=REFRESH_DEFAULT):
+    """Generator form: yields k after each iteration, returns D_opt_FW_descent_step's tuple."""
+    if verbose:
+        print("\nFW descent step size algorithm")
+        print("     k      F(x)         alpha_k       time")
+
+    t_start = time.time()
+    F = np.zeros(maxitrs)
+    G = np.zeros(maxitrs)
+    T = np.zeros(maxitrs)
+
+    st = _FWDivState(f, x0, radius, refresh)
+    rec = st.probe_div()
+    F[0] = st.value(rec)
+    T[0] = time.time() - t_start
+
+    k = 0
+    for k in range(1, maxitrs):
+        alpha = 2 / (k + 2)
+        hcoef, hdiv, ld1, q1, _ = st.scalars(alpha, rec)
+        st.apply(rec, alpha, hcoef, hdiv, ld1, q1)
+        st.refresh_if_due()
+        rec = st.probe_div()
+        F[k] = st.value(rec)
+        T[k] = time.time() - t_start
+
+        if verbose and (k % verbskip == 0 or k == 1):
+            print(f"{k:6d}  {F[k]:10.3e}  {alpha:10.3e}  {T[k]:6.1f}")
+
+        if abs(F[k] - F[k - 1]) < epsilon or math.sqrt(rec.sum_w2) < epsilon:
+            break
+        yield k
+
+    return st.x(), F[:k + 1], T[:k + 1], G[:k + 1]

@@ -24,6 +24,13 @@ class FwProbe(C.Structure):
                 ("x_j", C.c_double), ("logdet_H", C.c_double), ("q_prev", C.c_double)]
 
 
+class FwDivProbe(C.Structure):
+    """The record of accbpg_fw_div_probe_step (accbpg_fw_div_probe)."""
+    _fields_ = [("i", C.c_int64), ("w_i", C.c_double), ("x_i", C.c_double), ("sum_w", C.c_double),
+                ("sum_w2", C.c_double), ("slope", C.c_double), ("div", C.c_double), ("min_x", C.c_double),
+                ("sum_u2", C.c_double)]
+
+
 class FwStep(C.Structure):
     """One record of accbpg_fw_run: the probe record, the update the device applied, and what became of the step."""
     _fields_ = [("i", C.c_int64), ("j", C.c_int64), ("w_i", C.c_double), ("w_j", C.c_double), ("x_j", C.c_double),
@@ -100,6 +107,8 @@ _SIGS = {
     "accbpg_fw_logdet_pending": (C.c_int, [_P]),
     "accbpg_fw_update": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double]),
     "accbpg_fw_get_state": (C.c_int, [_P, _P, _P, _P]),
+    "accbpg_fw_div_probe_step": (C.c_int, [_P, C.c_double, C.c_double, C.POINTER(FwDivProbe)]),
+    "accbpg_fw_div_apply": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "accbpg_fw_logdet_snapshot": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "accbpg_fw_run": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, C.POINTER(FwStep), C.POINTER(C.c_int)]),
     "accbpg_dopt_batch_fw_init": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_double),

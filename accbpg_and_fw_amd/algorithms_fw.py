@@ -38,7 +38,11 @@ def FW_alg_div_step(f, h, L, x0, maxitrs, gamma, lmo, epsilon=1e-14, linesearch=
                     verbose=True, verbskip=1):
     """Returns (x, F, Ls, T).  Each iteration moves from x towards the vertex s = lmo(grad f(x)) by
     the step length above; with `linesearch` the constant L is first divided by ls_ratio and then
-    multiplied back until f(x+) <= f(x) + a*slope + a^gamma * L * D(s, x)."""
+    multiplied back until f(x+) <= f(x) + a*slope + a^gamma * L * D(s, x).
+
+    On the D-optimal objective with the Burg kernel and ``lmo_simplex``, ``D_opt_FW_div_step`` (D_opt_alg.py) runs the
+    same iteration at O(mn) per step on rank-one updates of the inverse Gram matrix; this function does not dispatch to
+    it."""
     return _drain(FW_alg_div_step_steps(f, h, L, x0, maxitrs, gamma, lmo, epsilon, linesearch, ls_ratio,
                                         verbose, verbskip))
 
@@ -100,7 +104,10 @@ def FW_alg_div_step_steps(f, h, L, x0, maxitrs, gamma, lmo, epsilon=1e-14, lines
 def FW_alg_descent_step(f, h, x0, maxitrs, lmo, epsilon=1e-14, verbose=True, verbskip=1):
     """Returns (x, F, T, G) with G all zeros, as the reference does.  Iteration k >= 1 moves x by 2/(k+2) towards
     s = lmo(grad f(x)) and stops on |F[k] - F[k-1]| < epsilon or ||grad f(x)|| < epsilon.  With maxitrs = 1 the
-    reference fails (UnboundLocalError on k); this returns the single evaluation at x0."""
+    reference fails (UnboundLocalError on k); this returns the single evaluation at x0.
+
+    On the D-optimal objective with ``lmo_simplex``, ``D_opt_FW_descent_step`` (D_opt_alg.py) runs the same iteration at
+    O(mn) per step; this function does not dispatch to it."""
     return _drain(FW_alg_descent_step_steps(f, h, x0, maxitrs, lmo, epsilon, verbose, verbskip))
 
 

@@ -113,6 +113,8 @@ extern "C" int accbpg_dopt_destroy(accbpg_dopt* h) {
     hipFree(h->chol_jobs); hipFree(h->chol_ready); hipFree(h->chol_aux); hipFree(h->chol_hand); hipFree(h->Gbuf);
     hipFree(h->fw_run);
     if (h->fw_steps_pin) hipHostFree(h->fw_steps_pin);
+    hipFree(h->fw_div_ws);
+    if (h->fw_div_pin) hipHostFree(h->fw_div_pin);
     if (h->hpin) hipHostFree(h->hpin);
     if (h->ev_done) hipEventDestroy(h->ev_done);
     for (auto& sl : h->fw_ring) {

@@ -690,6 +690,90 @@ __global__ __launch_bounds__(FB) void vt_usum_batch_kernel(const KyInst* __restr
     const KyInst t = tab[blockIdx.y];
     fw_usum_body(t.vws, nsplit, n, t.w);
 }
+// ---- the Bregman-step Frank-Wolfe probe (accbpg_fw_div_probe_step / accbpg_fw_div_apply) --------------------------
+// FW_alg_div_step / FW_alg_descent_step on the D-optimal objective with the simplex LMO (algorithms_fw.py:6-75,
+// :210-247; functions_lmo.py:137-160): the gradient is -w, the vertex is s = fill everywhere and `value` at the first
+// argmax of w, and everything the host needs for an iteration is a handful of sums over w and x.  The sums and the
+// minimum run over the fixed tree of reduce.hpp on red_blocks(n, FW_DIV_CAP) workgroups.
+//
+// Stage 2 of the probe (stage 1 is the first-index argmax records of fw_probe_partial / fw_wupdate_probe): every
+// workgroup combines the stage-1 maxima itself (at most FW_PART_MAX records: the same i everywhere), then folds its
+// entries.  Per entry, each operation rounded once, written as the generic path writes them (vec_kernels.hip,
+// ls_terms_partial_body with g = -w, x = s, y = x):
+//   sum_w += w;  sum_w2 += w*w;  slope += (-w) * (s - x);  div += s/x - log(s/x) - 1;  min_x = min_nan(min_x, x)
+__global__ __launch_bounds__(FB) void fw_div_probe_partial_kernel(const ValIdx* __restrict__ part, int nblk,
+                                                                 const double* __restrict__ w,
+                                                                 const double* __restrict__ x, int64_t n, double fill,
+                                                                 double value, double* __restrict__ rec,
+                                                                 ValIdx* __restrict__ mxslot) {
+    __shared__ ValIdx sh[FB / 64];
+    const double inf = __builtin_inf();
+    ValIdx best{-inf, INT64_MAX};
+    for (int b = threadIdx.x; b < nblk; b += FB) best = better_max(best, part[2 * b]);
+    const ValIdx mx = block_reduce_vi_n<true, FB>(best, sh);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, mn = inf;
+    const int64_t stride = (int64_t)gridDim.x * FB;
+    for (int64_t k = (int64_t)blockIdx.x * FB + threadIdx.x; k < n; k += stride) {
+        const double wk = w[k], xk = x[k];
+        const double sk = (k == mx.i) ? value : fill;
+        s0 += wk;
+        s1 += wk * wk;
+        const double d = sk - xk;
+        s2 += (-wk) * d;
+        const double r = sk / xk;
+        s3 += r - log(r) - 1.0;
+        mn = min_nan(mn, xk);
+    }
+    double v[5] = {s0, s1, s2, s3, mn};
+    block_reduce_store<FB, 5, true>(v, rec + (int64_t)blockIdx.x * 5);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *mxslot = mx;
+}
+// final stage: the block records in block order into doubles 3..7 of the pinned record, (i, w_i, x_i) in front of them,
+// and vp <- V[:,i] with i as it stands in device memory (no host round trip between the probe and the direction)
+__global__ __launch_bounds__(FB) void fw_div_probe_final_kernel(const double* __restrict__ rec, int nb,
+                                                               const ValIdx* __restrict__ mxslot,
+                                                               const double* __restrict__ x, int64_t n,
+                                                               const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                               double* __restrict__ vp, double* __restrict__ pin) {
+    reduce_final_body<FB, 5, true>(rec, nb, pin + 3);
+    const ValIdx mx = *mxslot;
+    const int64_t i = mx.i;
+    const bool ok = i >= 0 && i < n;
+    if (threadIdx.x == 0) {
+        reinterpret_cast<int64_t*>(pin)[0] = i;
+        pin[1] = mx.v;
+        pin[2] = ok ? x[i] : __builtin_nan("");
+    }
+    if (ok)
+        for (int64_t r = threadIdx.x; r < m; r += FB) vp[r] = V[r * ldv + i];
+}
+// u = sum of the row-split partials, as fw_wupdate sums them, kept for the apply; sum u^2 over the tree
+__global__ __launch_bounds__(FB) void fw_div_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
+                                                        double* __restrict__ u, double* __restrict__ u2part) {
+    double acc = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * FB;
+    for (int64_t k = (int64_t)blockIdx.x * FB + threadIdx.x; k < n; k += stride) {
+        double a = 0.0;
+        for (int s = 0; s < nsplit; ++s) a += upart[(int64_t)s * n + k];
+        u[k] = a;
+        acc += a * a;
+    }
+    double v[1] = {acc};
+    block_reduce_store<FB, 1, false>(v, u2part + blockIdx.x);
+}
+// x <- x + a*(s - x) with the vertex implicit: the bits of vec_axpby(1, s, -1, x) followed by vec_axpby(1, x, a, d)
+// (1*s, -1*x and 1*x are exact: one subtraction, one product, one addition)
+__global__ __launch_bounds__(FB) void fw_div_xupdate_kernel(double* __restrict__ x, int64_t n, int64_t p, double a,
+                                                           double fill, double value) {
+    const int64_t stride = (int64_t)gridDim.x * FB;
+    for (int64_t k = (int64_t)blockIdx.x * FB + threadIdx.x; k < n; k += stride) {
+        const double xk = x[k];
+        const double d = ((k == p) ? value : fill) - xk;
+        const double q = a * d;
+        x[k] = xk + q;
+    }
+}
+
 __global__ __launch_bounds__(FB) void column_kernel(const double* __restrict__ V, int64_t ldv, int64_t m, int64_t j,
                                                    double* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * FB;
@@ -850,6 +934,7 @@ extern "C" int accbpg_fw_init(accbpg_dopt* h, const double* x0_dev, double* logd
     ACC_HIP(hipStreamSynchronize(h->stream));
     h->fw_ready = true;
     h->fw_part_nblk = 0;
+    h->fw_div_i = -1;                                          // (Hv and u of an earlier accbpg_fw_div_probe_step are stale)
     return ACCBPG_OK;
 }
 
@@ -1104,6 +1189,94 @@ extern "C" int accbpg_fw_get_state(accbpg_dopt* h, double* x_dev, double* w_dev,
     if (H_dev)
         ACC_TRY(device_copy(H_dev, h->fw_H, (size_t)h->m * h->m, h->stream));
     ACC_HIP(hipStreamSynchronize(h->stream));
+    return ACCBPG_OK;
+}
+
+// ---- Bregman-step Frank-Wolfe on the maintained state (accbpg_fw_div_probe_step / accbpg_fw_div_apply) -----------
+// Workspace behind the handle (allocated by the first probe, freed with it): u (n doubles), FW_DIV_CAP block records
+// of five doubles, FW_DIV_CAP partial sums of u^2, (w_i, i); and a pinned record of 16 doubles: i, w_i, x_i, the five
+// reductions, sum u^2.
+static double* fw_div_rec_of(const accbpg_dopt* h) { return h->fw_div_ws + h->n; }
+static double* fw_div_u2part_of(const accbpg_dopt* h) { return fw_div_rec_of(h) + 5 * FW_DIV_CAP; }
+static ValIdx* fw_div_mxslot_of(const accbpg_dopt* h) { return reinterpret_cast<ValIdx*>(fw_div_u2part_of(h) + FW_DIV_CAP); }
+static int fw_div_alloc(accbpg_dopt* h) {
+    if (h->fw_div_ws) return ACCBPG_OK;
+    if (!h->fw_div_pin) {
+        ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fw_div_pin), sizeof(double) * 16, hipHostMallocDefault));
+        ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_div_pin_dev), h->fw_div_pin, 0));
+    }
+    ACC_HIP(hipMalloc(&h->fw_div_ws, sizeof(double) * ((size_t)h->n + 6 * FW_DIV_CAP + 2)));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_fw_div_probe_step(accbpg_dopt* h, double fill, double value, accbpg_fw_div_probe* out) {
+    if (!h || !out || !h->fw_ready) return ACCBPG_ERR_ARG;
+    ACC_TRY(fw_div_alloc(h));
+    h->fw_div_i = -1;
+    const FwGrids g = fw_grids(h->m, h->n, h->num_cu);
+    const FwInst& t = h->fw;
+    const int64_t m = h->m, n = h->n;
+    hipStream_t s = h->stream;
+    ValIdx* part = fw_part_of(t, m);
+    int nblk = fw_part_waiting(h, 0);
+    if (!nblk) {                                                // (else stage 1 came with the last update of w)
+        nblk = (int)g.nblk;
+        fw_probe_partial_kernel<<<g.nblk, FB, 0, s>>>(t.w, t.x, n, 0, part);
+    }
+    h->fw_part_nblk = 0;
+    h->fw_part_away = false;
+    const int nb = red_blocks(n, FW_DIV_CAP);
+    double *rec = fw_div_rec_of(h), *u2part = fw_div_u2part_of(h), *vp = fw_vp_of(t, m);
+    ValIdx* mxslot = fw_div_mxslot_of(h);
+    fw_div_probe_partial_kernel<<<nb, FB, 0, s>>>(part, nblk, t.w, t.x, n, fill, value, rec, mxslot);
+    fw_div_probe_final_kernel<<<1, FB, 0, s>>>(rec, nb, mxslot, t.x, n, t.V, h->ldv, m, vp, h->fw_div_pin_dev);
+    // the direction of the step: Hv = H V[:,i], u = V^T Hv (the kernels of accbpg_fw_update on their grids), sum u^2
+    fw_gemv_h_kernel<<<g.hb, FB, 0, s>>>(t.H, m, vp, t.hv);
+    prof_begin(h, PROF_FWV);
+    fw_vgemv_partial_kernel<<<dim3(g.vgx, (unsigned)g.ns), FB, 0, s>>>(t.V, h->ldv, m, n, t.hv, g.ns, t.vws, h->vec_ok);
+    prof_end(h, PROF_FWV);
+    fw_div_usum_kernel<<<nb, FB, 0, s>>>(t.vws, g.ns, n, h->fw_div_ws, u2part);
+    reduce_final_kernel<FB, 1, false><<<1, FB, 0, s>>>(u2part, nb, h->fw_div_pin_dev + 8);
+    ACC_HIP(hipGetLastError());
+    ACC_HIP(hipStreamSynchronize(s));
+    const double* pin = h->fw_div_pin;
+    out->i = reinterpret_cast<const int64_t*>(pin)[0];
+    out->w_i = pin[1];
+    out->x_i = pin[2];
+    out->sum_w = pin[3];
+    out->sum_w2 = pin[4];
+    out->slope = pin[5];
+    out->div = pin[6];
+    out->min_x = pin[7];
+    out->sum_u2 = pin[8];
+    if (out->i < 0 || out->i >= n) {
+        set_last_error("accbpg_fw_div_probe_step: pivot index %lld outside [0, n)", (long long)out->i);
+        return ACCBPG_ERR_ARG;
+    }
+    h->fw_div_i = out->i;
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_fw_div_apply(accbpg_dopt* h, int64_t p, double a, double fill, double value, double hcoef,
+                                   double hdiv) {
+    // Hv, vp and u are those of the last accbpg_fw_div_probe_step; any call that moved the state since then has either
+    // cleared fw_div_i (accbpg_fw_init) or left stage-1 records behind (an update of w)
+    if (!h || !h->fw_ready || p < 0 || p >= h->n || h->fw_div_i != p || h->fw_part_nblk != 0) {
+        set_last_error("accbpg_fw_div_apply: pivot %lld is not the index of the last accbpg_fw_div_probe_step on this state",
+                       (long long)p);
+        return ACCBPG_ERR_ARG;
+    }
+    const FwGrids g = fw_grids(h->m, h->n, h->num_cu);
+    const FwInst& t = h->fw;
+    const int64_t m = h->m, n = h->n;
+    hipStream_t s = h->stream;
+    h->fw_div_i = -1;
+    fw_div_xupdate_kernel<<<g.gb, FB, 0, s>>>(t.x, n, p, a, fill, value);
+    fw_rank1_kernel<<<g.rb, FB, 0, s>>>(t.H, m, t.hv, hcoef, hdiv, fw_vp_of(t, m), t.q);
+    // u is summed already: one "split"; fused with stage 1 of the next probe as in accbpg_fw_update
+    fw_wupdate_probe_kernel<<<g.wb, FB, 0, s>>>(t.w, n, h->fw_div_ws, 1, hcoef, hdiv, t.x, 0, fw_part_of(t, m));
+    h->fw_part_nblk = (int)g.wb;
+    ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
 

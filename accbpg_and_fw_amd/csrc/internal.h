@@ -97,6 +97,7 @@ struct ValIdx {
 };
 constexpr int FW_PART_MAX = 512;    // at most this many workgroups write stage-1 records
 constexpr int AWAY_NB = 128;        // at most this many slices of the away variant's second stage
+constexpr int FW_DIV_CAP = 512;     // block cap of the fixed-tree reductions of accbpg_fw_div_probe_step
 __host__ __device__ inline double* fw_vp_of(const FwInst& t, int64_t m) { return t.hv + m; }
 __host__ __device__ inline ValIdx* fw_part_of(const FwInst& t, int64_t m) { return reinterpret_cast<ValIdx*>(t.hv + 2 * m); }
 __host__ __device__ inline ValIdx* fw_part2_of(const FwInst& t, int64_t m) { return fw_part_of(t, m) + 2 * FW_PART_MAX; }
@@ -256,6 +257,12 @@ struct accbpg_dopt {
     accbpg::FwRunSlot* fw_run = nullptr;
     accbpg_fw_step* fw_steps_pin = nullptr;     // ACCBPG_FW_RUN_MAX records
     accbpg_fw_step* fw_steps_dev = nullptr;     // ... as the device addresses them
+    // accbpg_fw_div_probe_step / accbpg_fw_div_apply: u of the probed direction and the reduction records on the device,
+    // the probe record in pinned host memory (allocated by the first probe, freed with the handle)
+    double* fw_div_ws = nullptr;
+    double* fw_div_pin = nullptr;
+    double* fw_div_pin_dev = nullptr;           // ... as the device addresses it
+    int64_t fw_div_i = -1;                      // index of the last probe while its Hv and u are current, else -1
 
     bool use_glds = true;       // direct-to-LDS staging for interior big tiles (debug switch)
     int kern_variant = 0;       // schedule of the direct-to-LDS Gram / gradient kernels (development switch)

@@ -318,6 +318,34 @@ int accbpg_fw_update(accbpg_dopt* h, int64_t p, double xscale, double xadd, doub
 /* Copy state out (device to device): x (n), w (n), H (m*m, row-major).  NULL skips. */
 int accbpg_fw_get_state(accbpg_dopt* h, double* x_dev, double* w_dev, double* H_dev);
 
+/* Frank-Wolfe with a Bregman step (FW_alg_div_step / FW_alg_descent_step, accbpg/algorithms_fw.py:6-75, :210-247) on
+ * the maintained state, for the D-optimal objective, the Burg kernel and the simplex LMO (functions_lmo.py:137-160).
+ * The gradient is -w; the vertex is s_j = fill, s_i = value at i = first argmax of w; x+ = x + a (s - x) changes the
+ * Gram matrix by the factor (1 - a) and a rank-one term in v_i (plus a dense term of relative size <= fill * n that
+ * the caller accounts for to first order with sum_w).
+ *   _probe_step: one pass over w and x fills the record, then the direction of the step is computed with i read from
+ *       device memory: Hv = H V[:,i], u = V^T Hv (the kernels of accbpg_fw_update) and sum u^2.  Hv and u stay in the
+ *       handle for _apply; they do not depend on the step length, so a line search needs no launch per trial.  ONE
+ *       synchronisation.  The argmax follows np.argmin of -w (first index on ties, a NaN is picked).  The sums and the
+ *       minimum run over the fixed tree of the length-n reductions (256 threads, four entries per thread, at most 512
+ *       blocks, blocks in block order): repeated calls are bit-identical.
+ *   _apply: x_j <- x_j + a (s_j - x_j), bit for bit accbpg_vec_axpby(1, s, -1, x) followed by
+ *       accbpg_vec_axpby(1, x, a, d); H <- (H + hcoef Hv Hv^T) / hdiv; w <- (w + hcoef u^2) / hdiv, the update kernels
+ *       of accbpg_fw_update on their grids.  p must be the i of the last _probe_step and the state must not have moved
+ *       since (ACCBPG_ERR_ARG otherwise, nothing is launched).  Does not synchronise.
+ * Both mix freely with accbpg_fw_init / accbpg_fw_get_state / accbpg_fw_probe_step / accbpg_fw_update. */
+typedef struct accbpg_fw_div_probe {
+    int64_t i;                 /* first-index argmax of w (= first argmin of the gradient -w), NaN as np.argmin */
+    double  w_i, x_i;
+    double  sum_w, sum_w2;     /* sum w_j, sum w_j^2 */
+    double  slope;             /* sum_j (-w_j) * (s_j - x_j), s_j = fill except s_i = value; each op rounded once */
+    double  div;               /* sum_j (s_j/x_j - log(s_j/x_j) - 1) */
+    double  min_x;             /* NaN-keeping minimum of x */
+    double  sum_u2;            /* sum_j u_j^2, u = V^T (H V[:,i]) */
+} accbpg_fw_div_probe;
+int accbpg_fw_div_probe_step(accbpg_dopt* h, double fill, double value, accbpg_fw_div_probe* out_host);
+int accbpg_fw_div_apply(accbpg_dopt* h, int64_t p, double a, double fill, double value, double hcoef, double hdiv);
+
 /* The refresh_logdet = 2 part of accbpg_fw_probe_step as a call of its own: copies the current H into the ring slot
  * that comes round and starts its side factorisation; *collected_host <- the value that slot held (the snapshot taken
  * `depth` such calls earlier), NaN while there is none.  accbpg_fw_probe_step(h, away, 2, ...) is this call followed by

@@ -159,6 +159,8 @@ _SIGS = {
     "accbpg_debug_chol_variant": (C.c_int, [_P, C.c_int]),
     "accbpg_debug_plan_flags": (C.c_int, [C.c_int]),
     "accbpg_debug_gemm_loop": (C.c_int, [C.c_int]),
+    "accbpg_debug_prox_variant": (C.c_int, [C.c_int]),
+    "accbpg_debug_prox_state": (C.c_int, [C.POINTER(C.c_int)]),
     "accbpg_debug_chol_trace": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int64)]),
     "accbpg_debug_gram_variant": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "accbpg_debug_grad_variant": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_double)]),

@@ -11,7 +11,7 @@ extern "C" int accbpg_dopt_batch_destroy(accbpg_dopt_batch* b) {
     if (!b) return ACCBPG_OK;
     for (accbpg_dopt* h : b->inst) accbpg_dopt_destroy(h);
     hipFree(b->table); hipFree(b->chol_table[0]); hipFree(b->chol_table[1]); hipFree(b->ops_all); hipFree(b->red_all);
-    hipFree(b->dscal_all); hipFree(b->vflags); hipFree(b->vout); hipFree(b->vpart); hipFree(b->vgg); hipFree(b->vws); hipFree(b->fw_table);
+    hipFree(b->dscal_all); hipFree(b->vflags); hipFree(b->vout); hipFree(b->vpart); hipFree(b->vws); hipFree(b->fw_table);
     hipFree(b->fw_runs);
     if (b->fw_bsteps_pin) hipHostFree(b->fw_bsteps_pin);
     if (b->hpin) hipHostFree(b->hpin);

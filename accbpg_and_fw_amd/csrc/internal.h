@@ -327,7 +327,6 @@ struct accbpg_dopt_batch {
     int* vflags = nullptr;                  // K * 8 ints: status flags + {bisection, newton} of the prox
     double* vout = nullptr;                 // K * 4 doubles: reduction results
     double* vpart = nullptr;                // K * 4 * 1024 doubles: reduction partials
-    double* vgg = nullptr;                  // K * n doubles: gg of the prox when it does not fit in registers
     double* vws = nullptr;                  // workspace of the single-instance prox (long vectors, one instance at a time)
     double* vpin = nullptr;                 // pinned mirror (K * 8 doubles)
     accbpg::FwInst* fw_table = nullptr;     // device, K entries: Frank-Wolfe state of every instance (built by the first accbpg_dopt_batch_fw_init)

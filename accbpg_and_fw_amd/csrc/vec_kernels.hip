@@ -7,6 +7,7 @@
 // This translation unit is compiled with -ffp-contract=off: the reference evaluates these
 // expressions with separate NumPy ufuncs (one rounding per operation), so no multiply-add here
 // may be fused.  Replaces accbpg/functions.py:246-271 and 336-356.
+#include <atomic>
 #include <mutex>
 
 #include "internal.h"
@@ -569,6 +570,8 @@ int vec_scratch(double** pin, int** flags, double** out) {
 }
 
 static bool g_prox_multi_off = false;    // set when the multi-workgroup prox had to give up a wait (then: one workgroup)
+static std::atomic<int> g_prox_variant{0};          // accbpg_debug_prox_variant
+static thread_local int g_prox_last[2] = {0, 0};    // {variant, workgroups} of this thread's last prox launch
 
 int64_t vec_ws_doubles(int64_t n) { return n + 4 * RMAXBLK + 64; }
 
@@ -588,14 +591,27 @@ extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g
                                             void* stream) {
     if (!g_dev || !x_out_dev || n <= 0 || !ws_dev) return ACCBPG_ERR_ARG;
     if (!(L > 0.0)) return ACCBPG_ERR_ASSERT;                 // functions.py:270 / :340
+    // the form of this call: by size, or the one accbpg_debug_prox_variant names
+    const int forced = g_prox_variant.load(std::memory_order_relaxed);
+    bool multi, wide;
+    if (forced == 2 || forced == 3) { multi = true; wide = forced == 3; }
+    else if (forced == 1) { multi = false; wide = false; }
+    else {
+        multi = n > (int64_t)PB * 32 && n <= (int64_t)PB * 32 * 128 && !g_prox_multi_off;
+        wide = n > (int64_t)PB * 8 * 128;
+    }
+    const int ept = wide ? 32 : 8;
+    const int64_t G64 = (n + (int64_t)PB * ept - 1) / ((int64_t)PB * ept);
+    if (multi && G64 > 128) {                                   // only a forced form can get here
+        set_last_error("accbpg_burg_simplex_div_prox: the forced multi-workgroup form needs more than 128 workgroups");
+        return ACCBPG_ERR_ARG;
+    }
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
     int* g_info = g_flags + 4;                                  // {bisection, newton} right behind the flags
-    if (n > (int64_t)PB * 32 && n <= (int64_t)PB * 32 * 128 && !g_prox_multi_off) {
+    if (multi) {
         // long vectors: several workgroups, each with its slice in registers (ws_dev: exchange slots, then the flags)
-        const bool wide = n > (int64_t)PB * 8 * 128;
-        const int ept = wide ? 32 : 8;
-        const int G = (int)((n + (int64_t)PB * ept - 1) / ((int64_t)PB * ept));
+        const int G = (int)G64;
         ProxMultiShared shm;
         shm.part = ws_dev;
         shm.epoch = reinterpret_cast<int*>(ws_dev + 4 * G);
@@ -607,6 +623,7 @@ extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g
         else
             burg_prox_multi_kernel<8><<<G, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, shm, G, g_info, g_flags, 20000000LL);
         ACC_HIP(hipGetLastError());
+        g_prox_last[0] = wide ? 3 : 2; g_prox_last[1] = G;
         int* pin_m = reinterpret_cast<int*>(g_pin);
         ACC_HIP(hipMemcpyAsync(pin_m, g_flags, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
         ACC_HIP(hipMemcpyAsync(pin_m + 8, shm.abortw, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -618,20 +635,41 @@ extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g
         }
         g_prox_multi_off = true;                                // a wait timed out: one workgroup from here on
     }
-    if (n <= (int64_t)PB * 2)
+    int ran;
+    if (forced != 1 && n <= (int64_t)PB * 2) {
         burg_prox_kernel<2><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-    else if (n <= (int64_t)PB * 8)
+        ran = 10;
+    } else if (forced != 1 && n <= (int64_t)PB * 8) {
         burg_prox_kernel<8><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-    else if (n <= (int64_t)PB * 32)
+        ran = 11;
+    } else if (forced != 1 && n <= (int64_t)PB * 32) {
         burg_prox_kernel<32><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-    else
+        ran = 12;
+    } else {
         burg_prox_kernel<0><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
+        ran = 1;
+    }
+    g_prox_last[0] = ran; g_prox_last[1] = 1;
     ACC_HIP(hipGetLastError());
     int* pin_i = reinterpret_cast<int*>(g_pin);
     ACC_HIP(hipMemcpyAsync(pin_i, g_flags, 6 * sizeof(int), hipMemcpyDeviceToHost, s));   // flags + info, one copy
     ACC_HIP(hipStreamSynchronize(s));
     if (info_host) { info_host[0] = pin_i[4]; info_host[1] = pin_i[5]; }
     if (pin_i[FLAG_NONPOS]) return ACCBPG_ERR_ASSERT;         // y.min() > 0, functions.py:270
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_debug_prox_variant(int variant) {
+    if (variant < 0 || variant > 3) return ACCBPG_ERR_ARG;
+    g_prox_variant.store(variant, std::memory_order_relaxed);
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_debug_prox_state(int* out3_host) {
+    if (!out3_host) return ACCBPG_ERR_ARG;
+    out3_host[0] = g_prox_last[0];
+    out3_host[1] = g_prox_last[1];
+    out3_host[2] = g_prox_multi_off ? 1 : 0;
     return ACCBPG_OK;
 }
 
@@ -808,12 +846,10 @@ extern "C" int accbpg_burg_reg_div_prox(int kind, const double* y_dev, const dou
 // ------------------------------------------------------------------------------------------------------------
 static int batch_vec_scratch(accbpg_dopt_batch* b) {
     if (b->vflags) return ACCBPG_OK;
-    const int64_t n = b->inst[0]->n;
     ACC_HIP(hipMalloc(&b->vflags, sizeof(int) * 8 * (size_t)b->K));
     ACC_HIP(hipMemset(b->vflags, 0, sizeof(int) * 8 * (size_t)b->K));
     ACC_HIP(hipMalloc(&b->vout, sizeof(double) * 4 * (size_t)b->K));
     ACC_HIP(hipMalloc(&b->vpart, sizeof(double) * 4 * RMAXBLK * (size_t)b->K));
-    if (n > (int64_t)PB * 32) ACC_HIP(hipMalloc(&b->vgg, sizeof(double) * (size_t)n * (size_t)b->K));
     ACC_HIP(hipHostMalloc(&b->vpin, sizeof(double) * 8 * (size_t)b->K, hipHostMallocDefault));
     return ACCBPG_OK;
 }
@@ -866,10 +902,8 @@ extern "C" int accbpg_dopt_batch_burg_simplex_div_prox(accbpg_dopt_batch* b, con
         burg_prox_batch_kernel<2><<<act.n, PB, 0, s>>>(act, y_dev, g_dev, ld, Ls, eps, n, x_out_dev, nullptr, b->vflags);
     else if (n <= (int64_t)PB * 8)
         burg_prox_batch_kernel<8><<<act.n, PB, 0, s>>>(act, y_dev, g_dev, ld, Ls, eps, n, x_out_dev, nullptr, b->vflags);
-    else if (n <= (int64_t)PB * 32)
+    else                                                        // n <= PB * 32: longer rows returned above
         burg_prox_batch_kernel<32><<<act.n, PB, 0, s>>>(act, y_dev, g_dev, ld, Ls, eps, n, x_out_dev, nullptr, b->vflags);
-    else
-        burg_prox_batch_kernel<0><<<act.n, PB, 0, s>>>(act, y_dev, g_dev, ld, Ls, eps, n, x_out_dev, b->vgg, b->vflags);
     ACC_HIP(hipGetLastError());
     int* pin_i = reinterpret_cast<int*>(b->vpin);
     ACC_HIP(hipMemcpyAsync(pin_i, b->vflags, sizeof(int) * 8 * (size_t)b->K, hipMemcpyDeviceToHost, s));

@@ -87,7 +87,7 @@ int accbpg_dopt_eval_gap_ms(accbpg_dopt* first, accbpg_dopt* second, double* ms_
  * completed when `begin` returned.  Gradient evaluations (flag 1, 2), the staged entry points (accbpg_dopt_gram,
  * _factor, _eval_gram), the sharded objective and batches neither write nor consult records.  A record is dropped by any
  * error return of begin/end, while a flag-0 evaluation of its handle is in flight, and by accbpg_dopt_value_reuse,
- * accbpg_dopt_factor_in_small_launches and the accbpg_debug_*_variant switches; the redo of an abandoned one-launch
+ * accbpg_dopt_factor_in_small_launches and the accbpg_debug_*_variant switches of a handle; the redo of an abandoned one-launch
  * factorisation always evaluates.
  *   accbpg_dopt_value_reuse(h, on): on = 0 switches lookups and the record off for h, anything else on (the default).
  *   accbpg_dopt_value_reuse_stats: compare launches made and evaluations answered on h since its creation.
@@ -627,6 +627,17 @@ int accbpg_debug_plan_flags(int flags);
  * 0 = production (the global loads of three k-steps in flight), 1 = the loop with one k-step of look-ahead that
  * production had before, 2..4 = that many k-steps in flight (A/B measurements).  Bit-identical results from all. */
 int accbpg_debug_gemm_loop(int variant);
+
+/* Development switch, process wide, read at every accbpg_burg_simplex_div_prox call.
+ * variant: 0 = by size (production), 1 = burg_prox_kernel<0> (one workgroup, gg re-read from the workspace),
+ * 2 = burg_prox_multi_kernel<8>, 3 = burg_prox_multi_kernel<32>.  A forced multi form whose workgroup count would
+ * exceed 128 returns ACCBPG_ERR_ARG from the prox call, nothing launched.  Forcing 2 or 3 ignores the "multi off" latch
+ * for that call but still sets it on a timeout. */
+int accbpg_debug_prox_variant(int variant);
+/* out3_host <- { variant the LAST prox call of this host thread launched (1, 2, 3 as above; 10, 11, 12 =
+ * burg_prox_kernel<2>, <8>, <32>; a call that fell back after a timeout reports the kernel that produced the result),
+ * workgroups of that launch, the "multi off" latch (0/1) }. */
+int accbpg_debug_prox_state(int* out3_host);
 
 /* Timing ablation bits for the Cholesky step kernel (development aid; 0 = product behaviour):
  * 1 skip the diagonal-block factorisation, 2 skip the panel solve, 4 skip the MFMA products; 8, 16, 32 switch

@@ -218,7 +218,8 @@ def test_prox_and_divergence_match_reference_golden(acc, tag):
 
 @pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 2048, 2049, 8193, 40000, 300000])
 def test_prox_sizes_against_oracle(acc, O, n):
-    """Every register-cached variant and the re-read variant, ragged n."""
+    """Every register-cached variant and burg_prox_multi_kernel<8> (n = 40000, 300000), ragged n.  The wide
+    multi-workgroup form and the re-read variant start above n = 1048576 and 4194304: test_gpu_prox.py runs them."""
     rng = np.random.RandomState(n)
     y = rng.rand(n) + 1e-3
     y /= y.sum()

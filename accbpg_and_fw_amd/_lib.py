@@ -38,6 +38,13 @@ class FwStep(C.Structure):
                 ("hcoef", C.c_double), ("hdiv", C.c_double), ("kind", C.c_int32), ("status", C.c_int32)]
 
 
+class TrialOut(C.Structure):
+    """accbpg_trial_out: what a clean accbpg_dopt_burg_trial returns."""
+    _fields_ = [("fy", C.c_double), ("lin", C.c_double), ("dxy", C.c_double), ("dzz", C.c_double), ("fx", C.c_double),
+                ("fk", C.c_double), ("prox_info", C.c_int32 * 2), ("fk_answered", C.c_int32), ("reserved", C.c_int32)]
+
+
+TRIAL_REPLAY = 5            # ACCBPG_TRIAL_REPLAY
 FW_RUN_MAX = 1024           # ACCBPG_FW_RUN_MAX
 FW_APPLIED, FW_STOPPED, FW_BAD_PIVOT, FW_NOT_RUN = 0, 1, 2, 3      # accbpg_fw_step.status
 
@@ -52,8 +59,11 @@ _SIGS = {
     "accbpg_dopt_func_grad_begin": (C.c_int, [_P, _P, C.c_int, _P]),
     "accbpg_dopt_func_grad_end": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "accbpg_dopt_eval_gap_ms": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),
+    "accbpg_dopt_burg_trial": (C.c_int, [_P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P,
+                                         C.POINTER(TrialOut)]),
     "accbpg_dopt_value_reuse": (C.c_int, [_P, C.c_int]),
     "accbpg_dopt_value_reuse_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "accbpg_dopt_value_recorded": (C.c_int, [_P, _P]),
     "accbpg_dopt_value_peer": (C.c_int, [_P, _P]),
     "accbpg_dopt_gram": (C.c_int, [_P, _P, _P]),
     "accbpg_dopt_factor": (C.c_int, [_P, _P, C.POINTER(C.c_double)]),

@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from .functions import (BurgEntropy, BurgEntropySimplex, ShannonEntropy, SquaredL2Norm, SumOf2nd4thPowers,
+from .functions import (BurgEntropy, BurgEntropySimplex, DOptimalObj, ShannonEntropy, SquaredL2Norm, SumOf2nd4thPowers,
                         combine_ls_terms, from_dev, ls_terms, shannon_ls_terms, to_dev, vec_axpby, vec_div_scalar,
                         vec_dot_diff)
 from .utils import get_random_float
@@ -68,6 +68,22 @@ def _can_speculate(f, x, checkdiv):
     in use."""
     return (not checkdiv) and (not _lin(f)) and getattr(f, "_spec", False) and getattr(f, "_overlap", False) \
         and not getattr(f, "_prof", False) and hasattr(f, "grad_async") and isinstance(x, torch.Tensor) and x.is_cuda
+
+
+_BURG_SIMPLEX_HOOKS = ("div_prox_map", "prox_map", "_prox", "divergence", "extra_Psi")
+
+
+def _can_one_wait(f, h, x, checkdiv):
+    """ABPG_gain runs its line-search trials through accbpg_dopt_burg_trial (DOptimalObj.one_wait_trials, on by
+    default) on this package's D-optimal objective evaluating directly -- no Gram reuse, no gradients started ahead, no
+    memo, not a shard, not a batch instance -- with the Burg simplex kernel, device iterates and the value test.  A
+    native trial passes by the Python methods of f and h, so an objective or a kernel whose methods were overridden in
+    a subclass or wrapped on the instance keeps the stepwise loop, which calls them."""
+    if checkdiv or not isinstance(f, DOptimalObj) or not f._one_wait_ok():
+        return False
+    if type(h) is not BurgEntropySimplex or any(name in vars(h) for name in _BURG_SIMPLEX_HOOKS):
+        return False
+    return isinstance(x, torch.Tensor) and x.is_cuda and x.device == f.device
 
 
 def _value_end(f, pending):
@@ -253,7 +269,12 @@ def ABPG_gain(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, G0=1,
 def ABPG_gain_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, G0=1,
                     ls_inc=1.2, ls_dec=1.2, theta_eq=True, checkdiv=False,
                     restart=False, restart_rule='g', verbose=True, verbskip=1):
-    """Generator form of ABPG_gain: yields k after each outer iteration, returns its tuple."""
+    """Generator form of ABPG_gain: yields k after each outer iteration, returns its tuple.
+
+    With DOptimalObj.one_wait_trials (the default, see ``_can_one_wait``) a line-search trial is one native call with
+    one wait, and F[k] is answered inside the first trial of iteration k: T[k] is then stamped when F[k] is known on
+    the host, which is at that trial's wait.  A trial that has to be replayed stepwise has dropped the value record, so
+    an F[k] that rode in it is evaluated in full: the same number, one less in ``values_reused``."""
     if verbose:
         print("\nABPG_gain method for min_{x in C} F(x) = f(x) + Psi(x)")
         print("     k      F(x)       theta         Gk" +
@@ -278,12 +299,17 @@ def ABPG_gain_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, G0=1,
     retries_before = 0      # failed trials of the previous iteration: how far ahead the next one starts gradients
     k = -1
     for k in range(maxitrs):
-        pending = _value_begin(f, x, xcombo)                    # :347 (runs beside the first gradient below)
-        t_known = time.time()
-
         z_prev, x_prev = z, x
         G_prev, theta_prev = G, theta
         G = G / ls_dec                                          # :358
+
+        # a whole trial per call and one wait (DOptimalObj.one_wait_trials); where the accepting test left its value
+        # record at x (DOptimalObj.reuse_values) F[k] rides in the first trial, which answers it from that record
+        one_wait = _can_one_wait(f, h, x_prev, checkdiv)
+        fk_in_trial = one_wait and f.value_recorded(x_prev)
+        pending = None if fk_in_trial else _value_begin(f, x, xcombo)   # :347 (runs beside the first gradient below)
+        t_known = time.time()
+        fk_due = True
 
         def theta_for(Gt):                                      # :362-367 for a trial gain Gt
             if kk == 0:
@@ -299,28 +325,51 @@ def ABPG_gain_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, G0=1,
         searching = True
         while searching:                                        # :361
             theta = theta_for(G)
-            if started is not None:
-                y, ticket = started                             # the point and the evaluation of this very trial
-                started = None
-                fy, g = f.grad_wait(ticket)
+            done = None
+            if one_wait:                                        # :369-378 and f(x) of :387, None: replay it stepwise
+                done = f.trial(x_prev, z_prev, theta, theta ** (gamma - 1) * G * L, h.eps, fk_due and pending is None)
+            if fk_due and pending is None and (done is None or not done[4].fk_answered):
+                # F[k] was not answered in the trial (x changed in place under its record): evaluate it
+                pending = _value_begin(f, x_prev, xcombo)
+                t_known = time.time()
+            if done is not None:
+                y, g, z, x, res = done
+                fy = res.fy
+                h.last_info = (res.prox_info[0], res.prox_info[1])
+                if fk_due:
+                    if pending is None:
+                        F[k] = res.fk + h.extra_Psi(x_prev)     # :348, known at the trial's wait
+                        T[k] = time.time() - t_start            # :349
+                    else:
+                        F[k] = _value_end(f, pending) + h.extra_Psi(x_prev)
+                        T[k] = _stamp(f, pending, t_start, t_known)
+                        pending = None
+                    fk_due = False
+                lin, dxy, dzz = np.float64(res.lin), np.float64(res.dxy), np.float64(res.dzz)
             else:
-                y = vec_axpby(1 - theta, x_prev, theta, z_prev)  # :369
-                if _lin(f):
-                    fy, g = f.func_grad_combo(y, (1 - theta, x_prev, theta, z_prev), 2)
+                if started is not None:
+                    y, ticket = started                         # the point and the evaluation of this very trial
+                    started = None
+                    fy, g = f.grad_wait(ticket)
                 else:
-                    fy, g = f.func_grad(y)                      # :371
-            if pending is not None:
-                F[k] = _value_end(f, pending) + h.extra_Psi(x_prev)   # :348
-                T[k] = _stamp(f, pending, t_start, t_known)           # :349
-                pending = None
-            z = h.div_prox_map(z_prev, g, theta ** (gamma - 1) * G * L)   # :373
-            x = vec_axpby(1 - theta, x_prev, theta, z)          # :374
-            if _lin(f):
-                f.ensure_gram(z)                                # the one O(m^2 n) product of this pass
-                xcombo = (1 - theta, x_prev, theta, z)
+                    y = vec_axpby(1 - theta, x_prev, theta, z_prev)  # :369
+                    if _lin(f):
+                        fy, g = f.func_grad_combo(y, (1 - theta, x_prev, theta, z_prev), 2)
+                    else:
+                        fy, g = f.func_grad(y)                  # :371
+                if fk_due:
+                    F[k] = _value_end(f, pending) + h.extra_Psi(x_prev)   # :348
+                    T[k] = _stamp(f, pending, t_start, t_known)           # :349
+                    pending = None
+                    fk_due = False
+                z = h.div_prox_map(z_prev, g, theta ** (gamma - 1) * G * L)   # :373
+                x = vec_axpby(1 - theta, x_prev, theta, z)      # :374
+                if _lin(f):
+                    f.ensure_gram(z)                            # the one O(m^2 n) product of this pass
+                    xcombo = (1 - theta, x_prev, theta, z)
 
-            lin, dxy, dzz = _divergences(h, g, x, y, z, z_prev)  # :377-378 and the dot of :387
-            if dzz < epsilon:                                   # :379-380
+                lin, dxy, dzz = _divergences(h, g, x, y, z, z_prev)  # :377-378 and the dot of :387
+            if dzz < epsilon:                                   # :379-380 (a value the trial computed is dropped)
                 break
 
             Gdr = dxy / dzz / theta ** gamma                    # :382
@@ -334,7 +383,12 @@ def ABPG_gain_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, G0=1,
                     theta_next = theta_for(G * ls_inc)
                     y_next = vec_axpby(1 - theta_next, x_prev, theta_next, z_prev)
                     started = (y_next, f.grad_async(y_next))
-                searching = (_value(f, x, xcombo) > fy + lin + theta ** gamma * G * L * dzz)   # :387
+                if done is not None:
+                    f.calls["value"] += 1                       # f(x) came with the trial
+                    fx = res.fx
+                else:
+                    fx = _value(f, x, xcombo)
+                searching = (fx > fy + lin + theta ** gamma * G * L * dzz)   # :387
 
             if searching:
                 G = G * ls_inc                                  # :390

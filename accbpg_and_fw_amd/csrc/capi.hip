@@ -6,6 +6,7 @@
 
 #include "internal.h"
 #include "reduce.hpp"
+#include "trial_verdict.h"
 
 namespace accbpg {
 
@@ -105,6 +106,8 @@ extern "C" int accbpg_dopt_destroy(accbpg_dopt* h) {
         lk.erase(std::remove(lk.begin(), lk.end(), h), lk.end());
     }
     hipFree(h->val_copy);
+    hipFree(h->trial_stat);
+    if (h->trial_pin) hipHostFree(h->trial_pin);
     hipFree(h->Vblk);
     hipFree(h->Lbuf); hipFree(h->Wbuf); hipFree(h->Tbuf); hipFree(h->slabs); hipFree(h->tiles); hipFree(h->wg_ranges); hipFree(h->gram_cstart); hipFree(h->gram_contrib);
     if (!h->dscal_ext) hipFree(h->dscal);
@@ -218,6 +221,26 @@ static int value_matches(accbpg_dopt* h, const accbpg_dopt* rec, const double* x
     return ACCBPG_OK;
 }
 
+// The launches of one evaluation on h's stream, its scalars and flags at `status` (STATUS_DOUBLES device doubles: the
+// handle's own, or one slice of a trial's status block -- two evaluations enqueued back to back share the handle's
+// buffers, which stream order protects, and nothing else).  record: the reset launch keeps a copy of x in val_copy.
+static int enqueue_eval(accbpg_dopt* h, const double* x_dev, int flag, double* g_dev, double* status, bool record) {
+    // (with the one-launch Cholesky the Gram matrix gets a buffer of its own and stays intact for a redo)
+    double* gram = chol_tiles_usable(h) ? h->Gbuf : h->Lbuf;
+    ACC_TRY(launch_gram(h, x_dev, gram));
+    // resets the scalars and flags first, and checks x >= 0 in the same launch (functions.py:45)
+    // ... and for a value record keeps x as it was evaluated, for the compare of a later lookup (no launch of its own:
+    // BPG at (80,200) ran 4.6 % slower with a copy kernel per value, profiles/history/value_reuse_rate_copy_kernel.json)
+    if (record) ACC_TRY(value_alloc(h));
+    // (the factorisation's launches are the only ones of an evaluation that write status words)
+    ACC_TRY(launch_cholesky(h, h->Lbuf, flag != 0 ? h->Wbuf : nullptr, x_dev, gram, record ? h->val_copy : nullptr, status));
+    if (flag != 0) {
+        ACC_TRY(launch_trtri(h));
+        ACC_TRY(launch_colnorm(h, h->Wbuf, g_dev, -1.0));
+    }
+    return ACCBPG_OK;
+}
+
 // accbpg_dopt_func_grad_begin; lookup = false for the redo of an abandoned evaluation, which always evaluates
 static int func_grad_begin(accbpg_dopt* h, const double* x_dev, int flag, double* g_dev, bool lookup) {
     h->last_x = x_dev; h->last_flag = flag; h->last_g = g_dev;
@@ -240,18 +263,7 @@ static int func_grad_begin(accbpg_dopt* h, const double* x_dev, int flag, double
         }
         h->val_valid = false;                                   // until _end has seen this evaluation succeed
     }
-    // (with the one-launch Cholesky the Gram matrix gets a buffer of its own and stays intact for a redo)
-    double* gram = chol_tiles_usable(h) ? h->Gbuf : h->Lbuf;
-    ACC_TRY(launch_gram(h, x_dev, gram));
-    // resets the scalars and flags first, and checks x >= 0 in the same launch (functions.py:45)
-    // ... and for a value record keeps x as it was evaluated, for the compare of a later lookup (no launch of its own:
-    // BPG at (80,200) ran 4.6 % slower with a copy kernel per value, profiles/history/value_reuse_rate_copy_kernel.json)
-    if (record) ACC_TRY(value_alloc(h));
-    ACC_TRY(launch_cholesky(h, h->Lbuf, flag != 0 ? h->Wbuf : nullptr, x_dev, gram, record ? h->val_copy : nullptr));
-    if (flag != 0) {
-        ACC_TRY(launch_trtri(h));
-        ACC_TRY(launch_colnorm(h, h->Wbuf, g_dev, -1.0));
-    }
+    ACC_TRY(enqueue_eval(h, x_dev, flag, g_dev, h->dscal, record));
     h->val_pending = record;
     ACC_HIP(hipMemcpyAsync(h->hpin, h->dscal, sizeof(double) * STATUS_DOUBLES, hipMemcpyDeviceToHost, h->stream));   // scalars + flags
     ACC_HIP(hipEventRecord(h->ev_done, h->stream));            // when this evaluation's results are on the host
@@ -346,11 +358,122 @@ extern "C" int accbpg_dopt_func_grad(accbpg_dopt* h, const double* x_dev, int fl
     return accbpg_dopt_func_grad_end(h, f_host);
 }
 
+static_assert(TRIAL_EVAL_DOUBLES == STATUS_DOUBLES && TRIAL_FLAG_NOT_PD == FLAG_NOT_PD && TRIAL_FLAG_NEG_X == FLAG_NEG_X &&
+                  TRIAL_FLAG_NONPOS == FLAG_NONPOS && TRIAL_FLAG_ABORT == FLAG_ABORT,
+              "trial_verdict.h restates the status layout");
+
+/* One line-search trial of ABPG_gain (accbpg/algorithms.py:369-387) enqueued whole on the handle's stream and waited
+ * for once: see include/accbpg_hip.h.  Every launch is the one the stepwise entry points make, with its status words
+ * in a slice of its own of one block that a single copy brings to the host. */
+extern "C" int accbpg_dopt_burg_trial(accbpg_dopt* h, const double* x_prev_dev, const double* z_prev_dev, double theta,
+                                      double L, double eps, int want_fk, double* y_dev, double* g_dev, double* z_dev,
+                                      double* x_dev, double* ws_dev, accbpg_trial_out* out_host) {
+    if (!h || !x_prev_dev || !z_prev_dev || !y_dev || !g_dev || !z_dev || !x_dev || !ws_dev || !out_host)
+        return ACCBPG_ERR_ARG;
+    if (!(L > 0.0)) {                                           // functions.py:270: the stepwise prox raises it (nothing ran)
+        value_forget(h);                                        // (every REPLAY leaves the handle without a record)
+        return ACCBPG_TRIAL_REPLAY;
+    }
+    const int64_t n = h->n;
+    hipStream_t s = h->stream;
+    if (!h->trial_stat) {
+        double* p = nullptr;
+        ACC_HIP(hipMalloc(&p, sizeof(double) * TRIAL_DOUBLES));
+        if (hipMemset(p, 0, sizeof(double) * TRIAL_DOUBLES) != hipSuccess ||
+            hipHostMalloc(&h->trial_pin, sizeof(double) * TRIAL_DOUBLES, hipHostMallocDefault) != hipSuccess) {
+            hipFree(p);
+            set_last_error("accbpg_dopt_burg_trial: could not allocate the status block");
+            return ACCBPG_ERR_HIP;
+        }
+        h->trial_stat = p;
+    }
+    double* blk = h->trial_stat;
+    h->val_pending = false;                                     // (no begin/end evaluation is in flight across a trial)
+    h->val_hit = false;
+    const bool record = h->val_reuse;
+    TrialAsked asked = {0, 0};
+    const accbpg_dopt* rec = nullptr;
+    // what the call leaves behind when it does not end in a verdict: no record (its copy of x may be overwritten)
+    auto fail = [&](int rc) { value_forget(h); return rc; };
+    // a. F[k] = f(x_prev): the host-side part of the lookup of func_grad_begin; the compare itself rides in front
+    // (the first record at this address is the one compared -- h's own before its peer's.  func_grad_begin goes on to the
+    // peer when the contents differ from its own record; a trial cannot wait for that answer, so where both records sit
+    // at one address and only the peer's matches, F[k] is "not answered" here and evaluated: the same bits, one answer
+    // fewer in the counters)
+    if (want_fk && record) {
+        accbpg_dopt* const recs[2] = {h, h->val_peer};
+        for (int r = 0; r < 2 && !rec; ++r)
+            if (recs[r] && recs[r]->val_valid && recs[r]->val_x == x_prev_dev) rec = recs[r];
+        if (rec) {
+            asked.cmp_stamp = h->val_gen = h->val_gen % 1000000000 + 1;
+            const int64_t nb = std::min<int64_t>((n + 255) / 256, 1024);
+            value_compare_kernel<<<(unsigned)nb, 256, 0, s>>>(reinterpret_cast<const unsigned long long*>(x_prev_dev),
+                                                             reinterpret_cast<const unsigned long long*>(rec->val_copy), n,
+                                                             asked.cmp_stamp, reinterpret_cast<int*>(blk + TRIAL_CMP));
+            if (hipGetLastError() != hipSuccess) return fail(ACCBPG_ERR_HIP);
+        }
+    }
+    const double rec_f = rec ? rec->val_f : 0.0;
+    if (record) h->val_valid = false;                           // until the verdict has seen the value evaluation succeed
+    bool multi = false;
+    auto enqueue = [&]() -> int {
+        ACC_TRY(accbpg_vec_axpby(1.0 - theta, x_prev_dev, theta, z_prev_dev, n, y_dev, s));                       // b. :369
+        ACC_TRY(enqueue_eval(h, y_dev, 2, g_dev, blk + TRIAL_GRAD, false));                                       // c. :371
+        ACC_TRY(trial_prox_enqueue(z_prev_dev, g_dev, L, eps, n, z_dev, ws_dev, reinterpret_cast<int*>(blk + TRIAL_PROX),
+                                   TRIAL_PROX_GAVE_UP, s, &multi));                                               // d. :373
+        ACC_TRY(accbpg_vec_axpby(1.0 - theta, x_prev_dev, theta, z_dev, n, x_dev, s));                            // e. :374
+        ACC_TRY(trial_ls_terms_enqueue(g_dev, x_dev, y_dev, z_dev, z_prev_dev, n, ws_dev, blk + TRIAL_LS, s));    // f. :377-378
+        ACC_TRY(enqueue_eval(h, x_dev, 0, nullptr, blk + TRIAL_VALUE, record));                                   // g. :387
+        ACC_HIP(hipMemcpyAsync(h->trial_pin, blk, sizeof(double) * TRIAL_DOUBLES, hipMemcpyDeviceToHost, s));     // h.
+        ACC_HIP(hipEventRecord(h->ev_done, s));                 // when the trial's results are on the host (accbpg_dopt_eval_gap_ms)
+        ACC_HIP(hipStreamSynchronize(s));
+        return ACCBPG_OK;
+    };
+    const int rc = enqueue();
+    if (rc != ACCBPG_OK) return fail(rc);
+    asked.prox_multi = multi ? 1 : 0;
+    const double* pin = h->trial_pin;
+    const TrialVerdict v = trial_verdict(pin, asked);
+    if (v.chol_gave_up && !h->chol_tiles_off) {                 // as func_grad_end: launch per block column from now on
+        h->chol_tiles_off = true;
+        note_tiles_fallback("accbpg_dopt_burg_trial");
+    }
+    if (v.prox_gave_up) trial_prox_gave_up();
+    if (v.replay) return fail(ACCBPG_TRIAL_REPLAY);             // nothing is committed; the counters do not move
+    const int* px = reinterpret_cast<const int*>(pin + TRIAL_PROX);
+    out_host->fy = -pin[TRIAL_GRAD];                            // f = -logdet   (functions.py:51)
+    out_host->lin = pin[TRIAL_LS]; out_host->dxy = pin[TRIAL_LS + 1]; out_host->dzz = pin[TRIAL_LS + 2];
+    out_host->fx = -pin[TRIAL_VALUE];
+    out_host->prox_info[0] = px[TRIAL_PROX_INFO]; out_host->prox_info[1] = px[TRIAL_PROX_INFO + 1];
+    out_host->fk_answered = v.fk_answered;
+    out_host->fk = v.fk_answered ? rec_f : 0.0;
+    if (asked.cmp_stamp) {
+        ++h->val_compares;
+        if (v.fk_answered) ++h->val_answered;
+    }
+    if (record) {                                               // the value evaluation succeeded: its record is complete
+        h->val_x = x_dev;
+        h->val_f = out_host->fx;
+        h->val_valid = true;
+    }
+    return ACCBPG_OK;
+}
+
 extern "C" int accbpg_dopt_value_reuse(accbpg_dopt* h, int on) {
     if (!h) return ACCBPG_ERR_ARG;
     h->val_reuse = on != 0;
     value_forget(h);
     return ACCBPG_OK;
+}
+
+/* 1 when the host-side part of a value lookup at x_dev holds on h -- a valid record of h or its peer at that device
+ * address -- so that only the compare of the contents is left; 0 otherwise.  No launch, no wait. */
+extern "C" int accbpg_dopt_value_recorded(accbpg_dopt* h, const double* x_dev) {
+    if (!h || !x_dev || !h->val_reuse) return 0;
+    const accbpg_dopt* const recs[2] = {h, h->val_peer};
+    for (const accbpg_dopt* rec : recs)
+        if (rec && rec->val_valid && rec->val_x == x_dev) return 1;
+    return 0;
 }
 
 extern "C" int accbpg_dopt_value_reuse_stats(accbpg_dopt* h, int64_t* compares_host, int64_t* answered_host) {

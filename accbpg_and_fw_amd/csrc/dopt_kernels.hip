@@ -3001,11 +3001,11 @@ bool chol_tiles_usable(const accbpg_dopt* h) {
     return h->chol_tiles_ok && !h->chol_tiles_off && (h->chol_dbg & 63) == 0;
 }
 
-static int launch_chol_tiles(accbpg_dopt* h, const double* src, double* A, double* Winv) {
+static int launch_chol_tiles(accbpg_dopt* h, const double* src, double* A, double* Winv, double* dscal, int* dflag) {
     const int64_t m = h->m;
     const int T = (int)((m + NB - 1) / NB);
     CholInst ci;
-    ci.src = src; ci.L = A; ci.Ldiag = h->Tbuf; ci.Winv = Winv; ci.logdet = h->dscal; ci.flags = h->dflag;
+    ci.src = src; ci.L = A; ci.Ldiag = h->Tbuf; ci.Winv = Winv; ci.logdet = dscal; ci.flags = dflag;
     ci.ready = h->chol_ready; ci.aux = h->chol_aux; ci.hand = h->chol_hand; ci.trace = h->chol_trace;
     const int dev = (h->device >= 0 && h->device < 64) ? h->device : 0;
     std::lock_guard<std::mutex> lk(g_tiles_mu);
@@ -3035,8 +3035,12 @@ static int launch_chol_tiles(accbpg_dopt* h, const double* src, double* A, doubl
     return ACCBPG_OK;
 }
 
-int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xcheck, const double* src, double* xkeep) {
+int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xcheck, const double* src, double* xkeep,
+                    double* status) {
     const int64_t m = h->m;
+    // the scalars and flags of this factorisation: the handle's own, or the slice the caller names (laid out alike)
+    double* const dscal = status ? status : h->dscal;
+    int* const dflag = status ? reinterpret_cast<int*>(status + 16) : h->dflag;
     const int T = (int)((m + NB - 1) / NB);
     if (src == nullptr) src = A;
     const bool tiles = chol_tiles_usable(h);
@@ -3045,11 +3049,11 @@ int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xchec
     // wave of the Gram kernel (392 of the 512 registers of a SIMD lane), four do not -- and this launch often meets the OTHER stream's Gram launch, which holds
     // every compute unit for 2 ms (its rocprofv3 average with 1024 threads in the steady state of ABPG_gain: 328 us,
     // nearly all of it waiting for a compute unit)
-    zero_scalars_kernel<<<1, (xcheck || tiles) ? 512 : 64, 0, h->stream>>>(h->dscal, h->dflag, xcheck, h->n,
+    zero_scalars_kernel<<<1, (xcheck || tiles) ? 512 : 64, 0, h->stream>>>(dscal, dflag, xcheck, h->n,
                                                                          tiles ? h->chol_ready : nullptr, tiles ? T * T + 5 * T : 0,
                                                                          xcheck ? xkeep : nullptr);
     if (tiles) {
-        ACC_TRY(launch_chol_tiles(h, src, A, Winv));
+        ACC_TRY(launch_chol_tiles(h, src, A, Winv, dscal, dflag));
         h->diag_inv_ready = (Winv != nullptr);
         prof_end(h, PROF_CHOL);
         return ACCBPG_OK;
@@ -3068,7 +3072,7 @@ int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xchec
             int nupd = 0;
             if (pend) nupd = (kend >= T - 1) ? R * (R + 1) / 2 : R * (kend - kc);
             chol_step_kernel<<<npanel + nupd, NTHREADS, CHOL_LDS_BYTES, h->stream>>>(
-                A, m, m, kc, pend, kend, T, h->dscal, h->dflag, h->chol_dbg, Winv, h->Tbuf);
+                A, m, m, kc, pend, kend, T, dscal, dflag, h->chol_dbg, Winv, h->Tbuf);
         }
         const int Rr = T - (kend + 1);
         if (Rr > 0)

@@ -301,6 +301,10 @@ struct accbpg_dopt {
     double val_answer = 0.0;        // f of the answered evaluation in flight (from this record or the peer's)
     int val_gen = 0;                // stamp the next compare launch writes when it finds a difference
     int64_t val_compares = 0, val_answered = 0;
+    // accbpg_dopt_burg_trial: the status words of a trial's stages, one slice each (trial_verdict.h), and their pinned
+    // mirror (allocated by the first trial, freed with the handle)
+    double* trial_stat = nullptr;
+    double* trial_pin = nullptr;
     accbpg_dopt* val_peer = nullptr;            // lookups consult this handle's record after the own (read-only)
     std::vector<accbpg_dopt*> val_linked;       // the handles whose val_peer is this one (unlinked by destroy)
     bool prof_on = false;
@@ -359,7 +363,8 @@ int launch_gram(accbpg_dopt* h, const double* x, double* gram);
 int launch_cholesky(accbpg_dopt* h, double* A /* m*m, factor goes here */, double* Winv = nullptr /* diagonal-block inverses */,
                     const double* xcheck = nullptr /* x >= 0 check folded into the reset launch */,
                     const double* src = nullptr /* matrix to factor when it is not A itself */,
-                    double* xkeep = nullptr /* n doubles: receives a copy of xcheck in the same pass */);
+                    double* xkeep = nullptr /* n doubles: receives a copy of xcheck in the same pass */,
+                    double* status = nullptr /* 16 scalars + 8 int flags of this factorisation when not the handle's own */);
 bool chol_tiles_usable(const accbpg_dopt* h);
 int launch_trtri(accbpg_dopt* h);
 int launch_colnorm(accbpg_dopt* h, const double* W, double* out, double sign);
@@ -380,6 +385,14 @@ int64_t vec_ws_doubles(int64_t n);
 // per-(thread, device) scratch of the handle-free entry points: pinned host (32 doubles), device flags (8 ints),
 // device result scalars (16 doubles)
 int vec_scratch(double** pin, int** flags, double** out);
+// the length-n stages of accbpg_dopt_burg_trial: the launches of accbpg_burg_simplex_div_prox (in the form its dispatch
+// picks for n; flags8 = 8 device ints: flags, {bisection, newton}, and at gave_up_idx the multi-workgroup form's give-up
+// word) and of accbpg_ls_terms (out4 = 4 device doubles), enqueued on s with no wait
+int trial_prox_enqueue(const double* y_dev, const double* g_dev, double L, double eps, int64_t n, double* x_out_dev,
+                       double* ws_dev, int* flags8, int gave_up_idx, hipStream_t s, bool* multi);
+void trial_prox_gave_up();
+int trial_ls_terms_enqueue(const double* g_dev, const double* x_dev, const double* y_dev, const double* z_dev,
+                           const double* z1_dev, int64_t n, double* ws_dev, double* out4_dev, hipStream_t s);
 
 // fw_kernels.hip
 int vt_nsplit(int64_t m, int64_t n, int num_cu);

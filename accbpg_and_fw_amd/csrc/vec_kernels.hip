@@ -586,11 +586,16 @@ using namespace accbpg;
 
 extern "C" int64_t accbpg_vec_workspace_doubles(int64_t n) { return vec_ws_doubles(n); }
 
-extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g_dev, double L, double eps,
-                                            int64_t n, double* x_out_dev, double* ws_dev, int* info_host,
-                                            void* stream) {
-    if (!g_dev || !x_out_dev || n <= 0 || !ws_dev) return ACCBPG_ERR_ARG;
-    if (!(L > 0.0)) return ACCBPG_ERR_ASSERT;                 // functions.py:270 / :340
+namespace accbpg {
+// The launch forms of the Burg simplex prox.  prox_plan picks the form of a call: by size, or the one
+// accbpg_debug_prox_variant names.  prox_enqueue makes the launches of that form on s and waits for nothing: the
+// status goes to `flags` (8 device ints: flags 0..3, then {bisection, newton}); the multi-workgroup form raises
+// `gave_up` (a device int its launch zeroes through `flags` or the workspace) when it abandons a wait.
+struct ProxPlan {
+    bool multi, wide;
+    int forced, G;
+};
+static int prox_plan(int64_t n, ProxPlan* p) {
     // the form of this call: by size, or the one accbpg_debug_prox_variant names
     const int forced = g_prox_variant.load(std::memory_order_relaxed);
     bool multi, wide;
@@ -606,27 +611,91 @@ extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g
         set_last_error("accbpg_burg_simplex_div_prox: the forced multi-workgroup form needs more than 128 workgroups");
         return ACCBPG_ERR_ARG;
     }
+    p->multi = multi; p->wide = wide; p->forced = forced; p->G = (int)G64;
+    return ACCBPG_OK;
+}
+// long vectors: several workgroups, each with its slice in registers (ws_dev: exchange slots, then the epoch flags and,
+// unless the caller keeps the give-up word elsewhere -- inside `flags`, which is zeroed here --, that word)
+static int prox_enqueue_multi(const ProxPlan& p, const double* y_dev, const double* g_dev, double L, double eps, int64_t n,
+                              double* x_out_dev, double* ws_dev, int* flags, int* gave_up, hipStream_t s,
+                              int** gave_up_at) {
+    const int G = p.G;
+    int* g_info = flags + 4;
+    ProxMultiShared shm;
+    shm.part = ws_dev;
+    shm.epoch = reinterpret_cast<int*>(ws_dev + 4 * G);
+    shm.abortw = gave_up ? gave_up : shm.epoch + G;
+    ACC_HIP(hipMemsetAsync(ws_dev, 0, sizeof(double) * 4 * G + sizeof(int) * (G + 4), s));
+    ACC_HIP(hipMemsetAsync(flags, 0, 8 * sizeof(int), s));
+    if (p.wide)
+        burg_prox_multi_kernel<32><<<G, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, shm, G, g_info, flags, 20000000LL);
+    else
+        burg_prox_multi_kernel<8><<<G, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, shm, G, g_info, flags, 20000000LL);
+    ACC_HIP(hipGetLastError());
+    g_prox_last[0] = p.wide ? 3 : 2; g_prox_last[1] = G;
+    if (gave_up_at) *gave_up_at = shm.abortw;
+    return ACCBPG_OK;
+}
+static int prox_enqueue_single(int forced, const double* y_dev, const double* g_dev, double L, double eps, int64_t n,
+                               double* x_out_dev, double* ws_dev, int* flags, hipStream_t s) {
+    int* g_info = flags + 4;                                    // {bisection, newton} right behind the flags
+    int ran;
+    if (forced != 1 && n <= (int64_t)PB * 2) {
+        burg_prox_kernel<2><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, flags);
+        ran = 10;
+    } else if (forced != 1 && n <= (int64_t)PB * 8) {
+        burg_prox_kernel<8><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, flags);
+        ran = 11;
+    } else if (forced != 1 && n <= (int64_t)PB * 32) {
+        burg_prox_kernel<32><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, flags);
+        ran = 12;
+    } else {
+        burg_prox_kernel<0><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, flags);
+        ran = 1;
+    }
+    g_prox_last[0] = ran; g_prox_last[1] = 1;
+    ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+
+// The length-n stages of accbpg_dopt_burg_trial (capi.hip): the same launches as accbpg_burg_simplex_div_prox and
+// accbpg_ls_terms make, with their status words at addresses of the caller's and no wait.
+int trial_prox_enqueue(const double* y_dev, const double* g_dev, double L, double eps, int64_t n, double* x_out_dev,
+                       double* ws_dev, int* flags8, int gave_up_idx, hipStream_t s, bool* multi) {
+    ProxPlan p;
+    ACC_TRY(prox_plan(n, &p));
+    *multi = p.multi;
+    if (p.multi)
+        return prox_enqueue_multi(p, y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, flags8, flags8 + gave_up_idx, s, nullptr);
+    return prox_enqueue_single(p.forced, y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, flags8, s);
+}
+void trial_prox_gave_up() { g_prox_multi_off = true; }         // a wait timed out: one workgroup from here on
+int trial_ls_terms_enqueue(const double* g_dev, const double* x_dev, const double* y_dev, const double* z_dev,
+                           const double* z1_dev, int64_t n, double* ws_dev, double* out4_dev, hipStream_t s) {
+    const int nb = red_blocks(n, RMAXBLK);
+    double* part = ws_dev + n;
+    ls_terms_partial_kernel<<<nb, RB, 0, s>>>(g_dev, x_dev, y_dev, z_dev, z1_dev, n, 1, part);
+    ls_terms_final_kernel<<<1, RB, 0, s>>>(part, nb, out4_dev);
+    ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+}  // namespace accbpg
+
+extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g_dev, double L, double eps,
+                                            int64_t n, double* x_out_dev, double* ws_dev, int* info_host,
+                                            void* stream) {
+    if (!g_dev || !x_out_dev || n <= 0 || !ws_dev) return ACCBPG_ERR_ARG;
+    if (!(L > 0.0)) return ACCBPG_ERR_ASSERT;                 // functions.py:270 / :340
+    ProxPlan p;
+    ACC_TRY(prox_plan(n, &p));
     ACC_TRY(ensure_scratch());
     hipStream_t s = (hipStream_t)stream;
-    int* g_info = g_flags + 4;                                  // {bisection, newton} right behind the flags
-    if (multi) {
-        // long vectors: several workgroups, each with its slice in registers (ws_dev: exchange slots, then the flags)
-        const int G = (int)G64;
-        ProxMultiShared shm;
-        shm.part = ws_dev;
-        shm.epoch = reinterpret_cast<int*>(ws_dev + 4 * G);
-        shm.abortw = shm.epoch + G;
-        ACC_HIP(hipMemsetAsync(ws_dev, 0, sizeof(double) * 4 * G + sizeof(int) * (G + 4), s));
-        ACC_HIP(hipMemsetAsync(g_flags, 0, 8 * sizeof(int), s));
-        if (wide)
-            burg_prox_multi_kernel<32><<<G, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, shm, G, g_info, g_flags, 20000000LL);
-        else
-            burg_prox_multi_kernel<8><<<G, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, shm, G, g_info, g_flags, 20000000LL);
-        ACC_HIP(hipGetLastError());
-        g_prox_last[0] = wide ? 3 : 2; g_prox_last[1] = G;
+    if (p.multi) {
+        int* gave_up = nullptr;
+        ACC_TRY(prox_enqueue_multi(p, y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_flags, nullptr, s, &gave_up));
         int* pin_m = reinterpret_cast<int*>(g_pin);
         ACC_HIP(hipMemcpyAsync(pin_m, g_flags, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-        ACC_HIP(hipMemcpyAsync(pin_m + 8, shm.abortw, sizeof(int), hipMemcpyDeviceToHost, s));
+        ACC_HIP(hipMemcpyAsync(pin_m + 8, gave_up, sizeof(int), hipMemcpyDeviceToHost, s));
         ACC_HIP(hipStreamSynchronize(s));
         if (pin_m[8] == 0) {
             if (info_host) { info_host[0] = pin_m[4]; info_host[1] = pin_m[5]; }
@@ -635,22 +704,7 @@ extern "C" int accbpg_burg_simplex_div_prox(const double* y_dev, const double* g
         }
         g_prox_multi_off = true;                                // a wait timed out: one workgroup from here on
     }
-    int ran;
-    if (forced != 1 && n <= (int64_t)PB * 2) {
-        burg_prox_kernel<2><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-        ran = 10;
-    } else if (forced != 1 && n <= (int64_t)PB * 8) {
-        burg_prox_kernel<8><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-        ran = 11;
-    } else if (forced != 1 && n <= (int64_t)PB * 32) {
-        burg_prox_kernel<32><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-        ran = 12;
-    } else {
-        burg_prox_kernel<0><<<1, PB, 0, s>>>(y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_info, g_flags);
-        ran = 1;
-    }
-    g_prox_last[0] = ran; g_prox_last[1] = 1;
-    ACC_HIP(hipGetLastError());
+    ACC_TRY(prox_enqueue_single(p.forced, y_dev, g_dev, L, eps, n, x_out_dev, ws_dev, g_flags, s));
     int* pin_i = reinterpret_cast<int*>(g_pin);
     ACC_HIP(hipMemcpyAsync(pin_i, g_flags, 6 * sizeof(int), hipMemcpyDeviceToHost, s));   // flags + info, one copy
     ACC_HIP(hipStreamSynchronize(s));

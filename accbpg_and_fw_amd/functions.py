@@ -113,6 +113,7 @@ class DOptimalObj(RSmoothFunction):
         # a column shard of a larger instance may have fewer columns than rows
         assert _shard or self.m < self.n, "DOptimalObj: need m < n"
         self._V, _ = to_dev(H)
+        self._is_shard = bool(_shard)
         lib = _lib.load()
         if _borrowed is not None:
             # one instance of a DOptimalBatch: the handle belongs to the batch (kept alive through _owner)
@@ -142,6 +143,9 @@ class DOptimalObj(RSmoothFunction):
         self.gram_combos = 0
         self.value_hits = 0
         self._reuse = True
+        # ABPG_gain's line-search trials go through accbpg_dopt_burg_trial (see one_wait_trials())
+        self._one_wait = True
+        self.one_wait_trials_run = 0
 
     def __del__(self):
         for name in ("_h", "_h2"):
@@ -233,6 +237,56 @@ class DOptimalObj(RSmoothFunction):
             self._lib.accbpg_dopt_value_reuse_stats(h, C.byref(cmp_), C.byref(ans))
             total += ans.value
         return total
+
+    # ---- a whole line-search trial of ABPG_gain enqueued at once and waited for once (on by default) ----
+    def one_wait_trials(self, enable=True):
+        """A trial of ABPG_gain's line search is y, func_grad(y), the prox, x, the three line-search terms and f(x)
+        (accbpg/algorithms.py:369-387).  None of the intermediate results decides what is launched next, so with a
+        BurgEntropySimplex kernel, device iterates and ``checkdiv`` off the solver enqueues the whole trial -- and the
+        lookup that answers F[k] from the value record (``reuse_values``) -- through ``accbpg_dopt_burg_trial`` and
+        waits once instead of five times.  Same launches, bit-identical results, same ``calls`` and ``values_reused``; a
+        trial that is not clean (a flag of any stage) commits nothing and is run again through the stepwise calls,
+        which raise what the stepwise loop raises.  On by default; ``one_wait_trials(False)`` gives the stepwise loop.
+        Not used with ``linear_gram``, ``speculate`` or ``memoize_values``, on a shard or in a batch, or when
+        ``func_grad`` -- or a method of the Burg simplex kernel -- has been wrapped or overridden (the solver then
+        calls it, as before).  After a replay in an iteration whose F[k] rode in the trial the record is gone and F[k]
+        is evaluated in full: ``values_reused`` is then one less than the stepwise loop's.
+        ``one_wait_trials_run`` counts the trials that went through the entry."""
+        self._one_wait = bool(enable)
+        return self
+
+    def _one_wait_ok(self):
+        # (an objective whose func_grad was wrapped on the instance or overridden in a subclass -- instrumentation, a
+        # delay, a counter -- is evaluated through that func_grad, which a native trial would pass by)
+        if "func_grad" in self.__dict__ or type(self).func_grad is not DOptimalObj.func_grad:
+            return False
+        return self._one_wait and self._owned and not self._is_shard and not (self._lin or self._spec or getattr(self, "_memo_on", False))
+
+    def value_recorded(self, x):
+        """True when a value evaluation at the device vector x would find a record at its address (the host-side
+        part of the lookup of ``reuse_values``; the contents are compared on the device)."""
+        return bool(self._lib.accbpg_dopt_value_recorded(self._h, _ptr(x)))
+
+    def trial(self, x_prev, z_prev, theta, L, eps, want_fk):
+        """One trial through accbpg_dopt_burg_trial on the current stream.  None for a trial that has to be replayed
+        stepwise; else (y, g, z, x, TrialOut).  Counts the evaluations of a clean trial as the stepwise calls would,
+        except f(x), which the caller counts when it uses it."""
+        dev = self._V.device
+        y, g, z, x = (torch.empty(self.n, dtype=torch.float64, device=dev) for _ in range(4))
+        out = _lib.TrialOut()
+        with torch.cuda.device(dev):
+            self._lib.accbpg_dopt_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_dopt_burg_trial(self._h, _ptr(x_prev), _ptr(z_prev), float(theta), float(L),
+                                                  float(eps), 1 if want_fk else 0, _ptr(y), _ptr(g), _ptr(z), _ptr(x),
+                                                  _ptr(_Workspace.get(self.n, dev)), C.byref(out))
+        self.one_wait_trials_run += 1
+        if rc == _lib.TRIAL_REPLAY:
+            return None
+        _lib.check(rc, "accbpg_dopt_burg_trial")
+        self.calls["grad"] += 1
+        if out.fk_answered:
+            self.calls["value"] += 1
+        return y, g, z, x, out
 
     def _memo_get(self, x):
         memo = getattr(self, "_memo", None)

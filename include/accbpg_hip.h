@@ -91,12 +91,16 @@ int accbpg_dopt_eval_gap_ms(accbpg_dopt* first, accbpg_dopt* second, double* ms_
  * factorisation always evaluates.
  *   accbpg_dopt_value_reuse(h, on): on = 0 switches lookups and the record off for h, anything else on (the default).
  *   accbpg_dopt_value_reuse_stats: compare launches made and evaluations answered on h since its creation.
+ *   accbpg_dopt_value_recorded(h, x_dev): 1 when h or its peer holds a valid record at the device address x_dev (the
+ *     host-side part of the lookup: no launch, no wait), else 0.  A caller that can ask for the compare inside a larger
+ *     enqueue (accbpg_dopt_burg_trial) learns from it whether that is worth asking.
  *   accbpg_dopt_value_peer(h, peer): lookups on h consult peer's record after h's own (read-only: a handle writes its
  *     own record only; peer's counts while none of ITS flag-0 evaluations is in flight).  Both handles must be over
  *     the same V.  peer = NULL unlinks; destroying either handle unlinks too.  For the two handles of one objective
  *     whose value evaluations alternate between two streams. */
 int accbpg_dopt_value_reuse(accbpg_dopt* h, int on);
 int accbpg_dopt_value_reuse_stats(accbpg_dopt* h, int64_t* compares_host, int64_t* answered_host);
+int accbpg_dopt_value_recorded(accbpg_dopt* h, const double* x_dev);
 int accbpg_dopt_value_peer(accbpg_dopt* h, accbpg_dopt* peer);
 
 /* The same computation in three stages, for design-point sharding across GPUs
@@ -230,6 +234,55 @@ int accbpg_ls_terms(const double* g_dev, const double* x_dev, const double* y_de
  * (algorithms.py:147,150,369,374): two products, one sum, no fused multiply-add. */
 int accbpg_vec_axpby(double a, const double* x_dev, double b, const double* z_dev, int64_t n,
                      double* out_dev, void* stream);
+
+/* One line-search trial of ABPG_gain with BurgEntropySimplex (accbpg/algorithms.py:369-387) enqueued whole on the
+ * handle's stream and waited for ONCE.  None of the intermediate results decides what is launched next -- the launches
+ * depend on theta and L, which the host knows before the trial, and on device vectors -- so the call enqueues, in this
+ * order and with no host wait in between,
+ *   a. if want_fk: the bit-for-bit compare of x_prev against the value record of h or its peer (the lookup of
+ *      accbpg_dopt_func_grad_begin that answers F[k] = f(x_prev), :347) -- only when its host-side part already holds
+ *      (record valid, same device address); otherwise F[k] is "not answered" at no cost,
+ *   b. y = (1-theta) x_prev + theta z_prev                                    (accbpg_vec_axpby, :369)
+ *   c. f(y), g = grad f(y)                                                    (accbpg_dopt_func_grad flag 2, :371)
+ *   d. z = div_prox_map(z_prev, g, L)                                         (accbpg_burg_simplex_div_prox, :373)
+ *   e. x = (1-theta) x_prev + theta z                                         (accbpg_vec_axpby, :374)
+ *   f. <g, x-y>, D(x,y), D(z,z_prev)                                          (accbpg_ls_terms, :377-378, :387)
+ *   g. f(x)                                                                   (accbpg_dopt_func_grad flag 0, :387)
+ *   h. one copy of the stages' status words to pinned memory, one synchronisation of the stream.
+ * The launches are those of the entry points named, in the forms they pick for this m and n: every output is theirs
+ * bit for bit.  L is the prox constant theta^(gamma-1) * G * L of :373, eps the prox tolerance.  y_dev, g_dev, z_dev,
+ * x_dev are n doubles each, distinct from each other and from the inputs; ws_dev as for the vector entry points.  No
+ * accbpg_dopt_func_grad_begin may be waiting for its _end on h.
+ * Returns ACCBPG_OK for a clean trial: out_host is filled, the value record of h is f(x) at x_dev (as after
+ * accbpg_dopt_func_grad_end), and an enqueued compare counts in accbpg_dopt_value_reuse_stats (as answered when
+ * out_host->fk_answered; then out_host->fk is F[k]).  Returns ACCBPG_TRIAL_REPLAY for anything else that is not a HIP
+ * failure -- L <= 0, an entry of y or x negative, a Gram matrix not positive definite, a non-positive entry of z_prev
+ * or of a divergence's arguments, a one-launch factorisation or a multi-workgroup prox that abandoned a wait (the
+ * handle / the process then stays with the fallback form, as the stepwise entry points decide it): nothing is
+ * committed, out_host and the four vectors are unspecified, h keeps no value record and its counters do not move.  The
+ * caller then runs the same trial through the stepwise entry points, which raise what there is to raise.  Because the
+ * record is gone (the value evaluation's reset launch has overwritten its copy of x), an F[k] that rode in a replayed
+ * trial is evaluated in full by the stepwise lookup: the same bits, one answered evaluation fewer than the stepwise
+ * calls alone would have counted.  Nothing is read back before the wait, so the stages behind a flagged one still run,
+ * on whatever that stage left (a NaN ends the prox's scalar loops at once, each of them is bounded by 4096 steps, and
+ * the multi-workgroup wait by its budget): a replayed trial always ends, but may cost more than the stepwise calls,
+ * which stop at the first error.
+ * Where h's own record and its peer's sit at the same address, only h's is compared (accbpg_dopt_func_grad_begin goes on
+ * to the peer's when the contents differ): F[k] is then "not answered" and evaluated.  The event behind
+ * accbpg_dopt_eval_gap_ms is recorded behind the status copy, as by accbpg_dopt_func_grad_begin. */
+#define ACCBPG_TRIAL_REPLAY 5
+typedef struct accbpg_trial_out {
+    double fy;              /* f(y) */
+    double lin, dxy, dzz;   /* <g, x-y>, D(x,y), D(z,z_prev) */
+    double fx;              /* f(x) */
+    double fk;              /* F[k] = f(x_prev) when fk_answered */
+    int32_t prox_info[2];   /* {bisection steps, Newton steps} */
+    int32_t fk_answered;
+    int32_t reserved;
+} accbpg_trial_out;
+int accbpg_dopt_burg_trial(accbpg_dopt* h, const double* x_prev_dev, const double* z_prev_dev, double theta, double L,
+                           double eps, int want_fk, double* y_dev, double* g_dev, double* z_dev, double* x_dev,
+                           double* ws_dev, accbpg_trial_out* out_host);
 
 /* out_host[0] <- <g, x - y>   (algorithms.py:53,168,387,406) */
 int accbpg_vec_dot_diff(const double* g_dev, const double* x_dev, const double* y_dev, int64_t n,

@@ -587,7 +587,15 @@ __global__ __launch_bounds__(NTHREADS, 1) void colnorm_kernel(
 // 2 = diagonal k-steps only, 4 = MFMAs only (no loads, fragment reads, wait or barrier in the loop), 8 = no drain and
 // restart between row blocks (from the second row block on the stages are read without the barrier that orders them
 // behind their loads: a race by design, the variant is for timing only).
-constexpr int COLNORM_CV = 256; // the production gradient kernel: two phases per row block, one pipeline per workgroup
+// With 256 and without 512 (colnorm_phases_body): 1024 = every k-step on the block schedule (the production loop before
+// its k-steps were dealt out), 2048 = the dealt-out placement that production does not use, 4096 = timing ablations of
+// the loop in bits 0..2 (wrong results; Tile::grad_step: 1 = no loads, 2 = no counted wait and no barrier, 4 = no
+// fragment reads), 8192 = the diagonal steps on the block schedule, the rectangular ones dealt out.
+constexpr int COLNORM_CV = 256; // the production gradient kernel: two phases per row block, one pipeline per workgroup,
+                                // the k-steps with at least twelve unconditional pairs of MFMAs per group dealt out
+constexpr int COLNORM_BLOCK = 1024, COLNORM_OTHER_PLACEMENT = 2048, COLNORM_ABLATE = 4096, COLNORM_DIAG_BLOCK = 8192;
+constexpr bool COLNORM_PB = true;   // production's placement of the dealt-out step (Tile::grad_step_dealt)
+constexpr bool colnorm_pb(int cv) { return ((cv & COLNORM_OTHER_PLACEMENT) != 0) != COLNORM_PB; }
 
 // One k-step of the diagonal part of a row block: step j = 4 G + JJ of 16 (columns 16 j .. 16 j + 15 of the 256 x 256
 // diagonal block of W).  Fragment i of wave-row wm covers rows 16 (4 i + wm) .. + 15 of it, so its first live fragment
@@ -595,7 +603,7 @@ constexpr int COLNORM_CV = 256; // the production gradient kernel: two phases pe
 // live for the waves with wm >= JJ.  The loads of the step two ahead go out as in every step; for the last two steps of
 // the row block they are the first two stages of the NEXT row block (base `next_a`, k-steps 0 and 1), whose stage slots
 // are free by the rotation -- the pipeline does not drain between row blocks.
-template <class T, int G, int JJ, int RUN, int NLD>
+template <class T, int G, int JJ, int RUN, int NLD, int CV>
 __device__ __forceinline__ void colnorm_diag_step(T& t, double* __restrict__ lds, int& cur, int wm, int64_t kdiag,
                                                   int64_t ldv, const char* next_a) {
     int nx1 = cur + 1;
@@ -609,17 +617,23 @@ __device__ __forceinline__ void colnorm_diag_step(T& t, double* __restrict__ lds
         k2 = J - 14;
     }
     constexpr int ILO_NEXT = JJ == 3 ? ((G + 1) & 3) : G;
-    t.template grad_step<RUN, G, ILO_NEXT, (JJ > 0), NLD>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE,
-                                                          k2 * BK, k2 * BK * ldv, wm >= JJ);
+    constexpr int AB = (CV & COLNORM_ABLATE) ? (CV & 7) : 0;
+    // dealt out where a group has enough unconditional MFMAs to deal behind: steps 0..4 of the sixteen
+    if constexpr (!(CV & (COLNORM_BLOCK | COLNORM_DIAG_BLOCK)) && T::template dealt_pairs_per_group<G, (JJ > 0)>() >= 12)
+        t.template grad_step_dealt<RUN, G, ILO_NEXT, (JJ > 0), NLD, colnorm_pb(CV), AB>(
+            lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE, k2 * BK, k2 * BK * ldv, wm >= JJ);
+    else
+        t.template grad_step<RUN, G, ILO_NEXT, (JJ > 0), NLD, AB>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE,
+                                                                  k2 * BK, k2 * BK * ldv, wm >= JJ);
     cur = nx1;
 }
-template <class T, int G, int RUN, int NLD>
+template <class T, int G, int RUN, int NLD, int CV>
 __device__ __forceinline__ void colnorm_diag_group(T& t, double* __restrict__ lds, int& cur, int wm, int64_t kdiag,
                                                    int64_t ldv, const char* next_a) {
-    colnorm_diag_step<T, G, 0, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
-    colnorm_diag_step<T, G, 1, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
-    colnorm_diag_step<T, G, 2, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
-    colnorm_diag_step<T, G, 3, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 0, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 1, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 2, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
+    colnorm_diag_step<T, G, 3, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
 }
 
 // The production loop.  Row block rb = 16 rb rectangular k-steps (every fragment row live: one basic block of 128 MFMAs
@@ -627,7 +641,9 @@ __device__ __forceinline__ void colnorm_diag_group(T& t, double* __restrict__ ld
 // pipeline per workgroup: three stages rotate through all row blocks, the full-latency wait happens once, and the squares
 // of a row block and the zeroing of the accumulators run while the first two stages of the next one are in flight.
 // Every accumulator receives the MFMAs it received before, in the same k order, and colsum is added to in the same order.
-template <class T>
+// The rectangular k-steps and diagonal steps 0..4 are dealt out (Tile::grad_step_dealt) unless CV & COLNORM_BLOCK, the other
+// diagonal steps run the block schedule (Tile::grad_step), and the two hand the pipeline to each other.
+template <class T, int CV>
 __device__ __forceinline__ void colnorm_phases_body(
     const double* __restrict__ W, int64_t ldw, const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n,
     double* __restrict__ out, double sign) {
@@ -635,6 +651,8 @@ __device__ __forceinline__ void colnorm_phases_body(
     double* red = lds + 3 * T::G_STAGE;                         // [4][BN] behind the stages
     constexpr int NLD = T::G_NA + T::G_NB;
     constexpr int RUN = 4;                                      // loads per M0 write (mfma_tile.hpp: glds16_run4)
+    constexpr int AB = (CV & COLNORM_ABLATE) ? (CV & 7) : 0;    // timing ablations (wrong results)
+    constexpr bool PB = colnorm_pb(CV);
     static_assert(T::WAVES_N == 1 && T::MI == 4 && T::BM == 16 * BK, "diagonal groups are laid out for the 256 x 128 tile");
     const int64_t col0 = (int64_t)blockIdx.x * T::BN;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -654,6 +672,7 @@ __device__ __forceinline__ void colnorm_phases_body(
     __builtin_amdgcn_s_barrier();
     int cur = 0;
     t.template read_frag_lo<0, 0>(lds, 0);
+    if constexpr (AB & 4) t.template read_frag_lo<1, 0>(lds, 1);   // (no reads in the loop: both fragment sets hold something)
     t.zero();
     t.pin_acc();
     // The loop over the row blocks is rotated: a trip is the diagonal phase of row block rb, its squares, and the
@@ -665,10 +684,10 @@ __device__ __forceinline__ void colnorm_phases_body(
         // retires the same number of loads in every step)
         const int rbn = rb + 1 < nrb ? rb + 1 : rb;
         const char* next_a = reinterpret_cast<const char*>(W + (int64_t)rbn * T::BM * ldw);
-        colnorm_diag_group<T, 0, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
-        colnorm_diag_group<T, 1, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
-        colnorm_diag_group<T, 2, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
-        colnorm_diag_group<T, 3, RUN, NLD>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 0, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 1, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 2, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
+        colnorm_diag_group<T, 3, RUN, NLD, CV>(t, lds, cur, wm, kdiag, ldv, next_a);
         // square and add this row block's Y into the per-column sums; the next row block's stages are in flight
 #pragma unroll
         for (int j = 0; j < T::NI; ++j) {
@@ -696,8 +715,12 @@ __device__ __forceinline__ void colnorm_phases_body(
             int nx2 = cur + 2;
             if (nx2 >= 3) nx2 -= 3;
             const int64_t k2 = (ks + 2) * BK;
-            t.template grad_step<RUN, 0, 0, false, NLD>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE,
-                                                        k2, k2 * ldv, true);
+            if constexpr (CV & COLNORM_BLOCK)
+                t.template grad_step<RUN, 0, 0, false, NLD, AB>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE, lds + nx2 * T::G_STAGE,
+                                                                k2, k2 * ldv, true);
+            else
+                t.template grad_step_dealt<RUN, 0, 0, false, NLD, PB, AB>(lds + cur * T::G_STAGE, lds + nx1 * T::G_STAGE,
+                                                                          lds + nx2 * T::G_STAGE, k2, k2 * ldv, true);
             cur = nx1;
         } while (++ks < krect);
     }
@@ -903,7 +926,7 @@ template <class T, int CV = 0>
 __device__ __forceinline__ void colnorm_glds_body(
     const double* __restrict__ W, int64_t ldw, const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n,
     double* __restrict__ out, double sign) {
-    if constexpr (CV == COLNORM_CV) colnorm_phases_body<T>(W, ldw, V, ldv, m, n, out, sign);
+    if constexpr ((CV & 256) && !(CV & 512)) colnorm_phases_body<T, CV>(W, ldw, V, ldv, m, n, out, sign);
     else colnorm_restart_body<T, CV>(W, ldw, V, ldv, m, n, out, sign);
 }
 
@@ -3230,12 +3253,16 @@ int launch_trtri_batch(accbpg_dopt_batch* b, const BatchAct& act) {
 // timing ablations of the gradient kernel (big interior tile, direct-to-LDS only); returns average ms over `iters`.
 // var: 0 = production, 3 = the schedule before the two phases, 10..13 = that schedule with rectangular k-steps only /
 // diagonal k-steps only / MFMAs only / no drain and restart between row blocks (10..13 write wrong results to `out`).
+// 4 = the two-phase loop with every k-step on the block schedule (production before its k-steps were dealt out), 5 = the
+// dealt-out step in the placement production does not use, 6 = only the rectangular k-steps dealt out (4, 5, 6 write
+// what production writes).  20..23 = ablations of 4, 30..33 = of production: MFMAs only / MFMAs and the direct-to-LDS
+// loads / MFMAs and the fragment reads / everything but the counted wait and the barrier (wrong results in `out`).
 int debug_grad_variant(accbpg_dopt* h, double* out, int var, int iters, double* ms_out) {
     using T = TileBig<true, false>;
     const bool vw = ((reinterpret_cast<uintptr_t>(h->Wbuf) & 15) == 0) && ((h->m & 1) == 0);
     if (!h->big || !h->use_glds || !vw || !h->vec_ok || h->m % 256 != 0 || h->n % 128 != 0) return ACCBPG_ERR_ARG;
     const int grid = (int)(h->n / T::BN), lds = T::G_LDS_BYTES + 4 * T::BN * 8;
-    if (var != 0 && var != 3 && (var < 10 || var > 13)) return ACCBPG_ERR_ARG;
+    if (var != 0 && (var < 3 || var > 6) && (var < 10 || var > 13) && (var < 20 || var > 23) && (var < 30 || var > 33)) return ACCBPG_ERR_ARG;
     hipEvent_t a, b;
     ACC_HIP(hipEventCreate(&a));
     if (hipEventCreate(&b) != hipSuccess) {
@@ -3252,6 +3279,17 @@ int debug_grad_variant(accbpg_dopt* h, double* out, int var, int iters, double* 
             case 11: ACC_LAUNCH_C(COLNORM_CV | 512 | 2); break;
             case 12: ACC_LAUNCH_C(COLNORM_CV | 512 | 4); break;
             case 13: ACC_LAUNCH_C(COLNORM_CV | 512 | 8); break;
+            case 4: ACC_LAUNCH_C(COLNORM_CV | COLNORM_BLOCK); break;
+            case 5: ACC_LAUNCH_C(COLNORM_CV | COLNORM_OTHER_PLACEMENT); break;
+            case 6: ACC_LAUNCH_C(COLNORM_CV | COLNORM_DIAG_BLOCK); break;
+            case 20: ACC_LAUNCH_C(COLNORM_CV | COLNORM_BLOCK | COLNORM_ABLATE | 7); break;
+            case 21: ACC_LAUNCH_C(COLNORM_CV | COLNORM_BLOCK | COLNORM_ABLATE | 6); break;
+            case 22: ACC_LAUNCH_C(COLNORM_CV | COLNORM_BLOCK | COLNORM_ABLATE | 3); break;
+            case 23: ACC_LAUNCH_C(COLNORM_CV | COLNORM_BLOCK | COLNORM_ABLATE | 2); break;
+            case 30: ACC_LAUNCH_C(COLNORM_CV | COLNORM_ABLATE | 7); break;
+            case 31: ACC_LAUNCH_C(COLNORM_CV | COLNORM_ABLATE | 6); break;
+            case 32: ACC_LAUNCH_C(COLNORM_CV | COLNORM_ABLATE | 3); break;
+            case 33: ACC_LAUNCH_C(COLNORM_CV | COLNORM_ABLATE | 2); break;
             default: return ACCBPG_ERR_ARG;
         }
 #undef ACC_LAUNCH_C

@@ -553,36 +553,129 @@ struct Tile {
     // (element offsets ka / kb from the current bases) go to `nst` between the fragment rows of group 0, and the first
     // fragments of the next step (stage `st1`, first live row ILO_NEXT) are read under the last group's MFMAs.  The
     // counted wait leaves the NLD newest loads in flight, so it carries from step to step and across row blocks.
-    template <int RUN, int ILO, int ILO_NEXT, bool COND, int NLD>
+    // AB: timing ablations (wrong results; accbpg_debug_grad_variant only): 1 = no loads, 2 = no counted wait and no
+    // barrier, 4 = no fragment reads.
+    template <int RUN, int ILO, int ILO_NEXT, bool COND, int NLD, int AB = 0>
     __device__ __forceinline__ void grad_step(const double* __restrict__ st, const double* __restrict__ st1,
                                               double* __restrict__ nst, int64_t ka, int64_t kb, bool live) {
         constexpr int NP = G_NA + G_NB;
         constexpr int P1 = (NP + 2) / 3, P2 = 2 * P1 < NP ? 2 * P1 : NP;
         static_assert(NLD == NP, "every wave retires the loads of one step per step");
-        read_frag_lo<1, ILO>(st, 1);
+        if constexpr (!(AB & 4)) read_frag_lo<1, ILO>(st, 1);
         __builtin_amdgcn_sched_barrier(0);
         mma_row_lo<0, 0, ILO, COND>(live);
-        glds_issue_range<RUN>(ka, kb, nst, 0, P1);
+        if constexpr (!(AB & 1)) glds_issue_range<RUN>(ka, kb, nst, 0, P1);
         mma_row_lo<0, 1, ILO, COND>(live);
-        glds_issue_range<RUN>(ka, kb, nst, P1, P2);
+        if constexpr (!(AB & 1)) glds_issue_range<RUN>(ka, kb, nst, P1, P2);
         mma_row_lo<0, 2, ILO, COND>(live);
-        glds_issue_range<RUN>(ka, kb, nst, P2, NP);
+        if constexpr (!(AB & 1)) glds_issue_range<RUN>(ka, kb, nst, P2, NP);
         mma_row_lo<0, 3, ILO, COND>(live);
         __builtin_amdgcn_sched_barrier(0);
-        read_frag_lo<0, ILO>(st, 2);
+        if constexpr (!(AB & 4)) read_frag_lo<0, ILO>(st, 2);
         __builtin_amdgcn_sched_barrier(0);
         mma_frag_lo<1, ILO, COND>(live);
         __builtin_amdgcn_sched_barrier(0);
-        read_frag_lo<1, ILO>(st, 3);
+        if constexpr (!(AB & 4)) read_frag_lo<1, ILO>(st, 3);
         __builtin_amdgcn_sched_barrier(0);
         mma_frag_lo<0, ILO, COND>(live);
         __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
-        __builtin_amdgcn_s_barrier();
-        read_frag_lo<0, ILO_NEXT>(st1, 0);
+        if constexpr (!(AB & 2)) {
+            asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        if constexpr (!(AB & 4)) read_frag_lo<0, ILO_NEXT>(st1, 0);
         __builtin_amdgcn_sched_barrier(0);
         mma_frag_lo<1, ILO, COND>(live);
         __builtin_amdgcn_sched_barrier(0);
+    }
+
+    // The same k-step dealt out, for the steps with at least twelve unconditional pairs of MFMAs per fragment group (the
+    // rectangular phase, where every fragment row is live, and the first five steps of the diagonal phase): nothing is
+    // issued as a block at a group boundary.  Behind a pair goes at most ONE small thing -- a part of the next group's
+    // fragment reads (DEALT_PART_VALUES LDS reads) or one run of RUN loads of the step two ahead -- so that it issues in
+    // the shadow of the 128 cycles the pair keeps the matrix pipe busy.  Row ILO of a COND step stays one block of eight
+    // MFMAs behind its condition, in front of the group's NU unconditional pairs, with nothing dealt into it.  The
+    // counted wait and the barrier sit inside the last group, in front of pair QBAR, and group 0 of the next stage is
+    // read behind them under the rest of that group.  Placement B (PB): reads behind the first pairs of a group (1..6
+    // of 16, 0..5 of 12), loads of group 0 behind pairs NU/2, +2, +4, barrier behind the first quarter; otherwise reads
+    // behind the odd pairs 1..11, loads behind pairs 0, 4, 8, barrier in the middle of the group.  The MFMAs of an
+    // accumulator and their k order are those of grad_step, a wave issues the same NLD loads per step, and the step
+    // hands over what that one does (set 0 holds group 0 of `st1` from row ILO_NEXT on), so the two can follow each
+    // other in one pipeline.  Plain member templates.
+    static constexpr int DEALT_PART_VALUES = 2;                 // fragment values one part of read_part_g reads
+    // part PART of read_part_g without the A rows below ILO
+    template <int SET, int PART, int ILO>
+    __device__ __forceinline__ void read_part_lo(const double* __restrict__ stage, int kk) {
+        if constexpr (PART == 1 || PART == 6) {
+            const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+            const int wm = wave / WAVES_N;
+            const int lr = lane & 15, lq = lane >> 4;
+            const int sw = (lr >> 1) & 7;
+            const int koff = 2 * ((2 * kk + (lq >> 1)) ^ sw) + (lq & 1);
+            const double* as = stage + (16 * wm + lr) * BK + koff;
+            constexpr int i0 = (PART == 1) ? 0 : 2;
+            if constexpr (i0 >= ILO) fa[SET][i0] = as[i0 * 16 * WAVES_M * BK];
+            if constexpr (i0 + 1 >= ILO) fa[SET][i0 + 1] = as[(i0 + 1) * 16 * WAVES_M * BK];
+        } else {
+            read_part_g<SET, false, PART>(stage, kk);
+        }
+    }
+    template <int RUN, int ILO, int ILO_NEXT, int NU, bool PB, int AB, int G, int U>
+    __device__ __forceinline__ void dealt_behind(const double* __restrict__ st, const double* __restrict__ st1,
+                                                 double* __restrict__ nst, int64_t ka, int64_t kb) {
+        constexpr int NP = G_NA + G_NB;
+        constexpr int QBAR = PB ? NU / 4 : NU / 2;
+        if constexpr (G < 3) {
+            // read part behind this pair (part 0, x, does not exist here)
+            constexpr int rp = PB ? U + (NU == 16 ? 0 : 1) : (((U & 1) == 1) ? (U >> 1) + 1 : -1);
+            if constexpr (rp >= 1 && rp < 7 && !(AB & 4)) read_part_lo<(G & 1) ^ 1, (rp >= 1 && rp < 7) ? rp : 1, ILO>(st, G + 1);
+            constexpr int lp = PB ? U - NU / 2 : (((U & 1) == 0) ? (U >> 1) : -1);   // load slot (two pieces) behind this pair
+            if constexpr (G == 0 && lp >= 0 && 2 * lp < NP && (2 * lp) % RUN == 0 && !(AB & 1))
+                glds_issue_range<RUN>(ka, kb, nst, 2 * lp, 2 * lp + RUN);
+        } else {
+            constexpr int rp = U - QBAR + 1;
+            if constexpr (rp >= 1 && rp < 7 && !(AB & 4)) read_part_lo<0, (rp >= 1 && rp < 7) ? rp : 1, ILO_NEXT>(st1, 0);
+        }
+    }
+    template <int RUN, int ILO, int ILO_NEXT, int NU, bool PB, int AB, int NLD, int G, int U>
+    __device__ __forceinline__ void dealt_pairs(const double* __restrict__ st, const double* __restrict__ st1,
+                                                double* __restrict__ nst, int64_t ka, int64_t kb) {
+        if constexpr (U < NU) {
+            if constexpr (G == 3 && U == (PB ? NU / 4 : NU / 2) && !(AB & 2)) {
+                // stage st1 (issued one step ago) has landed: all but the newest NLD loads done; lgkmcnt(0): this wave's
+                // reads of stage st are complete before others may overwrite it
+                asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            mma_pair<(G & 1), (MI - NU / 4 + U / 4), (U % 4)>();
+            __builtin_amdgcn_sched_barrier(0);
+            dealt_behind<RUN, ILO, ILO_NEXT, NU, PB, AB, G, U>(st, st1, nst, ka, kb);
+            __builtin_amdgcn_sched_barrier(0);
+            dealt_pairs<RUN, ILO, ILO_NEXT, NU, PB, AB, NLD, G, U + 1>(st, st1, nst, ka, kb);
+        }
+    }
+    template <int ILO, bool COND>
+    static constexpr int dealt_pairs_per_group() { return 4 * (MI - ILO - (COND ? 1 : 0)); }
+    template <int RUN, int ILO, int ILO_NEXT, bool COND, int NLD, bool PB, int AB = 0>
+    __device__ __forceinline__ void grad_step_dealt(const double* __restrict__ st, const double* __restrict__ st1,
+                                                    double* __restrict__ nst, int64_t ka, int64_t kb, bool live) {
+        constexpr int NU = dealt_pairs_per_group<ILO, COND>();
+        static_assert(MI == 4 && NI == 8 && BKM, "pairs and parts are laid out for the 64 x 128 wave tile, k-major B");
+        static_assert(NLD == G_NA + G_NB && (G_NA + G_NB) % RUN == 0 && RUN % 2 == 0, "every wave retires the loads of one step per step, in whole runs");
+        static_assert(NU >= 12 && (G_NA + G_NB) / 2 <= 6, "one thing behind a pair: six read parts, and the loads behind the second half of group 0");
+        __builtin_amdgcn_sched_barrier(0);
+        mma_row_lo<0, ILO, COND ? ILO : MI, COND>(live);            // (row ILO behind its condition; nothing without COND)
+        __builtin_amdgcn_sched_barrier(0);
+        dealt_pairs<RUN, ILO, ILO_NEXT, NU, PB, AB, NLD, 0, 0>(st, st1, nst, ka, kb);
+        mma_row_lo<1, ILO, COND ? ILO : MI, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
+        dealt_pairs<RUN, ILO, ILO_NEXT, NU, PB, AB, NLD, 1, 0>(st, st1, nst, ka, kb);
+        mma_row_lo<0, ILO, COND ? ILO : MI, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
+        dealt_pairs<RUN, ILO, ILO_NEXT, NU, PB, AB, NLD, 2, 0>(st, st1, nst, ka, kb);
+        mma_row_lo<1, ILO, COND ? ILO : MI, COND>(live);
+        __builtin_amdgcn_sched_barrier(0);
+        dealt_pairs<RUN, ILO, ILO_NEXT, NU, PB, AB, NLD, 3, 0>(st, st1, nst, ka, kb);
     }
 
     // ---- "dual" diagonal tile (Gram matrix only) ---------------------------------------------

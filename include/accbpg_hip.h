@@ -661,7 +661,11 @@ int accbpg_debug_gram_variant(accbpg_dopt* h, const double* x_dev, int variant, 
 /* The same for the direct-to-LDS gradient kernel, on the inverse factor the handle holds from its last gradient
  * evaluation: variant 0 = the product kernel, 3 = its schedule before the k loop was split into phases, 10..13 = that
  * schedule with rectangular k-steps only / diagonal k-steps only / MFMAs only / no drain and restart between row
- * blocks (wrong data).  g_dev (n doubles) receives what the launches write. */
+ * blocks (wrong data); 4 = the product kernel with every k-step on the block schedule (reads and loads issued as
+ * blocks, as before they were dealt out between the MFMAs), 5 = dealt out in the placement the product kernel does not
+ * use, 6 = only the rectangular k-steps dealt out (4, 5, 6: same bits as 0); 20..23 / 30..33 = variant 4 / variant 0
+ * with MFMAs only / MFMAs and loads / MFMAs and fragment reads / everything but the counted wait and the barrier
+ * (wrong data).  g_dev (n doubles) receives what the launches write. */
 int accbpg_debug_grad_variant(accbpg_dopt* h, double* g_dev, int variant, int iters, double* ms_host);
 /* For a handle whose evaluations run BESIDE another stream's MFMA-bound launches (the value evaluation the solvers
  * start next to a gradient evaluation, accbpg/algorithms.py:135 beside :148): factor with one launch per 64-wide

@@ -746,49 +746,23 @@ _LMO_FILL = 1e-15       # lmo_simplex's entry away from the vertex (functions_lm
 REFRESH_DEFAULT = 256   # steps between two re-initialisations of (H, w, log det) from x
 
 
-class _FWDivState(_FWState):
-    """The Frank-Wolfe state plus what the Bregman-step solvers keep beside it: ``ld`` the log det of the tracked Gram
-    matrix, ``q`` the floor mass not in it, ``since`` the steps since the last initialisation."""
+class _DivBook:
+    """What the Bregman-step solvers keep beside one instance's Frank-Wolfe state, in host scalars: ``ld`` the log det
+    of the tracked Gram matrix, ``q`` the floor mass not in it, ``since`` the steps since the last initialisation.
+    Touches no device: the single and the lock-step solvers keep one per instance."""
 
-    def __init__(self, f, x0, radius, refresh):
-        super().__init__(f, x0)
+    def __init__(self, m, radius, refresh, logdet):
+        self.m = m
         self.radius = float(radius)
         self.refresh = int(refresh)
-        self.ld, self.q, self.since = self.logdet_gram, 0.0, 0
+        self.reset(logdet)
 
-    def x_dev(self):
-        out = torch.empty(self.n, dtype=torch.float64, device=self.obj.device)
-        with torch.cuda.device(self.obj.device):
-            rc = self.lib.accbpg_fw_get_state(self.h, _ptr(out), None, None)
-        _lib.check(rc, "accbpg_fw_get_state")
-        return out
+    def reset(self, logdet):
+        """(H, w, log det) were recomputed from x."""
+        self.ld, self.q, self.since = logdet, 0.0, 0
 
-    def x(self):
-        return from_dev(self.x_dev(), self.as_numpy)
-
-    def reinit(self, xd):
-        """(H, w, log det) afresh from the device vector xd; a singular Gram matrix is DOptimalObj's ValueError."""
-        logdet = C.c_double(0.0)
-        with torch.cuda.device(self.obj.device):
-            self.lib.accbpg_dopt_set_stream(self.h, _stream())
-            rc = self.lib.accbpg_fw_init(self.h, _ptr(xd), C.byref(logdet))
-        _lib.check(rc, "accbpg_fw_init")
-        self.ld, self.q, self.since = logdet.value, 0.0, 0
-
-    def refresh_if_due(self):
-        if self.refresh and self.since == self.refresh:
-            self.reinit(self.x_dev())
-
-    def probe_div(self):
-        rec = _lib.FwDivProbe()
-        if self._on_device():
-            rc = self.lib.accbpg_fw_div_probe_step(self.h, _LMO_FILL, self.radius, C.byref(rec))
-        else:
-            with torch.cuda.device(self.obj.device):
-                rc = self.lib.accbpg_fw_div_probe_step(self.h, _LMO_FILL, self.radius, C.byref(rec))
-        if rc:
-            _lib.check(rc, "accbpg_fw_div_probe_step")
-        return rec
+    def refresh_due(self):
+        return bool(self.refresh) and self.since == self.refresh
 
     def value(self, rec):
         """f(x) = -log det(V X V^T): the tracked part, and the dense floor term q V V^T to first order (tr(H V V^T) =
@@ -808,23 +782,187 @@ class _FWDivState(_FWState):
         f1 = -ld1 - q1 * sw1
         return hcoef, hdiv, ld1, q1, f1
 
-    def apply(self, rec, a, hcoef, hdiv, ld1, q1):
-        if self._on_device():
-            rc = self.lib.accbpg_fw_div_apply(self.h, rec.i, a, _LMO_FILL, self.radius, hcoef, hdiv)
-        else:
-            with torch.cuda.device(self.obj.device):
-                rc = self.lib.accbpg_fw_div_apply(self.h, rec.i, a, _LMO_FILL, self.radius, hcoef, hdiv)
-        if rc:
-            _lib.check(rc, "accbpg_fw_div_apply")
+    def stepped(self, ld1, q1):
+        """A rank-one step with these scalars was applied."""
         self.ld, self.q = ld1, q1
         self.since += 1
 
-    def full_step(self, rec):
-        """x + 1.0 * (s - x) with the vector kernels of the generic solver (the capped step a == 1)."""
-        xd = self.x_dev()
-        vertex = vec_vertex(rec.i, self.radius, _LMO_FILL, self.n, xd.device)
-        towards = vec_axpby(1.0, vertex, -1.0, xd)
-        return vec_axpby(1.0, xd, 1.0, towards)
+
+class _DivStepRun:
+    """The host side of one instance of D_opt_FW_div_step: from a probe record to what to do next.  One copy for the
+    single and the lock-step solver (as ``_fw_decide`` and ``_AwayRun`` are for theirs)."""
+
+    def __init__(self, book, L, maxitrs, gamma, epsilon, linesearch, ls_ratio):
+        self.book = book
+        self.L, self.gamma, self.epsilon, self.linesearch, self.ls_ratio = L, gamma, epsilon, linesearch, ls_ratio
+        self.F = np.zeros(maxitrs)
+        self.Ls = np.zeros(maxitrs)
+        self.T = np.zeros(maxitrs)
+        self.done = 0
+
+    def decide(self, k, rec, now, capped):
+        """Iteration k from its probe record.  ``capped(rec)`` builds the trial of the capped step a == 1 and returns
+        (trial, f(trial)) -- a full evaluation, as the generic solver's; f is not read without the line search -- and is
+        called once per trial at the cap.  Returns (step, trial, stop): step = (p, a, hcoef, hdiv) of the rank-one step
+        to apply (the book is advanced here) and trial None, or step None and the trial to re-initialise from (then
+        ``book.reset``); stop: the stop test holds, this step is the last."""
+        book, linesearch, gamma = self.book, self.linesearch, self.gamma
+        fx = book.value(rec)
+        self.F[k] = fx
+        self.T[k] = now
+
+        div = rec.div if rec.div != 0 else _SLOPE_FLOOR
+        slope = rec.slope
+        if 0 < slope <= _SLOPE_FLOOR:
+            slope = 0.0
+        if slope > 0:
+            raise ValueError("grad_d_prod must be non-positive")
+        assert rec.min_x > 0, "Entries of x or y not positive."
+
+        L = self.L
+        if linesearch:
+            L = L / self.ls_ratio
+        while True:
+            a = _step_length(slope, L, div, gamma)
+            trial = None
+            if a < 1:
+                hcoef, hdiv, ld1, q1, f1 = book.scalars(a, rec)
+            else:                                               # the cap: a full evaluation, as the generic solver's
+                trial, f1 = capped(rec)
+            if not linesearch:
+                break
+            assert not math.isinf(L), "L is infinite"
+            if f1 <= fx + a * slope + a ** gamma * L * div:
+                break
+            L = L * self.ls_ratio
+
+        self.L = L
+        self.Ls[k] = L
+        self.done = k + 1
+        stop = k > 0 and abs(self.F[k] - self.F[k - 1]) < self.epsilon
+        if trial is not None:
+            return None, trial, stop
+        book.stepped(ld1, q1)
+        return (rec.i, a, hcoef, hdiv), None, stop
+
+    def result(self, x):
+        e = self.done
+        return x, self.F[:e].copy(), self.Ls[:e].copy(), self.T[:e].copy()
+
+
+class _DescentRun:
+    """The host side of one instance of D_opt_FW_descent_step (one copy for the single and the lock-step solver): the
+    step of iteration k from the record of the probe before it, the stop test from the record after it."""
+
+    def __init__(self, book, maxitrs, epsilon):
+        self.book = book
+        self.epsilon = epsilon
+        self.F = np.zeros(maxitrs)
+        self.G = np.zeros(maxitrs)
+        self.T = np.zeros(maxitrs)
+        self.k = 0
+        self.rec = None
+
+    def first(self, rec, now):
+        self.rec = rec
+        self.F[0] = self.book.value(rec)
+        self.T[0] = now
+
+    def step(self, k):
+        """(p, alpha, hcoef, hdiv) of the step of iteration k; the book is advanced here."""
+        self.k = k
+        self.alpha = 2 / (k + 2)
+        hcoef, hdiv, ld1, q1, _ = self.book.scalars(self.alpha, self.rec)
+        self.book.stepped(ld1, q1)
+        return self.rec.i, self.alpha, hcoef, hdiv
+
+    def probed(self, k, rec, now):
+        """The record of the probe behind step k; True when the stop test holds."""
+        self.rec = rec
+        self.F[k] = self.book.value(rec)
+        self.T[k] = now
+        return abs(self.F[k] - self.F[k - 1]) < self.epsilon or math.sqrt(rec.sum_w2) < self.epsilon
+
+    def result(self, x):
+        e = self.k + 1
+        return x, self.F[:e].copy(), self.T[:e].copy(), self.G[:e].copy()
+
+
+def _capped_trial(obj, xd, p, radius, valued):
+    """The capped step a == 1 from the device vector xd on the objective ``obj``: x + 1.0 * (s - x) with the vector
+    kernels of the generic solver, and its value by a full evaluation when ``valued``.  Returns (trial, f or None)."""
+    vertex = vec_vertex(p, radius, _LMO_FILL, xd.numel(), xd.device)
+    towards = vec_axpby(1.0, vertex, -1.0, xd)
+    trial = vec_axpby(1.0, xd, 1.0, towards)
+    return trial, (obj.func_grad(trial, flag=0) if valued else None)
+
+
+class _FWDivState(_FWState):
+    """The Frank-Wolfe state of one handle plus the book of the Bregman-step solvers (``ld``, ``q``, ``since``)."""
+
+    def __init__(self, f, x0, radius, refresh):
+        super().__init__(f, x0)
+        self.radius = float(radius)
+        self.book = _DivBook(self.m, radius, refresh, self.logdet_gram)
+
+    ld = property(lambda self: self.book.ld)
+    q = property(lambda self: self.book.q)
+    since = property(lambda self: self.book.since)
+
+    def x_dev(self):
+        out = torch.empty(self.n, dtype=torch.float64, device=self.obj.device)
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_get_state(self.h, _ptr(out), None, None)
+        _lib.check(rc, "accbpg_fw_get_state")
+        return out
+
+    def x(self):
+        return from_dev(self.x_dev(), self.as_numpy)
+
+    def reinit(self, xd):
+        """(H, w, log det) afresh from the device vector xd; a singular Gram matrix is DOptimalObj's ValueError."""
+        logdet = C.c_double(0.0)
+        with torch.cuda.device(self.obj.device):
+            self.lib.accbpg_dopt_set_stream(self.h, _stream())
+            rc = self.lib.accbpg_fw_init(self.h, _ptr(xd), C.byref(logdet))
+        _lib.check(rc, "accbpg_fw_init")
+        self.book.reset(logdet.value)
+
+    def refresh_if_due(self):
+        if self.book.refresh_due():
+            self.reinit(self.x_dev())
+
+    def probe_div(self):
+        rec = _lib.FwDivProbe()
+        if self._on_device():
+            rc = self.lib.accbpg_fw_div_probe_step(self.h, _LMO_FILL, self.radius, C.byref(rec))
+        else:
+            with torch.cuda.device(self.obj.device):
+                rc = self.lib.accbpg_fw_div_probe_step(self.h, _LMO_FILL, self.radius, C.byref(rec))
+        if rc:
+            _lib.check(rc, "accbpg_fw_div_probe_step")
+        return rec
+
+    def scalars(self, a, rec):
+        return self.book.scalars(a, rec)
+
+    def apply_step(self, p, a, hcoef, hdiv):
+        """The device side of a rank-one step (the book is the caller's)."""
+        if self._on_device():
+            rc = self.lib.accbpg_fw_div_apply(self.h, p, a, _LMO_FILL, self.radius, hcoef, hdiv)
+        else:
+            with torch.cuda.device(self.obj.device):
+                rc = self.lib.accbpg_fw_div_apply(self.h, p, a, _LMO_FILL, self.radius, hcoef, hdiv)
+        if rc:
+            _lib.check(rc, "accbpg_fw_div_apply")
+
+    def apply(self, rec, a, hcoef, hdiv, ld1, q1):
+        self.apply_step(rec.i, a, hcoef, hdiv)
+        self.book.stepped(ld1, q1)
+
+    def capped(self, rec, valued):
+        """(trial, f(trial) or None) of the capped step a == 1 from the current x."""
+        return _capped_trial(self.obj, self.x_dev(), rec.i, self.radius, valued)
 
 
 def D_opt_FW_div_step(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2,
@@ -846,57 +984,23 @@ def D_opt_FW_div_step_steps(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=
         print("     k      F(x)         Lk       time")
 
     t_start = time.time()
-    F = np.zeros(maxitrs)
-    Ls = np.zeros(maxitrs)
-    T = np.zeros(maxitrs)
-
     st = _FWDivState(f, x0, radius, refresh)
-    done = 0
+    run = _DivStepRun(st.book, L, maxitrs, gamma, epsilon, linesearch, ls_ratio)
     for k in range(maxitrs):
         st.refresh_if_due()
         rec = st.probe_div()
-        fx = st.value(rec)
-        F[k] = fx
-        T[k] = time.time() - t_start
-
-        div = rec.div if rec.div != 0 else _SLOPE_FLOOR
-        slope = rec.slope
-        if 0 < slope <= _SLOPE_FLOOR:
-            slope = 0.0
-        if slope > 0:
-            raise ValueError("grad_d_prod must be non-positive")
-        assert rec.min_x > 0, "Entries of x or y not positive."
-
-        if linesearch:
-            L = L / ls_ratio
-        while True:
-            a = _step_length(slope, L, div, gamma)
-            trial = None
-            if a < 1:
-                hcoef, hdiv, ld1, q1, f1 = st.scalars(a, rec)
-            else:                                               # the cap: a full evaluation, as the generic solver's
-                trial = st.full_step(rec)
-                f1 = st.obj.func_grad(trial, flag=0) if linesearch else None
-            if not linesearch:
-                break
-            assert not math.isinf(L), "L is infinite"
-            if f1 <= fx + a * slope + a ** gamma * L * div:
-                break
-            L = L * ls_ratio
-
+        step, trial, stop = run.decide(k, rec, time.time() - t_start, lambda r: st.capped(r, linesearch))
         if trial is None:
-            st.apply(rec, a, hcoef, hdiv, ld1, q1)
+            st.apply_step(*step)
         else:
             st.reinit(trial)
-        Ls[k] = L
-        done = k + 1
         if verbose and k % verbskip == 0:
-            print(f"{k:6d}  {F[k]:10.3e}  {L:10.3e}  {T[k]:6.1f}")
-        if k > 0 and abs(F[k] - F[k - 1]) < epsilon:
+            print(f"{k:6d}  {run.F[k]:10.3e}  {run.L:10.3e}  {run.T[k]:6.1f}")
+        if stop:
             break
         yield k
 
-    return st.x(), F[:done], Ls[:done], T[:done]
+    return run.result(st.x())
 
 
 def D_opt_FW_descent_step(f, x0, maxitrs, epsilon=1e-14, verbose=True, verbskip=1, radius=1, refresh=REFRESH_DEFAULT):
@@ -913,30 +1017,139 @@ def D_opt_FW_descent_step_steps(f, x0, maxitrs, epsilon=1e-14, verbose=True, ver
         print("     k      F(x)         alpha_k       time")
 
     t_start = time.time()
-    F = np.zeros(maxitrs)
-    G = np.zeros(maxitrs)
-    T = np.zeros(maxitrs)
-
     st = _FWDivState(f, x0, radius, refresh)
-    rec = st.probe_div()
-    F[0] = st.value(rec)
-    T[0] = time.time() - t_start
+    run = _DescentRun(st.book, maxitrs, epsilon)
+    run.first(st.probe_div(), time.time() - t_start)
 
-    k = 0
     for k in range(1, maxitrs):
-        alpha = 2 / (k + 2)
-        hcoef, hdiv, ld1, q1, _ = st.scalars(alpha, rec)
-        st.apply(rec, alpha, hcoef, hdiv, ld1, q1)
+        st.apply_step(*run.step(k))
         st.refresh_if_due()
-        rec = st.probe_div()
-        F[k] = st.value(rec)
-        T[k] = time.time() - t_start
+        stop = run.probed(k, st.probe_div(), time.time() - t_start)
 
         if verbose and (k % verbskip == 0 or k == 1):
-            print(f"{k:6d}  {F[k]:10.3e}  {alpha:10.3e}  {T[k]:6.1f}")
+            print(f"{k:6d}  {run.F[k]:10.3e}  {run.alpha:10.3e}  {run.T[k]:6.1f}")
 
-        if abs(F[k] - F[k - 1]) < epsilon or math.sqrt(rec.sum_w2) < epsilon:
+        if stop:
             break
         yield k
 
-    return st.x(), F[:k + 1], T[:k + 1], G[:k + 1]
+    return run.result(st.x())
+
+
+# ---- the Bregman-step solvers on the instances of a batch in lock-step --------------------------------
+# The generators reach the device through the batch alone -- fw_rows, fw_init, fw_x, fw_div_probe, fw_div_apply and
+# fw_div_capped -- and take every decision in the per-instance _DivStepRun / _DescentRun of the sequential solvers.
+def _named(i, call, *args):
+    """call(*args) for instance i of a batch: what the sequential solver raises, with the instance index in front."""
+    try:
+        return call(*args)
+    except (ValueError, AssertionError) as err:
+        raise type(err)("instance %d: %s" % (i, err)) from None
+
+
+def _div_reinit(batch, X, books, which):
+    """Re-initialise the instances ``which`` (a K-mask) from their rows of X, the others staying as they are."""
+    logdet = batch.fw_init(X, active=which, named=True)
+    for i, on in enumerate(which):
+        if on:
+            books[i].reset(logdet[i])
+
+
+def _div_refresh(batch, X, books, active):
+    """Those of the active instances whose refresh is due, re-initialised from their own x in one masked call."""
+    due = [bool(active[i]) and books[i].refresh_due() for i in range(batch.K)]
+    if any(due):
+        for i in range(batch.K):
+            if due[i]:
+                X[i] = batch.fw_x(i, False)
+        _div_reinit(batch, X, books, due)
+
+
+def D_opt_FW_div_step_batch(batch, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2, radius=1,
+                            refresh=REFRESH_DEFAULT):
+    """D_opt_FW_div_step on the K instances of a ``DOptimalBatch`` in lock-step: one launch per step kernel covers the
+    instances still running and one synchronisation returns all their probe records; a line-search trial is host scalars,
+    so instances whose searches take different numbers of trials still share every launch.  ``x0``: one vector or a
+    K x n array; ``L``: a scalar or one per instance.  An instance that meets its stop test drops out of the later
+    launches; refreshes are per instance; a trial at the cap a == 1 is built and valued on that instance's own handle,
+    and an accepted one re-initialises that instance alone.  Silent.  Returns a list of K tuples (x, F, Ls, T), x, F
+    and Ls bit-identical to ``D_opt_FW_div_step(batch.instance(i), L_i, x0_i, maxitrs, gamma, ..., verbose=False)``;
+    what that raises is raised with "instance i: " in front."""
+    return _drain(D_opt_FW_div_step_batch_steps(batch, L, x0, maxitrs, gamma, epsilon, linesearch, ls_ratio, radius,
+                                                refresh))
+
+
+def D_opt_FW_div_step_batch_steps(batch, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2, radius=1,
+                                  refresh=REFRESH_DEFAULT):
+    """Generator form of D_opt_FW_div_step_batch: yields k after each lock-step iteration, returns its list."""
+    K = batch.K
+    Lv = _batch_eps(batch, L)
+    for i in range(K):
+        _named(i, _check_options, Lv[i], epsilon, ls_ratio)
+    t_start = time.time()
+    X, as_numpy = batch.fw_rows(x0)
+    logdet = batch.fw_init(X)
+    books = [_DivBook(batch.m, radius, refresh, logdet[i]) for i in range(K)]
+    runs = [_DivStepRun(books[i], Lv[i], maxitrs, gamma, epsilon, linesearch, ls_ratio) for i in range(K)]
+    active = [True] * K
+    steps = [None] * K
+    for k in range(maxitrs):
+        _div_refresh(batch, X, books, active)
+        recs = batch.fw_div_probe(active, radius)
+        now = time.time() - t_start
+        stepping = [False] * K
+        for i in range(K):
+            if not active[i]:
+                continue
+            steps[i], trial, stop = _named(i, runs[i].decide, k, recs[i], now,
+                                           lambda r, i=i: batch.fw_div_capped(i, r.i, radius, linesearch))
+            if trial is None:
+                stepping[i] = True
+            else:                                               # the capped step: this instance alone, from the trial
+                X[i] = trial
+                _div_reinit(batch, X, books, [j == i for j in range(K)])
+            active[i] = not stop                                # (the step of the stopping iteration is still taken)
+        if any(stepping):
+            batch.fw_div_apply(stepping, steps)
+        if not any(active):
+            break
+        yield k
+    return [runs[i].result(batch.fw_x(i, as_numpy)) for i in range(K)]
+
+
+def D_opt_FW_descent_step_batch(batch, x0, maxitrs, epsilon=1e-14, radius=1, refresh=REFRESH_DEFAULT):
+    """D_opt_FW_descent_step on the K instances of a ``DOptimalBatch`` in lock-step (see ``D_opt_FW_div_step_batch``).
+    Silent.  Returns a list of K tuples (x, F, T, G), x and F bit-identical to
+    ``D_opt_FW_descent_step(batch.instance(i), x0_i, maxitrs, ..., verbose=False)``."""
+    return _drain(D_opt_FW_descent_step_batch_steps(batch, x0, maxitrs, epsilon, radius, refresh))
+
+
+def D_opt_FW_descent_step_batch_steps(batch, x0, maxitrs, epsilon=1e-14, radius=1, refresh=REFRESH_DEFAULT):
+    """Generator form of D_opt_FW_descent_step_batch: yields k after each lock-step iteration, returns its list."""
+    K = batch.K
+    t_start = time.time()
+    X, as_numpy = batch.fw_rows(x0)
+    logdet = batch.fw_init(X)
+    books = [_DivBook(batch.m, radius, refresh, logdet[i]) for i in range(K)]
+    runs = [_DescentRun(books[i], maxitrs, epsilon) for i in range(K)]
+    active = [True] * K
+    steps = [None] * K
+    recs = batch.fw_div_probe(active, radius)
+    now = time.time() - t_start
+    for i in range(K):
+        runs[i].first(recs[i], now)
+    for k in range(1, maxitrs):
+        for i in range(K):
+            if active[i]:
+                steps[i] = runs[i].step(k)
+        batch.fw_div_apply(active, steps)
+        _div_refresh(batch, X, books, active)
+        recs = batch.fw_div_probe(active, radius)
+        now = time.time() - t_start
+        for i in range(K):
+            if active[i] and runs[i].probed(k, recs[i], now):
+                active[i] = False
+        if not any(active):
+            break
+        yield k
+    return [runs[i].result(batch.fw_x(i, as_numpy)) for i in range(K)]

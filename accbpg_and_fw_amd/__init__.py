@@ -18,7 +18,8 @@ from .algorithms_fw import FW_alg_div_step, FW_alg_descent_step
 from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball, lmo_l2_ball_positive_orthant
 from .D_opt_alg import (D_opt_FW, D_opt_FW_away, D_opt_FW_batch, D_opt_FW_away_batch, D_opt_FW_device,
                         D_opt_FW_away_device, D_opt_FW_batch_device, D_opt_FW_away_batch_device,
-                        D_opt_FW_div_step, D_opt_FW_descent_step)
+                        D_opt_FW_div_step, D_opt_FW_descent_step, D_opt_FW_div_step_batch,
+                        D_opt_FW_descent_step_batch)
 from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, D_opt_KYinit_device, D_opt_KYinit_batch,
                            Poisson_regrL1, Poisson_regrL2, KL_nonneg_regr, FrobeniusSymLossExL2Ball,
                            FrobeniusSymLossExLInfBall, FrobeniusSymLossResMeasEx, Poisson_regr_simplex,
@@ -39,5 +40,6 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "random_point_on_simplex", "edge_point_on_simplex", "get_random_float", "get_random_vector",
            "D_opt_FW_batch", "D_opt_FW_away_batch", "D_opt_FW_device", "D_opt_FW_away_device",
            "D_opt_FW_batch_device", "D_opt_FW_away_batch_device", "D_opt_KYinit_device",
-           "D_opt_KYinit_batch", "D_opt_FW_div_step", "D_opt_FW_descent_step"]
+           "D_opt_KYinit_batch", "D_opt_FW_div_step", "D_opt_FW_descent_step", "D_opt_FW_div_step_batch",
+           "D_opt_FW_descent_step_batch"]
 __version__ = "0.1.0"

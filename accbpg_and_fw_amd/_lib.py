@@ -126,6 +126,9 @@ _SIGS = {
     "accbpg_dopt_batch_fw_probe": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(FwProbe)]),
     "accbpg_dopt_batch_fw_update": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "accbpg_dopt_batch_fw_div_probe": (C.c_int, [_P, C.c_double, C.c_double, C.POINTER(C.c_int), C.POINTER(FwDivProbe)]),
+    "accbpg_dopt_batch_fw_div_apply": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                                 C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "accbpg_dopt_batch_fw_run": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int),
                                            C.POINTER(FwStep), C.POINTER(C.c_int)]),
     "accbpg_dopt_batch_kyinit": (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P]),

@@ -53,6 +53,8 @@ class DOptimalBatch:
         self._fw_probes = (_lib.FwProbe * self.K)()
         self._fw_args = ((C.c_int64 * self.K)(),) + tuple((C.c_double * self.K)() for _ in range(4))
         self._fw_steps = None                       # K x FW_RUN_MAX records of fw_run (allocated by the first call)
+        self._fw_div_probes = (_lib.FwDivProbe * self.K)()      # records of fw_div_probe
+        self._fw_div_radius = 1.0                   # ... and the vertex value of the last one (fw_div_apply steps towards it)
         self._fw_bad_pivot = ""                     # the library's message of the last fw_run that returned a status 2
 
     def __del__(self):
@@ -245,9 +247,16 @@ class DOptimalBatch:
     def _inst_h(self, i):
         return self.instance(i)._h
 
-    def fw_init(self, X0, active=None):
+    def fw_rows(self, x0):
+        """x0 (one vector or K x n, NumPy or torch) as the K x n device tensor ``fw_init`` takes, and whether it came as
+        NumPy."""
+        from .D_opt_alg import _batch_x0
+        return _batch_x0(self, x0)
+
+    def fw_init(self, X0, active=None, named=False):
         """``accbpg_fw_init`` for the active instances from the rows of X0 (K x n); returns log det(V_i diag(x0_i) V_i^T)
-        per instance (nan for inactive ones).  A singular instance raises as the single solver does."""
+        per instance (nan for inactive ones).  A singular instance raises as the single solver does; ``named``: with
+        "instance i: " in front."""
         self._rows(X0=X0)
         mask, idx = self._mask(active)
         ld = (C.c_double * self.K)(*([float("nan")] * self.K))
@@ -256,6 +265,12 @@ class DOptimalBatch:
             self._lib.accbpg_dopt_batch_set_stream(self._h, _stream())
             rc = self._lib.accbpg_dopt_batch_fw_init(self._h, _ptr(X0), self.n, mask, ld, st)
         _lib.check(rc, "accbpg_dopt_batch_fw_init")
+        if named:
+            for i in idx:
+                try:
+                    _lib.check(st[i], "accbpg_dopt_batch_fw_init")
+                except (ValueError, AssertionError) as err:
+                    raise type(err)("instance %d: %s" % (i, err)) from None
         self._raise(st, idx, "accbpg_dopt_batch_fw_init", None)
         return list(ld)
 
@@ -279,6 +294,41 @@ class DOptimalBatch:
             rc = self._lib.accbpg_dopt_batch_fw_update(self._h, mask, p, xs, xa, hc, hd)
         if rc:
             _lib.check(rc, "accbpg_dopt_batch_fw_update")
+
+    def fw_div_probe(self, active=None, radius=1):
+        """One Bregman-step probe of the active instances (``accbpg_dopt_batch_fw_div_probe`` with the simplex LMO's
+        vertex of this radius): one launch chain, one synchronisation.  Returns the K records (``_lib.FwDivProbe``; those
+        of inactive instances are stale).  The direction of each instance's step stays in its handle for
+        ``fw_div_apply``."""
+        from .D_opt_alg import _LMO_FILL
+        mask, _ = self._mask(active)
+        self._fw_div_radius = float(radius)
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_dopt_batch_fw_div_probe(self._h, _LMO_FILL, self._fw_div_radius, mask,
+                                                          self._fw_div_probes)
+        if rc:
+            _lib.check(rc, "accbpg_dopt_batch_fw_div_probe")
+        return self._fw_div_probes
+
+    def fw_div_apply(self, active, applies):
+        """One step x + a (s - x) per active instance towards the vertex of its last ``fw_div_probe``: applies[i] =
+        (p, a, hcoef, hdiv) with p that probe's index.  Refused for all if any instance's state moved since its probe.
+        Does not synchronise."""
+        from .D_opt_alg import _LMO_FILL
+        mask, idx = self._mask(active)
+        p, a, _, hc, hd = self._fw_args
+        for i in idx:
+            p[i], a[i], hc[i], hd[i] = applies[i]
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_dopt_batch_fw_div_apply(self._h, mask, p, a, _LMO_FILL, self._fw_div_radius, hc, hd)
+        if rc:
+            _lib.check(rc, "accbpg_dopt_batch_fw_div_apply")
+
+    def fw_div_capped(self, i, p, radius, valued):
+        """The capped step a == 1 of instance i towards the vertex at p, on that instance's own handle: (trial, f(trial))
+        as the sequential solver forms them; f is None unless ``valued``."""
+        from .D_opt_alg import _capped_trial
+        return _capped_trial(self.instance(i), self.fw_x(i, False), p, radius, valued)
 
     def fw_run(self, away, eps, nsteps, active=None):
         """``nsteps`` iterations of the active instances decided on the device behind one synchronisation

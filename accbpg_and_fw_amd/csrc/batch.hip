@@ -12,7 +12,7 @@ extern "C" int accbpg_dopt_batch_destroy(accbpg_dopt_batch* b) {
     for (accbpg_dopt* h : b->inst) accbpg_dopt_destroy(h);
     hipFree(b->table); hipFree(b->chol_table[0]); hipFree(b->chol_table[1]); hipFree(b->ops_all); hipFree(b->red_all);
     hipFree(b->dscal_all); hipFree(b->vflags); hipFree(b->vout); hipFree(b->vpart); hipFree(b->vws); hipFree(b->fw_table);
-    hipFree(b->fw_runs);
+    hipFree(b->fw_runs); hipFree(b->fw_div_table);
     if (b->fw_bsteps_pin) hipHostFree(b->fw_bsteps_pin);
     if (b->hpin) hipHostFree(b->hpin);
     if (b->vpin) hipHostFree(b->vpin);

@@ -701,11 +701,11 @@ __global__ __launch_bounds__(FB) void vt_usum_batch_kernel(const KyInst* __restr
 // entries.  Per entry, each operation rounded once, written as the generic path writes them (vec_kernels.hip,
 // ls_terms_partial_body with g = -w, x = s, y = x):
 //   sum_w += w;  sum_w2 += w*w;  slope += (-w) * (s - x);  div += s/x - log(s/x) - 1;  min_x = min_nan(min_x, x)
-__global__ __launch_bounds__(FB) void fw_div_probe_partial_kernel(const ValIdx* __restrict__ part, int nblk,
-                                                                 const double* __restrict__ w,
-                                                                 const double* __restrict__ x, int64_t n, double fill,
-                                                                 double value, double* __restrict__ rec,
-                                                                 ValIdx* __restrict__ mxslot) {
+__device__ __forceinline__ void fw_div_probe_partial_body(const ValIdx* __restrict__ part, int nblk,
+                                                          const double* __restrict__ w,
+                                                          const double* __restrict__ x, int64_t n, double fill,
+                                                          double value, double* __restrict__ rec,
+                                                          ValIdx* __restrict__ mxslot) {
     __shared__ ValIdx sh[FB / 64];
     const double inf = __builtin_inf();
     ValIdx best{-inf, INT64_MAX};
@@ -730,11 +730,11 @@ __global__ __launch_bounds__(FB) void fw_div_probe_partial_kernel(const ValIdx* 
 }
 // final stage: the block records in block order into doubles 3..7 of the pinned record, (i, w_i, x_i) in front of them,
 // and vp <- V[:,i] with i as it stands in device memory (no host round trip between the probe and the direction)
-__global__ __launch_bounds__(FB) void fw_div_probe_final_kernel(const double* __restrict__ rec, int nb,
-                                                               const ValIdx* __restrict__ mxslot,
-                                                               const double* __restrict__ x, int64_t n,
-                                                               const double* __restrict__ V, int64_t ldv, int64_t m,
-                                                               double* __restrict__ vp, double* __restrict__ pin) {
+__device__ __forceinline__ void fw_div_probe_final_body(const double* __restrict__ rec, int nb,
+                                                        const ValIdx* __restrict__ mxslot,
+                                                        const double* __restrict__ x, int64_t n,
+                                                        const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                        double* __restrict__ vp, double* __restrict__ pin) {
     reduce_final_body<FB, 5, true>(rec, nb, pin + 3);
     const ValIdx mx = *mxslot;
     const int64_t i = mx.i;
@@ -748,8 +748,8 @@ __global__ __launch_bounds__(FB) void fw_div_probe_final_kernel(const double* __
         for (int64_t r = threadIdx.x; r < m; r += FB) vp[r] = V[r * ldv + i];
 }
 // u = sum of the row-split partials, as fw_wupdate sums them, kept for the apply; sum u^2 over the tree
-__global__ __launch_bounds__(FB) void fw_div_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
-                                                        double* __restrict__ u, double* __restrict__ u2part) {
+__device__ __forceinline__ void fw_div_usum_body(const double* __restrict__ upart, int nsplit, int64_t n,
+                                                 double* __restrict__ u, double* __restrict__ u2part) {
     double acc = 0.0;
     const int64_t stride = (int64_t)gridDim.x * FB;
     for (int64_t k = (int64_t)blockIdx.x * FB + threadIdx.x; k < n; k += stride) {
@@ -763,8 +763,8 @@ __global__ __launch_bounds__(FB) void fw_div_usum_kernel(const double* __restric
 }
 // x <- x + a*(s - x) with the vertex implicit: the bits of vec_axpby(1, s, -1, x) followed by vec_axpby(1, x, a, d)
 // (1*s, -1*x and 1*x are exact: one subtraction, one product, one addition)
-__global__ __launch_bounds__(FB) void fw_div_xupdate_kernel(double* __restrict__ x, int64_t n, int64_t p, double a,
-                                                           double fill, double value) {
+__device__ __forceinline__ void fw_div_xupdate_body(double* __restrict__ x, int64_t n, int64_t p, double a,
+                                                    double fill, double value) {
     const int64_t stride = (int64_t)gridDim.x * FB;
     for (int64_t k = (int64_t)blockIdx.x * FB + threadIdx.x; k < n; k += stride) {
         const double xk = x[k];
@@ -773,6 +773,83 @@ __global__ __launch_bounds__(FB) void fw_div_xupdate_kernel(double* __restrict__
         x[k] = xk + q;
     }
 }
+
+// one instance: the handle's pointers as arguments
+__global__ __launch_bounds__(FB) void fw_div_probe_partial_kernel(const ValIdx* __restrict__ part, int nblk,
+                                                                 const double* __restrict__ w,
+                                                                 const double* __restrict__ x, int64_t n, double fill,
+                                                                 double value, double* __restrict__ rec,
+                                                                 ValIdx* __restrict__ mxslot) {
+    fw_div_probe_partial_body(part, nblk, w, x, n, fill, value, rec, mxslot);
+}
+__global__ __launch_bounds__(FB) void fw_div_probe_final_kernel(const double* __restrict__ rec, int nb,
+                                                               const ValIdx* __restrict__ mxslot,
+                                                               const double* __restrict__ x, int64_t n,
+                                                               const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                               double* __restrict__ vp, double* __restrict__ pin) {
+    fw_div_probe_final_body(rec, nb, mxslot, x, n, V, ldv, m, vp, pin);
+}
+__global__ __launch_bounds__(FB) void fw_div_usum_kernel(const double* __restrict__ upart, int nsplit, int64_t n,
+                                                        double* __restrict__ u, double* __restrict__ u2part) {
+    fw_div_usum_body(upart, nsplit, n, u, u2part);
+}
+__global__ __launch_bounds__(FB) void fw_div_xupdate_kernel(double* __restrict__ x, int64_t n, int64_t p, double a,
+                                                           double fill, double value) {
+    fw_div_xupdate_body(x, n, p, a, fill, value);
+}
+
+// The active instances of a batch in lock-step (accbpg_dopt_batch_fw_div_probe / _fw_div_apply), by the convention of
+// the step kernels above: blockIdx.y is the position among the active instances, blockIdx.x and gridDim.x are the single
+// launch's, so the fixed tree adds every instance's entries in the single handle's order.  The state comes from the
+// batch's FwInst table, the Bregman-step workspace and the pinned record from its FwDivInst table.  Hv = H V[:,i] and
+// the pass over V between the probe and the sum of u are fw_gemv_h_batch / fw_vgemv_partial_batch as they stand.
+__global__ __launch_bounds__(FB) void fw_div_probe_partial_batch_kernel(const FwInst* __restrict__ tab,
+                                                                       const FwDivInst* __restrict__ dtab,
+                                                                       FwProbeArgs pa, int64_t m, int64_t n, double fill,
+                                                                       double value) {
+    const int i = pa.idx[blockIdx.y];
+    const FwInst t = tab[i];
+    double* ws = dtab[i].ws;
+    fw_div_probe_partial_body(fw_part_of(t, m), pa.nblk[blockIdx.y], t.w, t.x, n, fill, value, fw_div_rec_of(ws, n),
+                              fw_div_mxslot_of(ws, n));
+}
+__global__ __launch_bounds__(FB) void fw_div_probe_final_batch_kernel(const FwInst* __restrict__ tab,
+                                                                     const FwDivInst* __restrict__ dtab, BatchAct act,
+                                                                     int nb, int64_t ldv, int64_t m, int64_t n) {
+    const int i = act.idx[blockIdx.y];
+    const FwInst t = tab[i];
+    const FwDivInst d = dtab[i];
+    fw_div_probe_final_body(fw_div_rec_of(d.ws, n), nb, fw_div_mxslot_of(d.ws, n), t.x, n, t.V, ldv, m, fw_vp_of(t, m),
+                            d.pin);
+}
+__global__ __launch_bounds__(FB) void fw_div_usum_batch_kernel(const FwInst* __restrict__ tab,
+                                                              const FwDivInst* __restrict__ dtab, BatchAct act,
+                                                              int nsplit, int64_t n) {
+    const int i = act.idx[blockIdx.y];
+    double* ws = dtab[i].ws;
+    fw_div_usum_body(tab[i].vws, nsplit, n, ws, fw_div_u2part_of(ws, n));
+}
+__global__ __launch_bounds__(FB) void fw_div_u2final_batch_kernel(const FwDivInst* __restrict__ dtab, BatchAct act,
+                                                                 int nb, int64_t n) {
+    const FwDivInst d = dtab[act.idx[blockIdx.y]];
+    reduce_final_body<FB, 1, false>(fw_div_u2part_of(d.ws, n), nb, d.pin + 8);
+}
+__global__ __launch_bounds__(FB) void fw_div_xupdate_batch_kernel(const FwInst* __restrict__ tab, FwUpdArgs ua,
+                                                                 int64_t n, double fill, double value) {
+    const int a = blockIdx.y;
+    fw_div_xupdate_body(tab[ua.idx[a]].x, n, ua.p[a], ua.xscale[a], fill, value);
+}
+// w <- (w + hcoef u^2) / hdiv from the kept u (one "split") with stage 1 of the next probe, as accbpg_fw_div_apply
+__global__ __launch_bounds__(FB) void fw_div_wupdate_probe_batch_kernel(const FwInst* __restrict__ tab,
+                                                                       const FwDivInst* __restrict__ dtab, FwUpdArgs ua,
+                                                                       int64_t m, int64_t n) {
+    const int a = blockIdx.y;
+    const int i = ua.idx[a];
+    const FwInst t = tab[i];
+    fw_wupdate_probe_body(t.w, n, dtab[i].ws, 1, ua.hcoef[a], ua.hdiv[a], t.x, 0, fw_part_of(t, m));
+}
+// what a batched launch of the family carries by value at most, inside the 4 KiB of kernel arguments at K = ACCBPG_BATCH_MAX
+static_assert(sizeof(FwUpdArgs) + 64 <= 4096 && sizeof(FwProbeArgs) + 64 <= 4096, "batched div-step kernel arguments");
 
 __global__ __launch_bounds__(FB) void column_kernel(const double* __restrict__ V, int64_t ldv, int64_t m, int64_t j,
                                                    double* __restrict__ out) {
@@ -1194,19 +1271,30 @@ extern "C" int accbpg_fw_get_state(accbpg_dopt* h, double* x_dev, double* w_dev,
 
 // ---- Bregman-step Frank-Wolfe on the maintained state (accbpg_fw_div_probe_step / accbpg_fw_div_apply) -----------
 // Workspace behind the handle (allocated by the first probe, freed with it): u (n doubles), FW_DIV_CAP block records
-// of five doubles, FW_DIV_CAP partial sums of u^2, (w_i, i); and a pinned record of 16 doubles: i, w_i, x_i, the five
-// reductions, sum u^2.
-static double* fw_div_rec_of(const accbpg_dopt* h) { return h->fw_div_ws + h->n; }
-static double* fw_div_u2part_of(const accbpg_dopt* h) { return fw_div_rec_of(h) + 5 * FW_DIV_CAP; }
-static ValIdx* fw_div_mxslot_of(const accbpg_dopt* h) { return reinterpret_cast<ValIdx*>(fw_div_u2part_of(h) + FW_DIV_CAP); }
+// of five doubles, FW_DIV_CAP partial sums of u^2, (w_i, i) -- the accessors next to FwDivInst (internal.h); and a
+// pinned record of 16 doubles: i, w_i, x_i, the five reductions, sum u^2.
 static int fw_div_alloc(accbpg_dopt* h) {
     if (h->fw_div_ws) return ACCBPG_OK;
     if (!h->fw_div_pin) {
         ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fw_div_pin), sizeof(double) * 16, hipHostMallocDefault));
         ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_div_pin_dev), h->fw_div_pin, 0));
     }
-    ACC_HIP(hipMalloc(&h->fw_div_ws, sizeof(double) * ((size_t)h->n + 6 * FW_DIV_CAP + 2)));
+    ACC_HIP(hipMalloc(&h->fw_div_ws, sizeof(double) * fw_div_ws_doubles(h->n)));
     return ACCBPG_OK;
+}
+
+// the pinned record of a handle, as accbpg_fw_div_probe
+static void fw_div_read_probe(const accbpg_dopt* h, accbpg_fw_div_probe* out) {
+    const double* pin = h->fw_div_pin;
+    out->i = reinterpret_cast<const int64_t*>(pin)[0];
+    out->w_i = pin[1];
+    out->x_i = pin[2];
+    out->sum_w = pin[3];
+    out->sum_w2 = pin[4];
+    out->slope = pin[5];
+    out->div = pin[6];
+    out->min_x = pin[7];
+    out->sum_u2 = pin[8];
 }
 
 extern "C" int accbpg_fw_div_probe_step(accbpg_dopt* h, double fill, double value, accbpg_fw_div_probe* out) {
@@ -1226,8 +1314,8 @@ extern "C" int accbpg_fw_div_probe_step(accbpg_dopt* h, double fill, double valu
     h->fw_part_nblk = 0;
     h->fw_part_away = false;
     const int nb = red_blocks(n, FW_DIV_CAP);
-    double *rec = fw_div_rec_of(h), *u2part = fw_div_u2part_of(h), *vp = fw_vp_of(t, m);
-    ValIdx* mxslot = fw_div_mxslot_of(h);
+    double *rec = fw_div_rec_of(h->fw_div_ws, n), *u2part = fw_div_u2part_of(h->fw_div_ws, n), *vp = fw_vp_of(t, m);
+    ValIdx* mxslot = fw_div_mxslot_of(h->fw_div_ws, n);
     fw_div_probe_partial_kernel<<<nb, FB, 0, s>>>(part, nblk, t.w, t.x, n, fill, value, rec, mxslot);
     fw_div_probe_final_kernel<<<1, FB, 0, s>>>(rec, nb, mxslot, t.x, n, t.V, h->ldv, m, vp, h->fw_div_pin_dev);
     // the direction of the step: Hv = H V[:,i], u = V^T Hv (the kernels of accbpg_fw_update on their grids), sum u^2
@@ -1239,16 +1327,7 @@ extern "C" int accbpg_fw_div_probe_step(accbpg_dopt* h, double fill, double valu
     reduce_final_kernel<FB, 1, false><<<1, FB, 0, s>>>(u2part, nb, h->fw_div_pin_dev + 8);
     ACC_HIP(hipGetLastError());
     ACC_HIP(hipStreamSynchronize(s));
-    const double* pin = h->fw_div_pin;
-    out->i = reinterpret_cast<const int64_t*>(pin)[0];
-    out->w_i = pin[1];
-    out->x_i = pin[2];
-    out->sum_w = pin[3];
-    out->sum_w2 = pin[4];
-    out->slope = pin[5];
-    out->div = pin[6];
-    out->min_x = pin[7];
-    out->sum_u2 = pin[8];
+    fw_div_read_probe(h, out);
     if (out->i < 0 || out->i >= n) {
         set_last_error("accbpg_fw_div_probe_step: pivot index %lld outside [0, n)", (long long)out->i);
         return ACCBPG_ERR_ARG;
@@ -1398,6 +1477,129 @@ extern "C" int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* acti
     prof_end(h0, PROF_FWV);
     fw_wupdate_probe_batch_kernel<<<dim3(g.wb, na), FB, 0, s>>>(b->fw_table, ua, m, n, g.ns);
     for (int a = 0; a < ua.n; ++a) b->inst[ua.idx[a]]->fw_part_nblk = (int)g.wb;
+    ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+
+// ---- the Bregman-step probe and apply for the active instances (accbpg_dopt_batch_fw_div_probe / _fw_div_apply) ---
+static int fw_div_batch_table(accbpg_dopt_batch* b) {
+    if (b->fw_div_table) return ACCBPG_OK;
+    std::vector<FwDivInst> tab((size_t)b->K);
+    for (int i = 0; i < b->K; ++i) {
+        accbpg_dopt* h = b->inst[i];
+        ACC_TRY(fw_div_alloc(h));
+        tab[i] = FwDivInst{h->fw_div_ws, h->fw_div_pin_dev};
+    }
+    ACC_HIP(hipMalloc(&b->fw_div_table, sizeof(FwDivInst) * (size_t)b->K));
+    ACC_HIP(hipMemcpy(b->fw_div_table, tab.data(), sizeof(FwDivInst) * (size_t)b->K, hipMemcpyHostToDevice));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_div_probe(accbpg_dopt_batch* b, double fill, double value, const int* active_host,
+                                              accbpg_fw_div_probe* out_host) {
+    if (!b || !out_host) return ACCBPG_ERR_ARG;
+    accbpg_dopt* h0 = b->inst[0];                               // one shape, one device: every instance's own partition
+    const FwGrids g = fw_grids(h0->m, h0->n, h0->num_cu);
+    const int64_t m = h0->m, n = h0->n, ldv = h0->ldv;
+    FwProbeArgs pa;
+    BatchAct act, fresh;                                        // fresh: instances without stage-1 records waiting
+    for (int i = 0; i < b->K; ++i) {
+        if (active_host && !active_host[i]) continue;
+        const accbpg_dopt* h = b->inst[i];
+        if (!h->fw_ready || !b->fw_table) {
+            set_last_error("accbpg_dopt_batch_fw_div_probe: instance %d has no Frank-Wolfe state (accbpg_dopt_batch_fw_init)", i);
+            return ACCBPG_ERR_ARG;                              // (nothing has been launched)
+        }
+        const int a = pa.n++;
+        pa.idx[a] = i;
+        act.idx[act.n++] = i;
+        pa.nblk[a] = fw_part_waiting(h, 0);                     // stage 1 came with the last update of w
+        if (!pa.nblk[a]) {
+            pa.nblk[a] = (int)g.nblk;
+            fresh.idx[fresh.n++] = i;
+        }
+    }
+    if (pa.n == 0) return ACCBPG_OK;
+    ACC_TRY(fw_div_batch_table(b));
+    for (int a = 0; a < pa.n; ++a) {
+        accbpg_dopt* h = b->inst[pa.idx[a]];
+        h->fw_div_i = -1;
+        h->fw_part_nblk = 0;
+        h->fw_part_away = false;
+    }
+    hipStream_t s = b->stream;
+    const unsigned na = (unsigned)pa.n;
+    const int nb = red_blocks(n, FW_DIV_CAP);
+    if (fresh.n > 0)
+        fw_probe_partial_batch_kernel<<<dim3(g.nblk, (unsigned)fresh.n), FB, 0, s>>>(b->fw_table, fresh, m, n, 0);
+    fw_div_probe_partial_batch_kernel<<<dim3((unsigned)nb, na), FB, 0, s>>>(b->fw_table, b->fw_div_table, pa, m, n, fill,
+                                                                           value);
+    fw_div_probe_final_batch_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_table, b->fw_div_table, act, nb, ldv, m, n);
+    // the direction of every instance's step: Hv = H V[:,i], u = V^T Hv, sum u^2
+    fw_gemv_h_batch_kernel<<<dim3(g.hb, na), FB, 0, s>>>(b->fw_table, act, m);
+    prof_begin(h0, PROF_FWV);
+    fw_vgemv_partial_batch_kernel<<<dim3(g.vgx, (unsigned)g.ns, na), FB, 0, s>>>(b->fw_table, act, ldv, m, n, g.ns);
+    prof_end(h0, PROF_FWV);
+    fw_div_usum_batch_kernel<<<dim3((unsigned)nb, na), FB, 0, s>>>(b->fw_table, b->fw_div_table, act, g.ns, n);
+    fw_div_u2final_batch_kernel<<<dim3(1, na), FB, 0, s>>>(b->fw_div_table, act, nb, n);
+    ACC_HIP(hipGetLastError());
+    ACC_HIP(hipStreamSynchronize(s));                           // every record is in its instance's pinned buffer
+    int bad_inst = -1;
+    for (int a = 0; a < pa.n; ++a) {
+        const int i = pa.idx[a];
+        accbpg_dopt* h = b->inst[i];
+        fw_div_read_probe(h, out_host + i);
+        if (out_host[i].i < 0 || out_host[i].i >= n) {
+            if (bad_inst < 0) bad_inst = i;
+            continue;
+        }
+        h->fw_div_i = out_host[i].i;
+    }
+    if (bad_inst >= 0) {
+        set_last_error("accbpg_dopt_batch_fw_div_probe: instance %d: pivot index %lld outside [0, n)", bad_inst,
+                       (long long)out_host[bad_inst].i);
+        return ACCBPG_ERR_ARG;
+    }
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_div_apply(accbpg_dopt_batch* b, const int* active_host, const int64_t* p_host,
+                                              const double* a_host, double fill, double value, const double* hcoef_host,
+                                              const double* hdiv_host) {
+    if (!b || !p_host || !a_host || !hcoef_host || !hdiv_host) return ACCBPG_ERR_ARG;
+    const accbpg_dopt* h0 = b->inst[0];                         // one shape, one device: every instance's own partition
+    const int64_t m = h0->m, n = h0->n;
+    FwUpdArgs ua;
+    for (int i = 0; i < b->K; ++i) {
+        if (active_host && !active_host[i]) continue;
+        const accbpg_dopt* h = b->inst[i];
+        // the test of accbpg_fw_div_apply, per instance: Hv, vp and u are those of its last div probe
+        if (!h->fw_ready || !b->fw_table || p_host[i] < 0 || p_host[i] >= n || h->fw_div_i != p_host[i] ||
+            h->fw_part_nblk != 0) {
+            set_last_error("accbpg_dopt_batch_fw_div_apply: instance %d: pivot %lld is not the index of the last div probe "
+                           "on this state", i, (long long)p_host[i]);
+            return ACCBPG_ERR_ARG;                              // (nothing has been launched)
+        }
+        const int a = ua.n++;
+        ua.idx[a] = i;
+        ua.p[a] = p_host[i];
+        ua.xscale[a] = a_host[i];                               // the step length
+        ua.hcoef[a] = hcoef_host[i];
+        ua.hdiv[a] = hdiv_host[i];
+    }
+    if (ua.n == 0) return ACCBPG_OK;
+    ACC_TRY(fw_div_batch_table(b));                             // (the probes may all have been single-handle ones)
+    const FwGrids g = fw_grids(h0->m, h0->n, h0->num_cu);
+    const unsigned na = (unsigned)ua.n;
+    hipStream_t s = b->stream;
+    fw_div_xupdate_batch_kernel<<<dim3(g.gb, na), FB, 0, s>>>(b->fw_table, ua, n, fill, value);
+    fw_rank1_batch_kernel<<<dim3(g.rb, na), FB, 0, s>>>(b->fw_table, ua, m);
+    fw_div_wupdate_probe_batch_kernel<<<dim3(g.wb, na), FB, 0, s>>>(b->fw_table, b->fw_div_table, ua, m, n);
+    for (int a = 0; a < ua.n; ++a) {
+        accbpg_dopt* h = b->inst[ua.idx[a]];
+        h->fw_div_i = -1;
+        h->fw_part_nblk = (int)g.wb;
+    }
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }

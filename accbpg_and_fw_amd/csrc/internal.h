@@ -108,12 +108,27 @@ constexpr size_t fw_scratch_doubles(int64_t m) { return (size_t)(2 * m + 2 * (2 
 __host__ __device__ inline double* fw_rec_d(double* rec) { return rec + 4; }
 __host__ __device__ inline int64_t* fw_rec_i(double* rec) { return reinterpret_cast<int64_t*>(rec + 8); }
 
+// The Bregman-step workspace of one instance (accbpg_fw_div_probe_step / accbpg_fw_div_apply) as the kernels address it;
+// the handle keeps its own two pointers (fw_div_ws, fw_div_pin_dev), a batch keeps a device table beside fw_table.
+// Behind ws: u (n doubles), FW_DIV_CAP block records of five doubles, FW_DIV_CAP partial sums of u^2, (w_i, i).
+struct FwDivInst {
+    double* ws;             // fw_div_ws
+    double* pin;            // the instance's pinned record of 16 doubles, as the device addresses it
+};
+__host__ __device__ inline double* fw_div_rec_of(double* ws, int64_t n) { return ws + n; }
+__host__ __device__ inline double* fw_div_u2part_of(double* ws, int64_t n) { return fw_div_rec_of(ws, n) + 5 * FW_DIV_CAP; }
+__host__ __device__ inline ValIdx* fw_div_mxslot_of(double* ws, int64_t n) {
+    return reinterpret_cast<ValIdx*>(fw_div_u2part_of(ws, n) + FW_DIV_CAP);
+}
+constexpr size_t fw_div_ws_doubles(int64_t n) { return (size_t)n + 6 * FW_DIV_CAP + 2; }
+
 struct FwProbeArgs {        // active instances of a probe and the stage-1 records each has waiting
     int n = 0;
     int idx[BATCH_MAX] = {};
     int nblk[BATCH_MAX] = {};
 };
 struct FwUpdArgs {          // active instances of an update and their scalars, by position in idx
+                            // (accbpg_dopt_batch_fw_div_apply: xscale carries the step length a, xadd is unused)
     int n = 0;
     int idx[BATCH_MAX] = {};
     unsigned long long awaymask = 0;    // bit a: support threshold of the fused stage 1 (1e-8 instead of 0)
@@ -334,6 +349,7 @@ struct accbpg_dopt_batch {
     double* vws = nullptr;                  // workspace of the single-instance prox (long vectors, one instance at a time)
     double* vpin = nullptr;                 // pinned mirror (K * 8 doubles)
     accbpg::FwInst* fw_table = nullptr;     // device, K entries: Frank-Wolfe state of every instance (built by the first accbpg_dopt_batch_fw_init)
+    accbpg::FwDivInst* fw_div_table = nullptr;  // device, K entries: their Bregman-step workspaces (built by the first accbpg_dopt_batch_fw_div_*)
     // accbpg_dopt_batch_fw_run (allocated by the first call): every instance's step scalars + scratch record on the
     // device, and the records of a call in pinned host memory, row i (ACCBPG_FW_RUN_MAX records) = instance i
     accbpg::FwRunSlot* fw_runs = nullptr;

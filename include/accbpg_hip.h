@@ -450,6 +450,33 @@ int accbpg_dopt_batch_fw_update(accbpg_dopt_batch* b, const int* active_host, co
                                 const double* xscale_host, const double* xadd_host, const double* hcoef_host,
                                 const double* hdiv_host);
 
+/* accbpg_fw_div_probe_step / accbpg_fw_div_apply for the active instances of a batch in lock-step, by the contract of
+ * accbpg_dopt_batch_fw_probe / _fw_update: ONE launch per step kernel covers the active instances (active_host[i] != 0;
+ * NULL = all), all host arrays have K entries, entry i = instance i, and entries of inactive instances are neither
+ * read nor written.  fill and value are shared by the instances.  Grids, row split and the fixed summation tree of
+ * every instance are the single handle's, so the records and x, w, H of instance i are bit for bit those of the two
+ * single-handle calls on accbpg_dopt_batch_instance(b, i).
+ *   _fw_div_probe: the records of accbpg_fw_div_probe_step(h_i, fill, value, ...) behind ONE synchronisation.  An
+ *       instance without stage-1 records waiting gets a fresh stage 1 in a launch over those instances alone.  Each
+ *       instance's Hv and u stay in its own handle, and its bookkeeping is what the single-handle probe leaves.  An
+ *       active instance without Frank-Wolfe state returns ACCBPG_ERR_ARG before anything is launched.  A pivot outside
+ *       [0, n) on some instance returns ACCBPG_ERR_ARG with the first such instance named in the message; all records
+ *       are filled in all the same and that instance accepts no _apply.
+ *   _fw_div_apply: accbpg_fw_div_apply(h_i, p_host[i], a_host[i], fill, value, hcoef_host[i], hdiv_host[i]).  If on any
+ *       active instance p_host[i] is not the index of that instance's last div probe, or its state has moved since,
+ *       the call returns ACCBPG_ERR_ARG (the instance is named) before anything is launched: no instance moves.  Does
+ *       not synchronise; leaves the stage-1 records of the next probe on every updated instance.
+ * The instances' workspaces are their handles' own, so batched and single-handle div calls may be mixed on one state
+ * (a batched probe followed by accbpg_fw_div_apply on the instance handle, or the converse), and both mix freely with
+ * accbpg_fw_* on the handles and accbpg_dopt_batch_fw_init / _fw_probe / _fw_update / _fw_run: any of those that moves
+ * the state between a div probe and its apply makes the apply refuse.  The table of workspace addresses is built by
+ * the first of the two calls and freed by accbpg_dopt_batch_destroy. */
+int accbpg_dopt_batch_fw_div_probe(accbpg_dopt_batch* b, double fill, double value, const int* active_host,
+                                   accbpg_fw_div_probe* out_host);
+int accbpg_dopt_batch_fw_div_apply(accbpg_dopt_batch* b, const int* active_host, const int64_t* p_host,
+                                   const double* a_host, double fill, double value, const double* hcoef_host,
+                                   const double* hdiv_host);
+
 /* accbpg_fw_run for the active instances of a batch in lock-step: ONE launch per step kernel covers the active
  * instances (active_host[i] != 0; NULL = all; the set is fixed for the call), the decisions of every iteration are
  * taken on the device per instance, as accbpg_fw_run takes them and with eps_host[i], and ONE synchronisation returns

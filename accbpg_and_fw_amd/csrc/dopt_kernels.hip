@@ -1554,13 +1554,50 @@ __device__ __forceinline__ void trsm64_blk(double* __restrict__ Xs, const double
     }
 }
 
+// The update of the columns to the right of panel pnl in trsm64_stream: wave w owns the 16 x 16 blocks (w, q) of the
+// tile for every column block q > pnl, NCB of them.  Their reads are issued together and their four-MFMA chains
+// interleaved (each accumulator in k order from zero, then subtracted once, as trsm64_blk does block after block).
+template <int NCB>
+__device__ __forceinline__ void trsm_right_update(double* __restrict__ Xs, const double* __restrict__ Lo, int pnl,
+                                                  int wave, int lane) {
+    static_assert(NTHREADS / 64 == 4, "one 16-row block of the tile per wave");
+    const int k0 = 16 * pnl;
+    const int lr = lane & 15, lq = lane >> 4;
+    const double* ap = Xs + (16 * wave + lr) * SP + k0 + lq;
+    const double* bp = Lo + (16 * (pnl + 1) + lr) * SP + k0 + lq;
+    double* cp = Xs + (16 * wave + lq) * SP + 16 * (pnl + 1) + lr;
+    double av[4], bv[NCB][4], cv[NCB][4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) av[kk] = ap[4 * kk];
+#pragma unroll
+    for (int j = 0; j < NCB; ++j)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) bv[j][kk] = bp[16 * j * SP + 4 * kk];
+#pragma unroll
+    for (int j = 0; j < NCB; ++j)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) cv[j][rr] = cp[4 * rr * SP + 16 * j];
+    d4 acc[NCB];
+#pragma unroll
+    for (int j = 0; j < NCB; ++j) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int j = 0; j < NCB; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bv[j][kk], acc[j], 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < NCB; ++j)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) cp[4 * rr * SP + 16 * j] = cv[j][rr] - acc[j][rr];
+}
+
 // trsm64_blk for the one-launch Cholesky: the factor of the block column arrives panel by panel (16 columns at a
 // time) while its owner is still factoring the panels to the right.  `fetch(pnl, 0)` waits for panel pnl and
 // brings its piece (the 16x16 factor copy + reciprocals into tbuf, the rows of the factor below it into Lo) into
 // LDS; it returns false when the launch is being abandoned.  `fetch(pnl, 1)` asks whether the piece has been flagged
 // and `fetch(pnl, 2)` acts on the answer: if so it starts the piece's loads, which then land behind the work on the
-// current panel.  `done(pnl)` runs once the 16 columns of panel pnl of the solution are final (every thread, behind a
-// barrier): the owner publishes them and folds them into what follows while the next piece is on its way.
+// current panel; a wave that did not see the flag looks once more and `fetch(pnl, 3)`, behind `done`, acts on that
+// answer, so that the loads land behind the update of the columns to the right.  `done(pnl)` runs once the 16 columns
+// of panel pnl of the solution are final (every thread, behind a barrier): the owner publishes them and folds them into what follows while the next piece is on its way.
 // Same arithmetic as trsm64_blk.  (Issuing the fold's matrix-pipe work in front of the NEXT panel's solve instead, to
 // run under its dependent vector chain, was measured slower: its LDS reads queue ahead of the solve's.)
 template <class Fetch, class Done>
@@ -1568,7 +1605,9 @@ __device__ __forceinline__ bool trsm64_stream(double* __restrict__ Xs, const dou
                                               const double* __restrict__ tbuf, Fetch fetch, Done done) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#pragma unroll 1
+    // (unrolled: the registers of a piece on its way are carried from one panel to the next, and around a back edge the
+    //  compiler copied them -- behind a wait for every load and write-through store in flight, once per panel)
+#pragma unroll
     for (int pnl = 0; pnl < NB / 16; ++pnl) {
         const int k0 = 16 * pnl;
         const double* lt = tbuf + pnl * POTRF_TB;
@@ -1580,23 +1619,11 @@ __device__ __forceinline__ bool trsm64_stream(double* __restrict__ Xs, const dou
         __syncthreads();
         if (!done(pnl)) return false;
         if (pnl == NB / 16 - 1) break;
-        {
-            // P(:, 16q ..) -= X_p L(16q .., k0 .. k0+15)^T for the column blocks q > pnl, 16 x 16 pieces
-            const int ncb = NB / 16 - 1 - pnl;
-            const int lr = lane & 15, lq = lane >> 4;
-            for (int b = wave; b < 4 * ncb; b += NTHREADS / 64) {
-                const int bi = b & 3, q = pnl + 1 + (b >> 2);
-                d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const double av = Xs[(16 * bi + lr) * SP + k0 + 4 * kk + lq];
-                    const double bv = Lo[(16 * q + lr) * SP + k0 + 4 * kk + lq];
-                    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) Xs[(16 * bi + lq + 4 * rr) * SP + 16 * q + lr] -= acc[rr];
-            }
-        }
+        if (pnl + 1 < NB / 16) fetch(pnl + 1, 3);                 // a second look, asked behind the solve, answered by now
+        // P(:, 16q ..) -= X_p L(16q .., k0 .. k0+15)^T for the column blocks q > pnl, 16 x 16 pieces
+        if (pnl == 0) trsm_right_update<3>(Xs, Lo, pnl, wave, lane);
+        else if (pnl == 1) trsm_right_update<2>(Xs, Lo, pnl, wave, lane);
+        else trsm_right_update<1>(Xs, Lo, pnl, wave, lane);
         // (the barrier inside the next fetch separates these writes from the next panel's solve)
     }
     return true;
@@ -2024,7 +2051,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void chol_tiles_kernel(CholInst one, c
     auto at = [&](auto* base, int bi, int bj) { return base + (int64_t)bi * NB * ld + (int64_t)bj * NB; };
     if (stall_test && blockIdx.x == 0) return;                    // test hook: block column 0 is never published
     auto stamp = [&](int slot) {
-        if (ci.trace != nullptr && diagrole && tid == 0) ci.trace[d * CT_NSTAMP + slot] = wall_clock64();
+        // (a global store: a flat one makes every counted wait behind it a wait for everything in flight)
+        if (ci.trace != nullptr && diagrole && tid == 0)
+            ((__attribute__((address_space(1))) long long*)ci.trace)[d * CT_NSTAMP + slot] = wall_clock64();
     };
     stamp(0);                                                     // workgroup started
 
@@ -2064,6 +2093,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void chol_tiles_kernel(CholInst one, c
         double pc_t[2], pc_l[3], pc_s[2];
         bool have = false;
         int looked = 0;
+        // The diagonal tile as its accumulator left it (hand[d]; its producer finished about a block column ago) is
+        // looked for beside every look for a piece and requested by the waves that saw its flag, so it lands behind
+        // the solves; only a wave that never saw the flag waits for it, in front of the last piece.
+        const bool wantD = diagrole && d >= 2;
+        bool haveD = false;
+        int lookedD = 0;
+        auto load_diag = [&]() {
+            const double* hd = ci.hand + (int64_t)d * NB * NB;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) accD[i][j][r] = ct_ld(hd + ((i * 2 + j) * 4 + r) * NTHREADS + tid);
+        };
         auto load_piece = [&](int pnl) {
             const int k0 = 16 * pnl;
 #pragma unroll
@@ -2096,16 +2140,72 @@ __global__ __launch_bounds__(NTHREADS, 2) void chol_tiles_kernel(CholInst one, c
             }
             if (pnl == 3) { run_logdet = pc_s[0]; run_bad = pc_s[1]; }
         };
+        auto land_now = [&](int pnl) {
+            const int k0 = 16 * pnl;
+            double t_t[2], t_l[3];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int e = tid + q * NTHREADS;
+                t_t[q] = (e < POTRF_TB) ? ct_ld(ax + pnl * POTRF_TB + e) : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int e = tid + q * NTHREADS;
+                t_l[q] = (e < (NB - k0 - 16) * 16) ? ct_ld(Ljj + (int64_t)(k0 + 16 + (e >> 4)) * ld + k0 + (e & 15)) : 0.0;
+            }
+            if (pnl == 3) {
+                run_logdet = ct_ld(ax + 4 * POTRF_TB);
+                run_bad = ct_ld(ax + 4 * POTRF_TB + 1);
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int e = tid + q * NTHREADS;
+                if (e < POTRF_TB) tbuf[pnl * POTRF_TB + e] = t_t[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int e = tid + q * NTHREADS;
+                if (e < (NB - k0 - 16) * 16) R1[(k0 + 16 + (e >> 4)) * SP + k0 + (e & 15)] = t_l[q];
+            }
+        };
+        // does any wave of the workgroup say yes?  One LDS word per wave and ONE barrier (the library's workgroup
+        // reduction behind __syncthreads_or takes three); the words are next written behind at least one more barrier
+        auto vote_any = [&](bool mine) -> bool {
+            int* votes = word + 4;
+            const int any = __any(mine ? 1 : 0);
+            if ((tid & 63) == 0) votes[tid >> 6] = any;
+            __syncthreads();
+            return (votes[0] | votes[1] | votes[2] | votes[3]) != 0;
+        };
         auto fetch = [&](int pnl, int mode) -> bool {
-            if (mode == 1) { looked = ct_ldi(pflag + pnl); return true; }            // (uniform within a wave)
-            if (mode == 2) { if (looked != 0) { load_piece(pnl); have = true; } return true; }
+            if (mode == 1) {                                                         // (uniform within a wave)
+                looked = ct_ldi(pflag + pnl);
+                if (wantD && !haveD) lookedD = ct_ldi(hflags + d);
+                return true;
+            }
+            if (mode == 3) {
+                if (!have && looked != 0) { load_piece(pnl); have = true; }
+                return true;
+            }
+            if (mode == 2) {
+                if (looked != 0) { load_piece(pnl); have = true; }
+                else looked = ct_ldi(pflag + pnl);                               // not yet: look again (mode 3)
+                if (wantD && !haveD && lookedD != 0) { load_diag(); haveD = true; }
+                return true;
+            }
             // (a piece that is already in registers goes to LDS in front of the barrier: nobody reads those
             //  columns of the images before it)
             stamp(8 + 4 * pnl + (have ? 0 : 0));
             if (have) land_piece(pnl);
-            if (__syncthreads_or(have ? 0 : 1)) {
+            // (one vote for both questions: it tells whether ANY wave misses something, not which)
+            const bool needD = pnl == 3 && wantD;
+            if (vote_any(!(have && (!needD || haveD)))) {
+                if (needD) {
+                    if (!ct_wait(hflags + d, nullptr, abortw, spin_limit, word)) return false;
+                    if (!haveD) { load_diag(); haveD = true; }
+                }
                 if (!ct_wait(pflag + pnl, nullptr, abortw, spin_limit, word)) return false;
-                if (!have) { load_piece(pnl); land_piece(pnl); }
+                if (!have) land_now(pnl);
                 __syncthreads();
             }
             have = false;
@@ -2141,18 +2241,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void chol_tiles_kernel(CholInst one, c
                     p01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, p01, 0, 0, 0);
                     p10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, p10, 0, 0, 0);
                     p11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, p11, 0, 0, 0);
-                }
-                if (pnl == 2 && d >= 2) {
-                    // the diagonal tile as its accumulator left it (long there by now): requested here, it lands
-                    // while the last piece of the factor is awaited
-                    if (!ct_wait(hflags + d, nullptr, abortw, spin_limit, word)) return false;
-                    const double* hd = ci.hand + (int64_t)d * NB * NB;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) accD[i][j][r] = ct_ld(hd + ((i * 2 + j) * 4 + r) * NTHREADS + tid);
                 }
             }
             stamp(11 + 4 * pnl);

@@ -9,7 +9,6 @@
 //   :58  -sum(H * HXHTinvH, axis=0)  -> -colsum(Y*Y) fused into the product (colnorm_kernel)
 #include <atomic>
 #include <mutex>
-#include <unordered_map>
 #include <type_traits>
 
 #include "internal.h"
@@ -26,7 +25,9 @@ struct GramSeg {
     int64_t row0, col0, kb, ke;
     bool dual, whole;
 };
-constexpr int GRAM_RMAX = 4;    // unit ranges a workgroup can own (wg_ranges[w][r] = {first, end})
+// (GRAM_RMAX, the unit ranges a workgroup can own: dopt_plan.hpp.  The planner's replay of the walk cuts its ranges with
+// the host copy of this rule, gram_segment_k there: sharing one function changed the code of every Gram kernel, so the
+// two are held together by the plan invariants of tests/test_plan_cpu.py instead.)
 template <class T>
 __device__ __forceinline__ GramSeg gram_segment(const TileRC* __restrict__ tiles, int64_t kiters, int64_t it,
                                                 int64_t it1) {
@@ -1880,7 +1881,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void chol_syrk_kernel(double* __restri
 // launch-per-column kernels (the source matrix is intact unless the factorisation ran in place, in which case
 // the caller regenerates it).
 // =========================================================================================
-constexpr int CT_TMAX = 32;                       // block columns this scheme handles
+// (CT_TMAX, the block columns this scheme handles: dopt_plan.hpp)
 constexpr int CT_AUX = 4 * POTRF_TB + 8;          // per block column: the four 16x16 factor copies + reciprocals, running log det, bad-pivot mark
 constexpr int CT_LDS_DOUBLES = 2 * NB * SQ + 4 * POTRF_TB + 16;
 constexpr int CT_LDS_BYTES = CT_LDS_DOUBLES * 8;  // 76.9 KB: two workgroups per CU
@@ -2479,35 +2480,6 @@ __global__ __launch_bounds__(NTHREADS, 1) void pipe_probe_kernel(int iters, int 
 // =========================================================================================
 // host side
 // =========================================================================================
-template <class K>
-static int set_lds(K kernel, int bytes) {
-    ACC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                bytes));
-    return ACCBPG_OK;
-}
-
-// The kernels with variants (schedules, ablations) raise their limit at the launch site, the first time the instantiation
-// is launched: on this runtime a launch that asks for more dynamic LDS than the kernel's limit reports NO error -- not from
-// the launch, not from hipGetLastError, not from a synchronize -- and leaves garbage (measured; a Gram variant that had
-// been left out of a list of set_lds calls went unnoticed until its results were compared).
-static int ensure_lds(const void* kernel, int bytes) {
-    static std::mutex mu;
-    static std::unordered_map<const void*, int> limit;
-    std::lock_guard<std::mutex> guard(mu);
-    auto it = limit.find(kernel);
-    if (it != limit.end() && it->second >= bytes) return ACCBPG_OK;
-    ACC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    limit[kernel] = bytes;
-    return ACCBPG_OK;
-}
-// (a kernel name with template commas goes in parentheses)
-#define ACC_LAUNCH_LDS(kernel, grid, block, lds, stream, ...)                        \
-    do {                                                                             \
-        auto k__ = kernel;                                                           \
-        ACC_TRY(ensure_lds(reinterpret_cast<const void*>(k__), (int)(lds)));         \
-        k__<<<(grid), (block), (lds), (stream)>>>(__VA_ARGS__);                      \
-    } while (0)
-
 void prof_begin(accbpg_dopt* h, ProfKind k) {
     if (!h->prof_on) return;
     ProfSlot& p = h->prof[k];
@@ -2542,19 +2514,6 @@ int set_gemm_loop(int variant) {
     g_gemm_loop.store(variant);
     return ACCBPG_OK;
 }
-template <int LOOP>
-static int set_lds_gemm_loop() {
-    ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<true>, LOOP>, TileSmall<true>::LDS_BYTES));
-    ACC_TRY(set_lds(gemm_ops_kernel<TileSmall<false>, LOOP>, TileSmall<false>::LDS_BYTES));
-    return ACCBPG_OK;
-}
-static int set_lds_gemm_ops() {
-    ACC_TRY(set_lds_gemm_loop<0>());
-    ACC_TRY(set_lds_gemm_loop<2>());
-    ACC_TRY(set_lds_gemm_loop<3>());
-    ACC_TRY(set_lds_gemm_loop<4>());
-    return ACCBPG_OK;
-}
 // f(std::integral_constant<int, LOOP>) for the LOOP that the switch selects
 template <class F>
 static int with_gemm_loop(F&& f) {
@@ -2567,343 +2526,78 @@ static int with_gemm_loop(F&& f) {
     }
 }
 
+// copies a plan table to the device (an empty one: nothing allocated, *dev stays null)
+template <class T>
+static int upload(const std::vector<T>& v, T** dev) {
+    if (v.empty()) return ACCBPG_OK;
+    ACC_HIP(hipMalloc(dev, sizeof(T) * v.size()));
+    ACC_HIP(hipMemcpy(*dev, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return ACCBPG_OK;
+}
+
+// Plan (dopt_plan.hpp: pure host logic, pinned by tests/test_plan_cpu.py), then upload.
 int build_plans(accbpg_dopt* h) {
     const int64_t m = h->m;
-    // ---- Gram tile list (lower tiles) and stream-K partition
-    const bool interior256 = h->vec_ok && (m % 256 == 0) && (h->n % BK == 0);
-    const int BM = h->big ? TileBig<false>::BM : TileSmall<false>::BM;
-    const int BN = h->big ? TileBig<false>::BN : TileSmall<false>::BN;
-    std::vector<TileRC> tl;
-    const int nrb = (int)((m + BM - 1) / BM), ncb = (int)((m + BN - 1) / BN);
-    // Long rows: the Gram matrix is formed column block by column block of V (one launch each, added up in G).  Over a
-    // pass of 16384 k-steps the workgroups of a launch drift apart and stop sharing their panels of V through L2: at
-    // (8192,262144) one launch reached 0.68 of the MFMA peak, the (8192,32768) shape 0.86 -- so rows of 65536 columns or
-    // more are cut into blocks of 32768 (which is also what the eight ranks of BASELINE config 5 hold each).
-    h->gram_chunks = 1;
-    h->gram_nc = h->n;
-    constexpr int64_t GRAM_NC = 32768;
-    if (!(g_plan_flags & 4) && h->big && interior256 && h->use_glds && h->n >= 2 * GRAM_NC && h->n % GRAM_NC == 0) {
-        h->gram_chunks = (int)(h->n / GRAM_NC);
-        h->gram_nc = GRAM_NC;
-        // Rows a megabyte or more apart: a tile of the Gram kernel streams 384 rows of V at once, and with that stride
-        // every one of them sits in a page of its own -- measured on one (8192, 32768) column block: 32.5 ms with rows
-        // 256 or 512 KiB apart, 34.6 ms at 1 MiB, 40.4 ms at 2 MiB (`tools/gram_stride.py`,
-        // profiles/r03_gram_stride.json).  The handle then keeps a copy of V stored block by block ([block][row][32768
-        // columns], made once, here) and the Gram launches read that; everything else keeps reading the caller's V,
-        // which must not change while the handle lives.
-        if (!(g_plan_flags & 8) && h->ldv * (int64_t)sizeof(double) >= (1 << 20)) {
-            const size_t bytes = sizeof(double) * (size_t)m * (size_t)h->n;
-            if (hipMalloc(&h->Vblk, bytes) == hipSuccess) {
-                for (int c = 0; c < h->gram_chunks; ++c)
-                    ACC_HIP(hipMemcpy2DAsync(h->Vblk + (size_t)c * m * GRAM_NC, sizeof(double) * GRAM_NC,
-                                             h->V + (size_t)c * GRAM_NC, sizeof(double) * (size_t)h->ldv,
-                                             sizeof(double) * GRAM_NC, (size_t)m, hipMemcpyDeviceToDevice, h->stream));
-                ACC_HIP(hipStreamSynchronize(h->stream));
-            } else {
-                (void)hipGetLastError();                        // no room for the copy: read V where it lies
-                h->Vblk = nullptr;
-            }
+    // ---- Gram tile list, stream-K partition and fix-up lists
+    GramPlanIn in;
+    in.m = m; in.n = h->n; in.ldv = h->ldv;
+    in.big = h->big; in.vec_ok = h->vec_ok; in.use_glds = h->use_glds;
+    in.num_cu = h->num_cu; in.grid_cap = h->gram_grid_cap; in.flags = g_plan_flags;
+    const GramPlan gp = plan_gram(in);
+    if (!gp.ok) return ACCBPG_ERR_ARG;
+    h->gram_chunks = gp.chunks;
+    h->gram_nc = gp.nc;
+    h->kiters = gp.kiters;
+    h->has_duals = gp.has_duals;
+    h->ntiles = (int)gp.tiles.size();
+    h->gram_grid = gp.grid;
+    h->gram_per = gp.per;
+    h->gram_nslot = gp.nslot;
+    if (gp.want_block_copy) {
+        // the copy of V stored block by block ([block][row][gram_nc columns]) that the Gram launches then read
+        const size_t bytes = sizeof(double) * (size_t)m * (size_t)h->n;
+        if (hipMalloc(&h->Vblk, bytes) == hipSuccess) {
+            for (int c = 0; c < gp.chunks; ++c)
+                ACC_HIP(hipMemcpy2DAsync(h->Vblk + (size_t)c * m * gp.nc, sizeof(double) * gp.nc,
+                                         h->V + (size_t)c * gp.nc, sizeof(double) * (size_t)h->ldv,
+                                         sizeof(double) * gp.nc, (size_t)m, hipMemcpyDeviceToDevice, h->stream));
+            ACC_HIP(hipStreamSynchronize(h->stream));
+        } else {
+            (void)hipGetLastError();                        // no room for the copy: read V where it lies
+            h->Vblk = nullptr;
         }
     }
-    h->kiters = (h->gram_nc + BK - 1) / BK;
-    // 256x128 tiles: the tile (rb, 2rb+1) next to the diagonal holds one useful 128 x 128 block, the odd
-    // diagonal block 2rb+1, under 128 rows that lie strictly above the diagonal.  On the direct-to-LDS
-    // path those blocks run as dual tiles instead (half of K each at full MFMA work), two per entry.
-    const bool duals = h->big && interior256 && h->use_glds && (h->kiters % 2 == 0) && BM == 2 * BN;
-    std::vector<int> lone;
-    for (int rb = 0; rb < nrb; ++rb)
-        for (int cb = 0; cb < ncb; ++cb)
-            if ((int64_t)cb * BN <= (int64_t)rb * BM + BM - 1) {
-                if (duals && cb == 2 * rb + 1) lone.push_back(cb);
-                else tl.push_back(TileRC{rb, cb});
-            }
-    for (size_t i = 0; i + 1 < lone.size(); i += 2)
-        tl.push_back(TileRC{lone[i] / 2, lone[i], lone[i], lone[i + 1]});
-    if (lone.size() & 1) tl.push_back(TileRC{lone.back() / 2, lone.back()});   // odd one out: ordinary tile
-    h->has_duals = lone.size() >= 2;
-    h->ntiles = (int)tl.size();
-    const int64_t total = (int64_t)h->ntiles * h->kiters;
-    int grid = h->big ? h->num_cu : 2 * h->num_cu;
-    if (h->gram_grid_cap > 0 && grid > h->gram_grid_cap) grid = h->gram_grid_cap;   // one instance of a batch: its share of the chip
-    if (grid > total) grid = (int)total;
-    if (grid < h->ntiles && total / h->ntiles < 8) grid = h->ntiles;   // tiny K: one tile per workgroup
-    int64_t per = (total + grid - 1) / grid;
-    grid = (int)((total + per - 1) / per);
-    h->gram_grid = grid;
-    h->gram_per = (int)per;
-    const int64_t kit = h->kiters;
-    // ---- unit ranges per workgroup.
-    // Plain stream-K hands workgroup w the contiguous range [w*per, (w+1)*per).  When a tile holds several
-    // whole ranges (q = kiters / per >= 1, remainder rem > 0) the ranges are instead ALIGNED to the
-    // tiles: every tile is cut at 0, per, .., q*per, so that all workgroups of "class" j start at k-step
-    // j*per of their tile and stream the same columns of V at the same time; the q*ntiles body pieces
-    // are dealt to the XCDs (workgroup id mod 8, round-robin placement -- speed only, never correctness)
-    // 32 at a time in an order in which 32 consecutive tiles form a compact block (few distinct row and
-    // column panels -> shared through that XCD's L2), and the remainders [q*per, kiters) are walked by
-    // the last workgroups as one contiguous stream.
-    std::vector<int64_t> ranges((size_t)grid * GRAM_RMAX * 2, 0);
-    const int64_t q = kit / per, rem = kit % per;
-    // (a tail workgroup crosses at most per/rem + 2 remainders)
-    const bool aligned = h->big && q >= 1 && rem > 0 && (int64_t)h->ntiles * q < grid &&
-                         per / rem + 2 <= GRAM_RMAX;
-    if (aligned) {
-        // compact order of the entries: 4 x 8 blocks of tiles
-        std::stable_sort(tl.begin(), tl.end(), [](const TileRC& a, const TileRC& b) {
-            const int ka[4] = {a.rb / 4, a.cb / 8, a.rb, a.cb}, kb[4] = {b.rb / 4, b.cb / 8, b.rb, b.cb};
-            for (int i = 0; i < 4; ++i)
-                if (ka[i] != kb[i]) return ka[i] < kb[i];
-            return false;
-        });
-        const int nbody = (int)(h->ntiles * q);
-        const int px = (grid % 8 == 0) ? grid / 8 : 0;          // workgroups per XCD
-        auto wg_of = [&](int i) { return px ? (i / px) + 8 * (i % px) : i; };
-        int idx = 0;
-        for (int64_t j = 0; j < q; ++j)
-            for (int e = 0; e < h->ntiles; ++e, ++idx) {
-                const int w = wg_of(idx);
-                ranges[((size_t)w * GRAM_RMAX) * 2] = (int64_t)e * kit + j * per;
-                ranges[((size_t)w * GRAM_RMAX) * 2 + 1] = (int64_t)e * kit + (j + 1) * per;
-            }
-        // remainders: tail-workgroup t covers the concatenated tails' units [t*per, (t+1)*per)
-        const int64_t tail_total = (int64_t)h->ntiles * rem;
-        for (int t = 0; nbody + t < grid; ++t) {
-            const int w = wg_of(nbody + t);
-            int64_t u = (int64_t)t * per;
-            const int64_t u1 = std::min(u + per, tail_total);
-            int r = 0;
-            while (u < u1) {
-                const int64_t e = u / rem, off = u - e * rem;
-                const int64_t len = std::min(rem - off, u1 - u);
-                if (r >= GRAM_RMAX) return ACCBPG_ERR_ARG;      // cannot happen: per / rem + 2 <= GRAM_RMAX
-                ranges[((size_t)w * GRAM_RMAX + r) * 2] = e * kit + q * per + off;
-                ranges[((size_t)w * GRAM_RMAX + r) * 2 + 1] = e * kit + q * per + off + len;
-                ++r;
-                u += len;
-            }
-        }
-    }
-    // More tiles than workgroups (m >= 4096 on 256 CUs; BASELINE config 5: 1056 entries): plain stream-K would hand
-    // every workgroup a contiguous range of 4.1 tiles that starts somewhere inside a tile, so no two workgroups ever
-    // stream the same columns of V at the same time and every k-step of every workgroup comes from HBM (measured at
-    // (8192,262144): 0.67 of the MFMA peak, against 0.84 at (8192,32768) where the Infinity Cache still covers the
-    // offsets).  Instead every workgroup gets `wt` WHOLE tiles, which it walks from k = 0 in step with all the others,
-    // and the workgroups of one XCD (id mod 8 under round-robin placement -- speed only, never correctness) hold, at
-    // every one of the wt phases, a compact 4 x 8 block of tiles: 4 row panels + 8 column panels feed 32 tiles through
-    // that XCD's L2.  The ntiles - wt*grid entries left over are cut into equal pieces, one per workgroup (the
-    // stream-K tail: a few percent of the work).
-    const bool whole_tiles = !(g_plan_flags & 1) && !aligned && h->big && per >= kit && h->ntiles >= grid && grid % 8 == 0 && grid >= 8;
-    if (whole_tiles) {
-        std::stable_sort(tl.begin(), tl.end(), [](const TileRC& a, const TileRC& b) {
-            const int ka[4] = {a.rb / 4, a.cb / 8, a.rb, a.cb}, kb[4] = {b.rb / 4, b.cb / 8, b.rb, b.cb};
-            for (int i = 0; i < 4; ++i)
-                if (ka[i] != kb[i]) return ka[i] < kb[i];
-            return false;
-        });
-        const int wt = h->ntiles / grid, B = grid / 8;
-        const int nbody = wt * grid;
-        std::vector<TileRC> perm(tl);
-        for (int pph = 0; pph < wt; ++pph)
-            for (int xcd = 0; xcd < 8; ++xcd)
-                for (int sl = 0; sl < B; ++sl) {
-                    const int w = 8 * sl + xcd;
-                    perm[(size_t)wt * w + pph] = tl[((size_t)pph * 8 + xcd) * B + sl];
-                }
-        tl.swap(perm);
-        const int64_t tail_total = (int64_t)(h->ntiles - nbody) * kit;
-        const int64_t tail_per = (tail_total + grid - 1) / grid;
-        for (int w = 0; w < grid; ++w) {
-            ranges[((size_t)w * GRAM_RMAX) * 2] = (int64_t)wt * w * kit;
-            ranges[((size_t)w * GRAM_RMAX) * 2 + 1] = (int64_t)wt * (w + 1) * kit;
-            const int64_t t0 = std::min((int64_t)w * tail_per, tail_total), t1 = std::min((int64_t)(w + 1) * tail_per, tail_total);
-            ranges[((size_t)w * GRAM_RMAX + 1) * 2] = (int64_t)nbody * kit + t0;
-            ranges[((size_t)w * GRAM_RMAX + 1) * 2 + 1] = (int64_t)nbody * kit + t1;
-        }
-    }
-    if (!aligned && !whole_tiles) {
-        for (int w = 0; w < grid; ++w) {
-            ranges[((size_t)w * GRAM_RMAX) * 2] = std::min((int64_t)w * per, total);
-            ranges[((size_t)w * GRAM_RMAX) * 2 + 1] = std::min((int64_t)(w + 1) * per, total);
-        }
-    }
-    // XCD-aware order.  Workgroups whose ranges start a whole number of tiles apart run the same
-    // k-step at the same time; with `per` steps per workgroup those are workgroups dw = kiters/g apart
-    // (g = gcd(per, kiters)), D = per/g tiles apart, and when dw is a multiple of 8 they share an XCD
-    // (round-robin placement: speed only, never correctness).  Arrange the list so that positions
-    // i, i+D, i+2D, ... hold a compact 2 x 4 block of tiles (2 A panels + 4 B panels feed 8 tiles),
-    // which those workgroups then stream through the same L2 together.
-    {
-        auto gcd64 = [](int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; };
-        const int64_t g = gcd64(per, h->kiters);
-        const int64_t D = per / g, dw = h->kiters / g;
-        const int nt = (int)tl.size();
-        if (!aligned && !whole_tiles && h->big && D > 1 && D < nt && nt % D == 0 && dw % 8 == 0) {
-            const int gs = (int)(nt / D);
-            // sequence in which consecutive runs are compact: row-block pairs, then 4 column blocks at a time
-            std::vector<TileRC> seq;
-            std::vector<char> used(tl.size(), 0);
-            auto find = [&](int rb, int cb) {
-                for (size_t i = 0; i < tl.size(); ++i)
-                    if (!used[i] && tl[i].rb == rb && tl[i].cb == cb) return (int)i;
-                return -1;
-            };
-            const int bcols = (gs >= 2 && gs % 2 == 0) ? gs / 2 : 4;      // 2 x (gs/2) blocks fill one group
-            for (int rp = nrb - 2 + (nrb & 1); rp >= -1; rp -= 2)
-                for (int c4 = 0; c4 < ncb; c4 += bcols)
-                    for (int dr = 0; dr < 2; ++dr)
-                        for (int dc = 0; dc < bcols; ++dc) {
-                            const int rb = rp + dr, cb = c4 + dc;
-                            if (rb < 0 || rb >= nrb || cb >= ncb) continue;
-                            // only full 2x4 blocks first; ragged remainders are appended below
-                            const int i = find(rb, cb);
-                            if (i >= 0 && find(rp + (1 - dr), cb) != -2) { used[i] = 1; seq.push_back(tl[i]); }
-                        }
-            for (size_t i = 0; i < tl.size(); ++i)
-                if (!used[i]) seq.push_back(tl[i]);
-            std::vector<TileRC> perm(tl.size());
-            for (int i = 0; i < (int)D; ++i)
-                for (int j = 0; j < gs; ++j) perm[(size_t)D * j + i] = seq[(size_t)i * gs + j];
-            tl.swap(perm);
-        }
-    }
-    ACC_HIP(hipMalloc(&h->tiles, sizeof(TileRC) * tl.size()));
-    ACC_HIP(hipMemcpy(h->tiles, tl.data(), sizeof(TileRC) * tl.size(), hipMemcpyHostToDevice));
-    // ---- replay every workgroup's walk (the device splits a range at tile and dual-half boundaries the
-    // same way): slab slot of each segment = its ordinal in the walk; contributors of each tile in k order
-    {
-        struct Contrib { int64_t kb; int w, slot; };
-        std::vector<std::vector<Contrib>> cl((size_t)h->ntiles * 2);
-        const int64_t half = kit / 2;
-        int nslot = 1;
-        for (int w = 0; w < grid; ++w) {
-            int seg = 0;
-            for (int r = 0; r < GRAM_RMAX; ++r) {
-                int64_t it = ranges[((size_t)w * GRAM_RMAX + r) * 2];
-                const int64_t it1 = ranges[((size_t)w * GRAM_RMAX + r) * 2 + 1];
-                while (it < it1) {
-                    const int64_t e = it / kit, off = it - e * kit;
-                    const bool dual = tl[(size_t)e].d1 >= 0;
-                    const int hs = (dual && off >= half) ? 1 : 0;
-                    const int64_t lo = dual ? (hs ? half : 0) : 0, hi = dual ? (hs ? kit : half) : kit;
-                    const int64_t ue = std::min(hi, off + (it1 - it));
-                    const bool whole = (off == lo && ue == hi);
-                    if (dual || !whole || h->gram_chunks > 1) cl[(size_t)e * 2 + hs].push_back(Contrib{off, w, seg});
-                    it += ue - off;
-                    ++seg;
-                }
-            }
-            nslot = std::max(nslot, seg);
-        }
-        h->gram_nslot = nslot;
-        std::vector<int32_t> cstart(cl.size() + 1, 0), contrib;
-        for (size_t i = 0; i < cl.size(); ++i) {
-            std::sort(cl[i].begin(), cl[i].end(), [](const Contrib& a, const Contrib& b) { return a.kb < b.kb; });
-            for (const Contrib& c : cl[i]) { contrib.push_back(c.w); contrib.push_back(c.slot); }
-            cstart[i + 1] = (int32_t)(contrib.size() / 2);
-        }
-        if (contrib.empty()) contrib.push_back(0);
-        ACC_HIP(hipMalloc(&h->wg_ranges, sizeof(int64_t) * ranges.size()));
-        ACC_HIP(hipMemcpy(h->wg_ranges, ranges.data(), sizeof(int64_t) * ranges.size(), hipMemcpyHostToDevice));
-        ACC_HIP(hipMalloc(&h->gram_cstart, sizeof(int32_t) * cstart.size()));
-        ACC_HIP(hipMemcpy(h->gram_cstart, cstart.data(), sizeof(int32_t) * cstart.size(), hipMemcpyHostToDevice));
-        ACC_HIP(hipMalloc(&h->gram_contrib, sizeof(int32_t) * contrib.size()));
-        ACC_HIP(hipMemcpy(h->gram_contrib, contrib.data(), sizeof(int32_t) * contrib.size(), hipMemcpyHostToDevice));
-    }
-    ACC_HIP(hipMalloc(&h->slabs, sizeof(double) * (size_t)grid * h->gram_nslot * BM * BN));
+    ACC_TRY(upload(gp.tiles, &h->tiles));
+    ACC_TRY(upload(gp.ranges, &h->wg_ranges));
+    ACC_TRY(upload(gp.cstart, &h->gram_cstart));
+    ACC_TRY(upload(gp.contrib, &h->gram_contrib));
+    const size_t tile_doubles = h->big ? (size_t)TILE_BIG_M * TILE_BIG_N : (size_t)TILE_SMALL_M * TILE_SMALL_N;
+    ACC_HIP(hipMalloc(&h->slabs, sizeof(double) * (size_t)gp.grid * gp.nslot * tile_doubles));
 
-    // ---- inverse merge plan: binary tree over the NB-blocks of L.
-    // Per level two products: T1 = L21 * W11, then W21 = -W22 * T1.  The 64 x 64-tile kernel is bound by
-    // the latency of its k-steps, and the top levels have few tiles with long K: products with K >= 512
-    // are cut into pieces of 256 along K (written to Pbuf, zero ranges of the triangular operands
-    // skipped per piece) and summed by a reduction launch in a fixed order.
-    const int T = (int)((m + NB - 1) / NB);
-    h->ops_host.clear();
-    h->merge_stages.clear();
-    std::vector<RedOp> reds;
-    constexpr int64_t KP = 256, KSPLIT_MIN = 512;
+    // ---- inverse merges: binary tree over the NB-blocks of L, long products split along K into Pbuf
     ACC_HIP(hipMalloc(&h->Pbuf, sizeof(double) * (size_t)m * m));
-    for (int span = 1; span < T; span *= 2) {
-        std::vector<GemmOp> first, second;
-        for (int g = 0; g + span < T; g += 2 * span) {
-            const int64_t r1 = (int64_t)g * NB;                         // left group rows/cols start
-            const int64_t s1 = (int64_t)span * NB;                      // left size (always full)
-            const int64_t r2 = r1 + s1;
-            const int64_t s2 = std::min<int64_t>((int64_t)span * NB, m - r2);
-            GemmOp a{};
-            a.A = h->Lbuf + r2 * m + r1; a.lda = m;                     // L21 (s2 x s1)
-            a.B = h->Wbuf + r1 * m + r1; a.ldb = m;                     // W11 (s1 x s1), B[k][col]
-            a.C = h->Tbuf + r2 * m + r1; a.ldc = m;                     // T1  (s2 x s1)
-            a.M = (int)s2; a.N = (int)s1; a.K = (int)s1; a.lower_only = 0; a.alpha = 1.0; a.beta = 0.0;
-            a.tri = 1;                                                  // W11 is lower triangular
-            GemmOp b{};
-            b.A = h->Wbuf + r2 * m + r2; b.lda = m;                     // W22 (s2 x s2)
-            b.B = h->Tbuf + r2 * m + r1; b.ldb = m;                     // T1, B[k][col]
-            b.C = h->Wbuf + r2 * m + r1; b.ldc = m;                     // W21
-            b.M = (int)s2; b.N = (int)s1; b.K = (int)s2; b.lower_only = 0; b.alpha = -1.0; b.beta = 0.0;
-            b.tri = 2;                                                  // W22 is lower triangular
-            first.push_back(a);
-            second.push_back(b);
-        }
-        for (std::vector<GemmOp>* list : {&first, &second}) {
-            // split when every product of the list is a whole number of K pieces (full-size groups; N even)
-            bool split = !list->empty();
-            size_t pdoubles = 0;
-            for (const GemmOp& o : *list) {
-                split = split && o.K >= KSPLIT_MIN && o.K % KP == 0 && (o.N % 2 == 0) && (o.ldc % 2 == 0);
-                pdoubles += (size_t)(o.K / KP) * o.M * o.N;
-            }
-            split = split && pdoubles <= (size_t)m * m;
-            accbpg_dopt::MergeStage st{0, (int)h->ops_host.size(), 0, 0, 0};
-            accbpg_dopt::MergeStage rs{1, (int)reds.size(), 0, 0, 0};
-            double* pb = h->Pbuf;
-            for (const GemmOp& o : *list) {
-                st.maxm = std::max(st.maxm, o.M); st.maxn = std::max(st.maxn, o.N);
-                if (!split) { h->ops_host.push_back(o); continue; }
-                const int ns = (int)(o.K / KP);
-                RedOp r{o.C, pb, o.ldc, o.M, o.N, ns, 0};
-                reds.push_back(r);
-                rs.maxm = std::max(rs.maxm, o.M * o.N);
-                for (int p = 0; p < ns; ++p) {
-                    GemmOp q = o;
-                    q.A = o.A + p * KP;                                 // A[row][k]: k is the fast index
-                    q.B = o.B + p * KP * o.ldb;                         // B[k][col]
-                    q.K = (int)KP;
-                    q.koff = (int)(p * KP);
-                    q.C = pb; q.ldc = o.N;
-                    pb += (size_t)o.M * o.N;
-                    h->ops_host.push_back(q);
-                }
-            }
-            st.end = (int)h->ops_host.size();
-            h->merge_stages.push_back(st);
-            if (split) { rs.end = (int)reds.size(); h->merge_stages.push_back(rs); }
-        }
-    }
-    if (!h->ops_host.empty()) {
-        ACC_HIP(hipMalloc(&h->ops, sizeof(GemmOp) * h->ops_host.size()));
-        ACC_HIP(hipMemcpy(h->ops, h->ops_host.data(), sizeof(GemmOp) * h->ops_host.size(), hipMemcpyHostToDevice));
-    }
-    h->red_host = reds;
-    if (!reds.empty()) {
-        ACC_HIP(hipMalloc(&h->red, sizeof(RedOp) * reds.size()));
-        ACC_HIP(hipMemcpy(h->red, reds.data(), sizeof(RedOp) * reds.size(), hipMemcpyHostToDevice));
-    }
+    MergePlan mp = plan_merges(m, h->Lbuf, h->Wbuf, h->Tbuf, h->Pbuf);
+    h->ops_host = std::move(mp.ops);
+    h->red_host = std::move(mp.reds);
+    h->merge_stages = std::move(mp.stages);
+    ACC_TRY(upload(h->ops_host, &h->ops));
+    ACC_TRY(upload(h->red_host, &h->red));
+    const int T = (int)((m + NB - 1) / NB);
     ACC_HIP(hipMalloc(&h->chol_op, sizeof(GemmOp) * (size_t)(T + 1)));
 
-    // ---- one-launch Cholesky: a workgroup per tile (the owner of a diagonal tile also owns the tile left of it)
+    // ---- one-launch Cholesky: all its workgroups must be resident at once
     if (T <= CT_TMAX) {
-        std::vector<CholJob> jobs;
-        for (int d2 = 0; d2 < T; ++d2) jobs.push_back(CholJob{d2, d2});            // the chain first
-        for (int j = 0; j < T; ++j)                                               // then by urgency: leftmost columns
-            for (int i = j + 2; i < T; ++i) jobs.push_back(CholJob{i, j});
-        ACC_TRY(set_lds(chol_tiles_kernel, CT_LDS_BYTES));
+        const std::vector<CholJob> jobs = chol_jobs(T);
+        ACC_TRY(ensure_lds(h->device, reinterpret_cast<const void*>(chol_tiles_kernel), CT_LDS_BYTES));
         int per_cu = 0;
         ACC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, chol_tiles_kernel, NTHREADS, CT_LDS_BYTES));
         h->chol_tiles_grid = (int)jobs.size();
         h->chol_slots = std::min(per_cu, 2) * h->num_cu;         // workgroups of this kernel the chip holds at once
         h->chol_tiles_ok = per_cu >= 1 && (int64_t)jobs.size() <= (int64_t)h->chol_slots;
         if (h->chol_tiles_ok) {
-            ACC_HIP(hipMalloc(&h->chol_jobs, sizeof(CholJob) * jobs.size()));
-            ACC_HIP(hipMemcpy(h->chol_jobs, jobs.data(), sizeof(CholJob) * jobs.size(), hipMemcpyHostToDevice));
+            CholJob* jobs_dev = nullptr;
+            ACC_TRY(upload(jobs, &jobs_dev));
+            h->chol_jobs = jobs_dev;
             ACC_HIP(hipMalloc(&h->chol_ready, sizeof(int) * (size_t)(T * T + 5 * T)));
             ACC_HIP(hipMemset(h->chol_ready, 0, sizeof(int) * (size_t)(T * T + 5 * T)));
             ACC_HIP(hipMalloc(&h->chol_hand, sizeof(double) * (size_t)T * NB * NB));
@@ -2912,20 +2606,6 @@ int build_plans(accbpg_dopt* h) {
             ACC_HIP(hipMemset(h->Gbuf, 0, sizeof(double) * (size_t)m * m));
         }
     }
-
-    ACC_TRY(set_lds(gram_streamk_kernel<TileBig<false, true>>, TileBig<false>::LDS_BYTES));
-    ACC_TRY(set_lds(gram_streamk_kernel<TileBig<false, false>>, TileBig<false>::LDS_BYTES));
-    ACC_TRY(set_lds(gram_streamk_kernel<TileSmall<false, true>>, TileSmall<false>::LDS_BYTES));
-    ACC_TRY(set_lds(gram_streamk_kernel<TileSmall<false, false>>, TileSmall<false>::LDS_BYTES));
-    ACC_TRY(set_lds(colnorm_kernel<TileBig<true, true>>, TileBig<true>::LDS_BYTES));
-    ACC_TRY(set_lds(colnorm_kernel<TileBig<true, false>>, TileBig<true>::LDS_BYTES));
-    ACC_TRY(set_lds(colnorm_kernel<TileSmall<true, true>>, TileSmall<true>::LDS_BYTES));
-    ACC_TRY(set_lds(colnorm_kernel<TileSmall<true, false>>, TileSmall<true>::LDS_BYTES));
-    ACC_TRY(set_lds_gemm_ops());
-    ACC_TRY(set_lds(chol_step_kernel, CHOL_LDS_BYTES));
-    ACC_TRY(set_lds(chol_syrk_kernel, SYRK_LDS_BYTES));
-    ACC_TRY(set_lds(gemm_big_kernel<TileBig<true>>, TileBig<true>::LDS_BYTES));
-    ACC_TRY(set_lds(gemm_big_kernel<TileBig<false>>, TileBig<false>::LDS_BYTES));
     return ACCBPG_OK;
 }
 
@@ -2947,13 +2627,13 @@ static int gram_launch_t(accbpg_dopt* h, const double* x, double* gram) {
                 prof_begin(h, PROF_GRAM);
 #define ACC_GRAM_ARGS Vc, ldc, h->m, nc, xc, h->tiles, h->wg_ranges, h->kiters, h->gram_nslot, h->slabs, gram, h->m, all_slabs
                 if (h->kern_variant == 1)
-                    ACC_LAUNCH_LDS((gram_streamk_glds_kernel<T, GRAM_GV ^ 128>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GRAM_GV ^ 128>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
                 else if (h->kern_variant == 3)
-                    ACC_LAUNCH_LDS((gram_streamk_glds_kernel<T, 0>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, 0>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
                 else if (h->kern_variant == 2)
-                    ACC_LAUNCH_LDS((gram_streamk_glds_kernel<T, (GRAM_GV ^ 128) | 256>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, (GRAM_GV ^ 128) | 256>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
                 else
-                    ACC_LAUNCH_LDS((gram_streamk_glds_kernel<T, GRAM_GV>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GRAM_GV>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
 #undef ACC_GRAM_ARGS
                 ACC_HIP(hipGetLastError());
                 prof_end(h, PROF_GRAM);
@@ -2966,7 +2646,7 @@ static int gram_launch_t(accbpg_dopt* h, const double* x, double* gram) {
         }
     }
     prof_begin(h, PROF_GRAM);
-    gram_streamk_kernel<T><<<h->gram_grid, NTHREADS, T::LDS_BYTES, h->stream>>>(
+    ACC_LAUNCH_LDS(h->device, gram_streamk_kernel<T>, h->gram_grid, NTHREADS, T::LDS_BYTES, h->stream,
         h->V, h->ldv, h->m, h->n, x, h->tiles, h->wg_ranges, h->kiters, h->gram_nslot, h->slabs, gram, h->m, h->vec_ok);
     ACC_HIP(hipGetLastError());
     prof_end(h, PROF_GRAM);
@@ -2977,20 +2657,45 @@ static int gram_launch_t(accbpg_dopt* h, const double* x, double* gram) {
     return ACCBPG_OK;
 }
 
+// Average ms of `iters` calls of launch() on stream s, after one call that is not timed.  The events are destroyed on
+// every way out.
+template <class F>
+static int timed_launches(hipStream_t s, int iters, double* ms_out, F&& launch) {
+    hipEvent_t a, b;
+    ACC_HIP(hipEventCreate(&a));
+    if (hipEventCreate(&b) != hipSuccess) {
+        hipEventDestroy(a);
+        return ACCBPG_ERR_HIP;
+    }
+    auto timed = [&]() -> int {
+        ACC_TRY(launch());
+        ACC_HIP(hipEventRecord(a, s));
+        for (int i = 0; i < iters; ++i) ACC_TRY(launch());
+        ACC_HIP(hipEventRecord(b, s));
+        ACC_HIP(hipEventSynchronize(b));
+        float ms = 0.f;
+        ACC_HIP(hipEventElapsedTime(&ms, a, b));
+        *ms_out = ms / iters;
+        ACC_HIP(hipGetLastError());
+        return ACCBPG_OK;
+    };
+    const int rc = timed();
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    return rc;
+}
+
 // timing ablations of the Gram kernel (big interior tile only); returns average ms over `iters`
 int debug_gram_variant(accbpg_dopt* h, const double* x, int var, int iters, double* ms_out) {
     using T = TileBig<false, false>;
     if (!h->big) return ACCBPG_ERR_ARG;
     if (h->has_duals && var < 10) return ACCBPG_ERR_ARG;     // the register-staged variants know no dual tiles
-    hipEvent_t a, b;
-    ACC_HIP(hipEventCreate(&a));
-    ACC_HIP(hipEventCreate(&b));
     auto launch = [&]() -> int {
 #define ACC_LAUNCH_VAR(VV)                                                                                       \
-    gram_streamk_kernel<T, VV><<<h->gram_grid, NTHREADS, T::LDS_BYTES, h->stream>>>(                             \
+    ACC_LAUNCH_LDS(h->device, (gram_streamk_kernel<T, VV>), h->gram_grid, NTHREADS, T::LDS_BYTES, h->stream,      \
         h->V, h->ldv, h->m, h->n, x, h->tiles, h->wg_ranges, h->kiters, h->gram_nslot, h->slabs, h->Tbuf, h->m, h->vec_ok)
 #define ACC_LAUNCH_G(GG)                                                                                         \
-    ACC_LAUNCH_LDS((gram_streamk_glds_kernel<T, GG>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream,          \
+    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GG>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream,          \
         h->V, h->ldv, h->m, h->n, x, h->tiles, h->wg_ranges, h->kiters, h->gram_nslot, h->slabs, h->Tbuf, h->m, 0)
         switch (var) {
             case 10: ACC_LAUNCH_G(0); break;
@@ -3022,22 +2727,7 @@ int debug_gram_variant(accbpg_dopt* h, const double* x, int var, int iters, doub
 #undef ACC_LAUNCH_VAR
         return ACCBPG_OK;
     };
-    ACC_TRY(set_lds(gram_streamk_kernel<T, 1>, T::LDS_BYTES));
-    ACC_TRY(set_lds(gram_streamk_kernel<T, 2>, T::LDS_BYTES));
-    ACC_TRY(set_lds(gram_streamk_kernel<T, 3>, T::LDS_BYTES));
-    ACC_TRY(set_lds(gram_streamk_kernel<T, 4>, T::LDS_BYTES));
-    ACC_TRY(launch());
-    ACC_HIP(hipEventRecord(a, h->stream));
-    for (int i = 0; i < iters; ++i) ACC_TRY(launch());
-    ACC_HIP(hipEventRecord(b, h->stream));
-    ACC_HIP(hipEventSynchronize(b));
-    float ms = 0.f;
-    ACC_HIP(hipEventElapsedTime(&ms, a, b));
-    *ms_out = ms / iters;
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    ACC_HIP(hipGetLastError());
-    return ACCBPG_OK;
+    return timed_launches(h->stream, iters, ms_out, launch);
 }
 
 int launch_gram(accbpg_dopt* h, const double* x, double* gram) {
@@ -3078,12 +2768,14 @@ int device_copy(double* dst, const double* src, size_t ndoubles, hipStream_t s) 
 int launch_gemm_ops(const GemmOp* ops_dev, int nops, int maxM, int maxN, bool b_kmajor, hipStream_t s) {
     if (nops <= 0 || maxM <= 0 || maxN <= 0) return ACCBPG_OK;
     dim3 grid((maxN + 63) / 64, (maxM + 63) / 64, nops);
+    int dev = 0;
+    ACC_HIP(hipGetDevice(&dev));
     return with_gemm_loop([&](auto loop) -> int {
         constexpr int LOOP = decltype(loop)::value;
         if (b_kmajor)
-            gemm_ops_kernel<TileSmall<true>, LOOP><<<grid, NTHREADS, TileSmall<true>::LDS_BYTES, s>>>(ops_dev);
+            ACC_LAUNCH_LDS(dev, (gemm_ops_kernel<TileSmall<true>, LOOP>), grid, NTHREADS, TileSmall<true>::LDS_BYTES, s, ops_dev);
         else
-            gemm_ops_kernel<TileSmall<false>, LOOP><<<grid, NTHREADS, TileSmall<false>::LDS_BYTES, s>>>(ops_dev);
+            ACC_LAUNCH_LDS(dev, (gemm_ops_kernel<TileSmall<false>, LOOP>), grid, NTHREADS, TileSmall<false>::LDS_BYTES, s, ops_dev);
         ACC_HIP(hipGetLastError());
         return ACCBPG_OK;
     });
@@ -3132,8 +2824,8 @@ static int launch_chol_tiles(accbpg_dopt* h, const double* src, double* A, doubl
             if (ring.ev[slot] && ring.stream[slot] != h->stream) ACC_HIP(hipStreamWaitEvent(h->stream, ring.ev[slot], 0));
         }
     }
-    chol_tiles_kernel<<<dim3(h->chol_tiles_grid, 1), NTHREADS, CT_LDS_BYTES, h->stream>>>(
-        ci, nullptr, reinterpret_cast<const CholJob*>(h->chol_jobs), m, m, T, h->chol_spin_limit, h->chol_stall_test, BatchAct{});
+    ACC_LAUNCH_LDS(h->device, chol_tiles_kernel, dim3(h->chol_tiles_grid, 1), NTHREADS, CT_LDS_BYTES, h->stream,
+        ci,nullptr, reinterpret_cast<const CholJob*>(h->chol_jobs), m, m, T, h->chol_spin_limit, h->chol_stall_test, BatchAct{});
     ACC_HIP(hipGetLastError());
     {
         const int slot = (int)(ring.issued % TILES_RING);
@@ -3182,12 +2874,12 @@ int launch_cholesky(accbpg_dopt* h, double* A, double* Winv, const double* xchec
             const int R = T - (kc + 1);
             int nupd = 0;
             if (pend) nupd = (kend >= T - 1) ? R * (R + 1) / 2 : R * (kend - kc);
-            chol_step_kernel<<<npanel + nupd, NTHREADS, CHOL_LDS_BYTES, h->stream>>>(
+            ACC_LAUNCH_LDS(h->device, chol_step_kernel, npanel + nupd, NTHREADS, CHOL_LDS_BYTES, h->stream,
                 A, m, m, kc, pend, kend, T, dscal, dflag, h->chol_dbg, Winv, h->Tbuf);
         }
         const int Rr = T - (kend + 1);
         if (Rr > 0)
-            chol_syrk_kernel<<<Rr * (Rr + 1) / 2, NTHREADS, SYRK_LDS_BYTES, h->stream>>>(A, m, m, k0, kend - k0 + 1, T);
+            ACC_LAUNCH_LDS(h->device, chol_syrk_kernel, Rr * (Rr + 1) / 2, NTHREADS, SYRK_LDS_BYTES, h->stream, A, m, m, k0, kend - k0 + 1, T);
     }
     h->diag_inv_ready = (Winv != nullptr);
     prof_end(h, PROF_CHOL);
@@ -3218,10 +2910,11 @@ int launch_trtri(accbpg_dopt* h) {
 }
 
 template <class T>
-static void colnorm_launch_t(accbpg_dopt* h, const double* W, double* out, double sign, bool vw) {
+static int colnorm_launch_t(accbpg_dopt* h, const double* W, double* out, double sign, bool vw) {
     const int grid = (int)((h->n + T::BN - 1) / T::BN);
-    colnorm_kernel<T><<<grid, NTHREADS, T::LDS_BYTES, h->stream>>>(W, h->m, h->V, h->ldv, h->m, h->n, out, sign, vw,
-                                                                  h->vec_ok);
+    ACC_LAUNCH_LDS(h->device, colnorm_kernel<T>, grid, NTHREADS, T::LDS_BYTES, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out,
+                   sign, vw, h->vec_ok);
+    return ACCBPG_OK;
 }
 
 int launch_colnorm(accbpg_dopt* h, const double* W, double* out, double sign) {
@@ -3233,19 +2926,19 @@ int launch_colnorm(accbpg_dopt* h, const double* W, double* out, double sign) {
             using T = TileBig<true, false>;
             const int grid = (int)(h->n / T::BN), lds = T::G_LDS_BYTES + 4 * T::BN * 8;
             if (h->kern_variant == 1)
-                ACC_LAUNCH_LDS((colnorm_glds_kernel<T, COLNORM_CV ^ 256>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
+                ACC_LAUNCH_LDS(h->device, (colnorm_glds_kernel<T, COLNORM_CV ^ 256>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
             else if (h->kern_variant == 2)
-                ACC_LAUNCH_LDS((colnorm_glds_kernel<T, 96>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
+                ACC_LAUNCH_LDS(h->device, (colnorm_glds_kernel<T, 96>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
             else if (h->kern_variant == 3)        // the production schedule before the two phases: runtime skip, restart per row block
-                ACC_LAUNCH_LDS((colnorm_glds_kernel<T, COLNORM_CV | 512>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
+                ACC_LAUNCH_LDS(h->device, (colnorm_glds_kernel<T, COLNORM_CV | 512>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
             else
-                ACC_LAUNCH_LDS((colnorm_glds_kernel<T, COLNORM_CV>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
-        } else if (interior) colnorm_launch_t<TileBig<true, false>>(h, W, out, sign, vw);
-        else colnorm_launch_t<TileBig<true, true>>(h, W, out, sign, vw);
+                ACC_LAUNCH_LDS(h->device, (colnorm_glds_kernel<T, COLNORM_CV>), grid, NTHREADS, lds, h->stream, W, h->m, h->V, h->ldv, h->m, h->n, out, sign);
+        } else if (interior) ACC_TRY((colnorm_launch_t<TileBig<true, false>>(h, W, out, sign, vw)));
+        else ACC_TRY((colnorm_launch_t<TileBig<true, true>>(h, W, out, sign, vw)));
     } else {
         const bool interior = vw && h->vec_ok && (h->m % 64 == 0) && (h->n % 64 == 0);
-        if (interior) colnorm_launch_t<TileSmall<true, false>>(h, W, out, sign, vw);
-        else colnorm_launch_t<TileSmall<true, true>>(h, W, out, sign, vw);
+        if (interior) ACC_TRY((colnorm_launch_t<TileSmall<true, false>>(h, W, out, sign, vw)));
+        else ACC_TRY((colnorm_launch_t<TileSmall<true, true>>(h, W, out, sign, vw)));
     }
     prof_end(h, PROF_GRAD);
     ACC_HIP(hipGetLastError());
@@ -3260,14 +2953,9 @@ int launch_colnorm(accbpg_dopt* h, const double* W, double* out, double sign) {
 int launch_gram_batch(accbpg_dopt_batch* b, const BatchAct& act, const double* xbase, int64_t ldx) {
     using T = TileBig<false, false>;
     accbpg_dopt* h0 = b->inst[0];
-    static bool lds_set = false;
-    if (!lds_set) {
-        ACC_TRY(set_lds(gram_streamk_glds_batch_kernel<T>, T::G_LDS_BYTES));
-        lds_set = true;
-    }
     // (kernel-time accounting of a batch rides on instance 0's slots: accbpg_dopt_profile_* on accbpg_dopt_batch_instance(b, 0))
     prof_begin(h0, PROF_GRAM);
-    gram_streamk_glds_batch_kernel<T><<<dim3(h0->gram_grid, act.n), NTHREADS, T::G_LDS_BYTES, b->stream>>>(
+    ACC_LAUNCH_LDS(b->device, gram_streamk_glds_batch_kernel<T>, dim3(h0->gram_grid, act.n), NTHREADS, T::G_LDS_BYTES, b->stream,
         b->table, act, h0->ldv, h0->m, h0->n, xbase, ldx, h0->tiles, h0->wg_ranges, h0->kiters, h0->gram_nslot, h0->m);
     prof_end(h0, PROF_GRAM);
     prof_begin(h0, PROF_GRAMFIX);
@@ -3299,7 +2987,7 @@ int launch_cholesky_batch(accbpg_dopt_batch* b, const BatchAct& act, bool with_i
             if (ring.ev[slot] && ring.stream[slot] != b->stream) ACC_HIP(hipStreamWaitEvent(b->stream, ring.ev[slot], 0));
         }
     }
-    chol_tiles_kernel<<<dim3(h0->chol_tiles_grid, act.n), NTHREADS, CT_LDS_BYTES, b->stream>>>(
+    ACC_LAUNCH_LDS(b->device, chol_tiles_kernel, dim3(h0->chol_tiles_grid, act.n), NTHREADS, CT_LDS_BYTES, b->stream,
         CholInst{}, b->chol_table[with_inverse ? 1 : 0], reinterpret_cast<const CholJob*>(h0->chol_jobs), m, m, T,
         h0->chol_spin_limit, 0, act);
     prof_end(h0, PROF_CHOL);
@@ -3324,7 +3012,8 @@ int launch_trtri_batch(accbpg_dopt_batch* b, const BatchAct& act) {
         if (st.kind == 0) {
             dim3 grid((st.maxn + 63) / 64, (st.maxm + 63) / 64, count * act.n);
             ACC_TRY(with_gemm_loop([&](auto loop) -> int {
-                gemm_ops_batch_kernel<TileSmall<true>, decltype(loop)::value><<<grid, NTHREADS, TileSmall<true>::LDS_BYTES, b->stream>>>(
+                ACC_LAUNCH_LDS(b->device, (gemm_ops_batch_kernel<TileSmall<true>, decltype(loop)::value>), grid, NTHREADS,
+                               TileSmall<true>::LDS_BYTES, b->stream,
                     b->ops_all, b->ops_per_inst, st.begin, count, act);
                 return ACCBPG_OK;
             }));
@@ -3351,15 +3040,9 @@ int debug_grad_variant(accbpg_dopt* h, double* out, int var, int iters, double* 
     if (!h->big || !h->use_glds || !vw || !h->vec_ok || h->m % 256 != 0 || h->n % 128 != 0) return ACCBPG_ERR_ARG;
     const int grid = (int)(h->n / T::BN), lds = T::G_LDS_BYTES + 4 * T::BN * 8;
     if (var != 0 && (var < 3 || var > 6) && (var < 10 || var > 13) && (var < 20 || var > 23) && (var < 30 || var > 33)) return ACCBPG_ERR_ARG;
-    hipEvent_t a, b;
-    ACC_HIP(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) {
-        hipEventDestroy(a);
-        return ACCBPG_ERR_HIP;
-    }
     auto launch = [&]() -> int {
 #define ACC_LAUNCH_C(CC) \
-    ACC_LAUNCH_LDS((colnorm_glds_kernel<T, CC>), grid, NTHREADS, lds, h->stream, h->Wbuf, h->m, h->V, h->ldv, h->m, h->n, out, -1.0)
+    ACC_LAUNCH_LDS(h->device, (colnorm_glds_kernel<T, CC>), grid, NTHREADS, lds, h->stream, h->Wbuf, h->m, h->V, h->ldv, h->m, h->n, out, -1.0)
         switch (var) {
             case 0: ACC_LAUNCH_C(COLNORM_CV); break;
             case 3: ACC_LAUNCH_C(COLNORM_CV | 512); break;
@@ -3383,35 +3066,15 @@ int debug_grad_variant(accbpg_dopt* h, double* out, int var, int iters, double* 
 #undef ACC_LAUNCH_C
         return ACCBPG_OK;
     };
-    // (the events are destroyed on every way out)
-    auto timed = [&]() -> int {
-        ACC_TRY(launch());
-        ACC_HIP(hipEventRecord(a, h->stream));
-        for (int i = 0; i < iters; ++i) ACC_TRY(launch());
-        ACC_HIP(hipEventRecord(b, h->stream));
-        ACC_HIP(hipEventSynchronize(b));
-        float ms = 0.f;
-        ACC_HIP(hipEventElapsedTime(&ms, a, b));
-        *ms_out = ms / iters;
-        ACC_HIP(hipGetLastError());
-        return ACCBPG_OK;
-    };
-    const int rc = timed();
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    return rc;
+    return timed_launches(h->stream, iters, ms_out, launch);
 }
 
 int launch_colnorm_batch(accbpg_dopt_batch* b, const BatchAct& act, double* gbase, int64_t ldg, double sign) {
     using T = TileBig<true, false>;
     accbpg_dopt* h0 = b->inst[0];
-    static bool lds_set = false;
-    if (!lds_set) {
-        ACC_TRY(set_lds(colnorm_glds_batch_kernel<T>, T::G_LDS_BYTES + 4 * T::BN * 8));
-        lds_set = true;
-    }
     prof_begin(h0, PROF_GRAD);
-    colnorm_glds_batch_kernel<T><<<dim3((unsigned)(h0->n / T::BN), act.n), NTHREADS, T::G_LDS_BYTES + 4 * T::BN * 8, b->stream>>>(
+    ACC_LAUNCH_LDS(b->device, colnorm_glds_batch_kernel<T>, dim3((unsigned)(h0->n / T::BN), act.n), NTHREADS,
+                   T::G_LDS_BYTES + 4 * T::BN * 8, b->stream,
         b->table, act, h0->m, h0->ldv, h0->m, h0->n, gbase, ldg, sign);
     prof_end(h0, PROF_GRAD);
     ACC_HIP(hipGetLastError());
@@ -3424,22 +3087,21 @@ int launch_test_gemm(const double* A, int64_t lda, const double* B, int64_t ldb,
     op.A = A; op.B = B; op.C = C; op.lda = lda; op.ldb = ldb; op.ldc = ldc;
     op.M = (int)M; op.N = (int)N; op.K = (int)K; op.lower_only = 0; op.alpha = alpha; op.beta = beta;
     if (config == 1) {
+        int dev = 0;
+        ACC_HIP(hipGetDevice(&dev));
         if (b_kmajor) {
             using T = TileBig<true>;
-            ACC_TRY(set_lds(gemm_big_kernel<T>, T::LDS_BYTES));
             dim3 grid((unsigned)((N + T::BN - 1) / T::BN), (unsigned)((M + T::BM - 1) / T::BM));
-            gemm_big_kernel<T><<<grid, NTHREADS, T::LDS_BYTES, s>>>(op);
+            ACC_LAUNCH_LDS(dev, gemm_big_kernel<T>, grid, NTHREADS, T::LDS_BYTES, s, op);
         } else {
             using T = TileBig<false>;
-            ACC_TRY(set_lds(gemm_big_kernel<T>, T::LDS_BYTES));
             dim3 grid((unsigned)((N + T::BN - 1) / T::BN), (unsigned)((M + T::BM - 1) / T::BM));
-            gemm_big_kernel<T><<<grid, NTHREADS, T::LDS_BYTES, s>>>(op);
+            ACC_LAUNCH_LDS(dev, gemm_big_kernel<T>, grid, NTHREADS, T::LDS_BYTES, s, op);
         }
     } else {
         GemmOp* d = nullptr;
         ACC_HIP(hipMalloc(&d, sizeof(GemmOp)));
         ACC_HIP(hipMemcpyAsync(d, &op, sizeof(GemmOp), hipMemcpyHostToDevice, s));
-        ACC_TRY(set_lds_gemm_ops());
         int rc = launch_gemm_ops(d, 1, (int)M, (int)N, b_kmajor != 0, s);
         hipStreamSynchronize(s);
         hipFree(d);

@@ -3,9 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/accbpg_hip.h"
+#include "dopt_plan.hpp"
 
 namespace accbpg {
 
@@ -28,33 +32,29 @@ void note_tiles_fallback(const char* where);
         if (rc__ != ACCBPG_OK) return rc__; \
     } while (0)
 
-// one product of the batched small-GEMM kernel: C = alpha * A * op(B) + beta * C
-struct GemmOp {
-    const double* A;
-    const double* B;
-    double* C;
-    int64_t lda, ldb, ldc;
-    int32_t M, N, K;
-    int32_t lower_only;     // skip tiles / elements strictly above the diagonal of C
-    int32_t tri;            // bit 0: B[k][col] is zero for k < col; bit 1: A[row][k] is zero for k > row (k ranges are cut)
-    int32_t koff;           // k index of this op's first k-step in the coordinates of those triangles (split-K pieces)
-    double alpha, beta;
-};
-
-// sum of split-K partial products: C[r][c] = sum_p P[p*M*N + r*N + c]
-struct RedOp {
-    double* C;
-    const double* P;
-    int64_t ldc;
-    int32_t M, N, ns, pad;
-};
-
-// entry of the Gram tile list: one BM x BN tile (d1 < 0), or a pair of 128 x 128 diagonal blocks d1, d2
-// (128-block indices) that run as "dual" tiles over half of K each (mfma_tile.hpp)
-struct TileRC {
-    int32_t rb, cb;
-    int32_t d1 = -1, d2 = -1;
-};
+// A kernel's limit of dynamic LDS is raised at the launch site, the first time the kernel is launched on a device (the
+// attribute belongs to that device's function object): on this runtime a launch that asks for more dynamic LDS than the
+// kernel's limit reports NO error -- not from the launch, not from hipGetLastError, not from a synchronize -- and leaves
+// garbage (measured; a Gram variant that had been left out of a list of attribute calls went unnoticed until its results
+// were compared).  Every launch that passes dynamic LDS goes through ACC_LAUNCH_LDS.
+inline int ensure_lds(int device, const void* kernel, int bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, int> limit;
+    std::lock_guard<std::mutex> guard(mu);
+    const std::pair<int, const void*> key(device, kernel);
+    auto it = limit.find(key);
+    if (it != limit.end() && it->second >= bytes) return ACCBPG_OK;
+    ACC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    limit[key] = bytes;
+    return ACCBPG_OK;
+}
+// (a kernel name with template commas goes in parentheses)
+#define ACC_LAUNCH_LDS(device, kernel, grid, block, lds, stream, ...)                        \
+    do {                                                                                     \
+        auto k__ = kernel;                                                                   \
+        ACC_TRY(::accbpg::ensure_lds((device), reinterpret_cast<const void*>(k__), (int)(lds))); \
+        k__<<<(grid), (block), (lds), (stream)>>>(__VA_ARGS__);                              \
+    } while (0)
 
 // A batch of same-shaped instances evaluated by ONE launch per kernel family (blockIdx.y = position among the
 // active instances): the per-instance pointers live in a device table, the active set travels as a kernel argument.
@@ -170,7 +170,6 @@ struct FwRunSlot {
     double rec[16];
 };
 
-struct CholJob { int i, j; };                     // i == j: owner of the diagonal tile (and of (i, i-1))
 struct CholInst {                                  // one factorisation (one entry per instance of a batched launch)
     const double* src;      // matrix to factor (lower triangle significant), leading dimension ld
     double* L;              // off-diagonal tiles of the factor (may be src: in place)
@@ -185,7 +184,6 @@ struct CholInst {                                  // one factorisation (one ent
     long long* trace;       // development aid: CT_NSTAMP wall-clock stamps per block column from the chain workgroups (or null)
 };
 
-constexpr int NB = 64;          // Cholesky / inverse block size
 constexpr int FLAG_NOT_PD = 0;  // index into the device flag array
 constexpr int FLAG_NEG_X = 1;
 constexpr int FLAG_NONPOS = 2;
@@ -240,8 +238,7 @@ struct accbpg_dopt {
     accbpg::GemmOp* ops = nullptr;            // device op table of the inverse merges
     std::vector<accbpg::GemmOp> ops_host;
     std::vector<accbpg::RedOp> red_host;
-    // launch list of the inverse merges: kind 0 = products ops[begin, end), kind 1 = partial-sum reductions red[begin, end)
-    struct MergeStage { int kind, begin, end, maxm, maxn; };
+    using MergeStage = accbpg::MergeStage;    // launch list of the inverse merges (dopt_plan.hpp)
     std::vector<MergeStage> merge_stages;
     accbpg::RedOp* red = nullptr;
     double* Pbuf = nullptr;     // m*m: split-K partial products of the top merge levels

@@ -23,12 +23,13 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "dopt_plan.hpp"
+
 namespace accbpg {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-constexpr int BK = 16;
 constexpr int SK = BK + 2;          // LDS row stride (doubles) of a k-contiguous image
 constexpr int NTHREADS = 256;
 
@@ -919,7 +920,7 @@ __device__ __forceinline__ void sched_post_barrier() {
 // The two instantiated shapes: "big" fills one CU with a 256x128 tile (wave tile 64x128, 256
 // accumulator VGPRs, one workgroup per CU); "small" is a 64x64 tile for the latency-bound
 // pieces (Cholesky trailing updates, inverse merges, small instances).
-template <bool BKM, bool EDGE = true> using TileBig = Tile<256, 128, 64, 128, BKM, EDGE>;
-template <bool BKM, bool EDGE = true> using TileSmall = Tile<64, 64, 32, 32, BKM, EDGE>;
+template <bool BKM, bool EDGE = true> using TileBig = Tile<TILE_BIG_M, TILE_BIG_N, 64, 128, BKM, EDGE>;
+template <bool BKM, bool EDGE = true> using TileSmall = Tile<TILE_SMALL_M, TILE_SMALL_N, 32, 32, BKM, EDGE>;
 
 }  // namespace accbpg

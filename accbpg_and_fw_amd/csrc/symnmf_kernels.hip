@@ -174,16 +174,12 @@ __global__ __launch_bounds__(YB) void symnmf_scalars_kernel(const double* __rest
 
 template <class T>
 int launch_mx(accbpg_symnmf* h, const double* X, hipStream_t s) {
-    static bool lds_set = false;
-    if (!lds_set) {
-        ACC_HIP(hipFuncSetAttribute((const void*)symnmf_mx_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    T::LDS_BYTES));
-        lds_set = true;
-    }
+    int dev = 0;
+    ACC_HIP(hipGetDevice(&dev));
     const bool va = ((reinterpret_cast<uintptr_t>(h->M) & 15) == 0) && ((h->ldm & 1) == 0);
     const bool vb = ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((h->r & 1) == 0);
     dim3 grid((unsigned)((h->n + T::BM - 1) / T::BM), (unsigned)((h->r + T::BN - 1) / T::BN), (unsigned)h->nsplit);
-    symnmf_mx_kernel<T><<<grid, NTHREADS, T::LDS_BYTES, s>>>(h->M, h->ldm, X, h->n, h->r, h->kchunk, h->P, va, vb);
+    ACC_LAUNCH_LDS(dev, symnmf_mx_kernel<T>, grid, NTHREADS, T::LDS_BYTES, s, h->M,h->ldm, X, h->n, h->r, h->kchunk, h->P, va, vb);
     ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }

@@ -55,18 +55,21 @@ def test_registers_fit_two_workgroups_per_cu(kernel):
 
 def test_lds_request_is_ct_lds_bytes(kernel):
     """What a workgroup gets is the dynamic size of its launches plus the kernel's static LDS (256 bytes while it
-    voted through the device library's workgroup reduction, none since).  Every launch and the attribute set at handle creation pass CT_LDS_BYTES, whose value
-    is that of the constants in the source; the static part has not grown."""
+    voted through the device library's workgroup reduction, none since).  Every launch (through ACC_LAUNCH_LDS, which
+    raises the kernel's limit to what the launch asks for) and the limit raised at handle creation, ahead of the
+    occupancy query, pass CT_LDS_BYTES, whose value is that of the constants in the source; the static part has not
+    grown."""
     src = open(SRC).read()
-    hdr = open(os.path.join(os.path.dirname(SRC), "internal.h")).read()
     const = {}
-    for text in (hdr, src):
+    for text in (open(os.path.join(os.path.dirname(SRC), "dopt_plan.hpp")).read(), src):
         for name, expr in re.findall(r"constexpr int (NB|SQ|POTRF_TB|CT_LDS_DOUBLES|CT_LDS_BYTES) = ([^;]+);", text):
             const[name] = eval(expr, {"__builtins__": {}}, dict(const))
     assert const["CT_LDS_BYTES"] == CT_LDS_BYTES, const
-    launches = re.findall(r"chol_tiles_kernel<<<.*?NTHREADS,\s*(\w+),", src)
+    assert not re.search(r"chol_tiles_kernel\s*<<<", src)          # no launch beside the ones counted here
+    launches = re.findall(r"ACC_LAUNCH_LDS\([^,]+, chol_tiles_kernel,.*?NTHREADS,\s*(\w+),", src)
     assert len(launches) >= 2 and set(launches) == {"CT_LDS_BYTES"}, launches
-    assert re.search(r"set_lds\(chol_tiles_kernel, CT_LDS_BYTES\)", src)
+    assert re.search(r"ensure_lds\(h->device, [^;]*\(chol_tiles_kernel\), CT_LDS_BYTES\)\);\s*int per_cu = 0;\s*"
+                     r"ACC_HIP\(hipOccupancyMaxActiveBlocksPerMultiprocessor\(&per_cu, chol_tiles_kernel, NTHREADS, CT_LDS_BYTES\)\)", src)
     static = _directive(kernel, ".amdhsa_group_segment_fixed_size")
     assert static <= CT_STATIC_LDS_BYTES, static
     assert 2 * (const["CT_LDS_BYTES"] + static) <= CU_LDS_BYTES

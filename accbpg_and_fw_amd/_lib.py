@@ -171,6 +171,8 @@ _SIGS = {
     "accbpg_dopt_factor_in_small_launches": (C.c_int, [_P, C.c_int]),
     "accbpg_debug_chol_variant": (C.c_int, [_P, C.c_int]),
     "accbpg_debug_plan_flags": (C.c_int, [C.c_int]),
+    "accbpg_debug_guard_bands": (C.c_int, [C.c_int64]),
+    "accbpg_debug_guard_check": (C.c_int, [C.POINTER(C.c_int64)]),
     "accbpg_debug_gemm_loop": (C.c_int, [C.c_int]),
     "accbpg_debug_prox_variant": (C.c_int, [C.c_int]),
     "accbpg_debug_prox_state": (C.c_int, [C.POINTER(C.c_int)]),

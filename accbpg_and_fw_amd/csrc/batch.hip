@@ -10,9 +10,9 @@ using namespace accbpg;
 extern "C" int accbpg_dopt_batch_destroy(accbpg_dopt_batch* b) {
     if (!b) return ACCBPG_OK;
     for (accbpg_dopt* h : b->inst) accbpg_dopt_destroy(h);
-    hipFree(b->table); hipFree(b->chol_table[0]); hipFree(b->chol_table[1]); hipFree(b->ops_all); hipFree(b->red_all);
-    hipFree(b->dscal_all); hipFree(b->vflags); hipFree(b->vout); hipFree(b->vpart); hipFree(b->vws); hipFree(b->fw_table);
-    hipFree(b->fw_runs); hipFree(b->fw_div_table);
+    acc_free(b->table); acc_free(b->chol_table[0]); acc_free(b->chol_table[1]); acc_free(b->ops_all); acc_free(b->red_all);
+    acc_free(b->dscal_all); acc_free(b->vflags); acc_free(b->vout); acc_free(b->vpart); acc_free(b->vws); acc_free(b->fw_table);
+    acc_free(b->fw_runs); acc_free(b->fw_div_table);
     if (b->fw_bsteps_pin) hipHostFree(b->fw_bsteps_pin);
     if (b->hpin) hipHostFree(b->hpin);
     if (b->vpin) hipHostFree(b->vpin);
@@ -24,7 +24,7 @@ static int batch_init(accbpg_dopt_batch* b, const double* const* V_host, int K, 
     ACC_HIP(hipGetDevice(&b->device));
     hipDeviceProp_t prop;
     ACC_HIP(hipGetDeviceProperties(&prop, b->device));
-    ACC_HIP(hipMalloc(&b->dscal_all, sizeof(double) * 24 * (size_t)K));
+    ACC_HIP(acc_malloc(&b->dscal_all, sizeof(double) * 24 * (size_t)K, "dscal_all"));
     ACC_HIP(hipMemset(b->dscal_all, 0, sizeof(double) * 24 * (size_t)K));
     ACC_HIP(hipHostMalloc(&b->hpin, sizeof(double) * 24 * (size_t)K, hipHostMallocDefault));
     // instances that share a launch: as many as have their one-launch factorisations resident together.  The first
@@ -79,18 +79,18 @@ static int batch_init(accbpg_dopt_batch* b, const double* const* V_host, int K, 
         ops.insert(ops.end(), h->ops_host.begin(), h->ops_host.end());
         reds.insert(reds.end(), h->red_host.begin(), h->red_host.end());
     }
-    ACC_HIP(hipMalloc(&b->table, sizeof(BatchInst) * K));
+    ACC_HIP(acc_malloc(&b->table, sizeof(BatchInst) * K, "table"));
     ACC_HIP(hipMemcpy(b->table, tab.data(), sizeof(BatchInst) * K, hipMemcpyHostToDevice));
-    ACC_HIP(hipMalloc(&b->chol_table[0], sizeof(CholInst) * K));
+    ACC_HIP(acc_malloc(&b->chol_table[0], sizeof(CholInst) * K, "chol_table[0]"));
     ACC_HIP(hipMemcpy(b->chol_table[0], c0.data(), sizeof(CholInst) * K, hipMemcpyHostToDevice));
-    ACC_HIP(hipMalloc(&b->chol_table[1], sizeof(CholInst) * K));
+    ACC_HIP(acc_malloc(&b->chol_table[1], sizeof(CholInst) * K, "chol_table[1]"));
     ACC_HIP(hipMemcpy(b->chol_table[1], c1.data(), sizeof(CholInst) * K, hipMemcpyHostToDevice));
     if (!ops.empty()) {
-        ACC_HIP(hipMalloc(&b->ops_all, sizeof(GemmOp) * ops.size()));
+        ACC_HIP(acc_malloc(&b->ops_all, sizeof(GemmOp) * ops.size(), "ops_all"));
         ACC_HIP(hipMemcpy(b->ops_all, ops.data(), sizeof(GemmOp) * ops.size(), hipMemcpyHostToDevice));
     }
     if (!reds.empty()) {
-        ACC_HIP(hipMalloc(&b->red_all, sizeof(RedOp) * reds.size()));
+        ACC_HIP(acc_malloc(&b->red_all, sizeof(RedOp) * reds.size(), "red_all"));
         ACC_HIP(hipMemcpy(b->red_all, reds.data(), sizeof(RedOp) * reds.size(), hipMemcpyHostToDevice));
     }
     return ACCBPG_OK;

@@ -55,22 +55,22 @@ int dopt_init(accbpg_dopt* h) {
     h->vec_ok = ((reinterpret_cast<uintptr_t>(h->V) & 15) == 0) && ((h->ldv & 1) == 0);
     h->big = (m >= 768) || (h->force_big && h->vec_ok && m >= 256 && (m % 256 == 0) && (n % 128 == 0));
     const size_t mm = sizeof(double) * (size_t)m * (size_t)m;
-    ACC_HIP(hipMalloc(&h->Lbuf, mm));
-    ACC_HIP(hipMalloc(&h->Wbuf, mm));
-    ACC_HIP(hipMalloc(&h->Tbuf, mm));
+    ACC_HIP(acc_malloc(&h->Lbuf, mm, "Lbuf"));
+    ACC_HIP(acc_malloc(&h->Wbuf, mm, "Wbuf"));
+    ACC_HIP(acc_malloc(&h->Tbuf, mm, "Tbuf"));
     ACC_HIP(hipMemset(h->Lbuf, 0, mm));
     ACC_HIP(hipMemset(h->Wbuf, 0, mm));     // the upper triangle of W must read as zero
     ACC_HIP(hipMemset(h->Tbuf, 0, mm));
     if (h->dscal_ext) {
         h->dscal = h->dscal_ext;                                // a slice of the batch's array (zeroed by the batch)
     } else {
-        ACC_HIP(hipMalloc(&h->dscal, sizeof(double) * 24));     // 16 scalars, then the status flags: one readback
+        ACC_HIP(acc_malloc(&h->dscal, sizeof(double) * 24, "dscal"));     // 16 scalars, then the status flags: one readback
         ACC_HIP(hipMemset(h->dscal, 0, sizeof(double) * 24));
     }
     h->dflag = reinterpret_cast<int*>(h->dscal + 16);
     ACC_HIP(hipHostMalloc(&h->hpin, sizeof(double) * 32, hipHostMallocDefault));
     const int64_t vws = std::max<int64_t>(vec_ws_doubles(n), 64 * n);
-    ACC_HIP(hipMalloc(&h->vws, sizeof(double) * (size_t)vws));
+    ACC_HIP(acc_malloc(&h->vws, sizeof(double) * (size_t)vws, "vws"));
     ACC_HIP(hipEventCreate(&h->ev_done));
     return build_plans(h);
 }
@@ -105,18 +105,18 @@ extern "C" int accbpg_dopt_destroy(accbpg_dopt* h) {
         auto& lk = h->val_peer->val_linked;
         lk.erase(std::remove(lk.begin(), lk.end(), h), lk.end());
     }
-    hipFree(h->val_copy);
-    hipFree(h->trial_stat);
+    acc_free(h->val_copy);
+    acc_free(h->trial_stat);
     if (h->trial_pin) hipHostFree(h->trial_pin);
-    hipFree(h->Vblk);
-    hipFree(h->Lbuf); hipFree(h->Wbuf); hipFree(h->Tbuf); hipFree(h->slabs); hipFree(h->tiles); hipFree(h->wg_ranges); hipFree(h->gram_cstart); hipFree(h->gram_contrib);
-    if (!h->dscal_ext) hipFree(h->dscal);
-    hipFree(h->vws); hipFree(h->xbuf); hipFree(h->ops); hipFree(h->chol_op); hipFree(h->red); hipFree(h->Pbuf);
-    hipFree(h->fw_x); hipFree(h->fw_w); hipFree(h->fw_H); hipFree(h->fw_hv);
-    hipFree(h->chol_jobs); hipFree(h->chol_ready); hipFree(h->chol_aux); hipFree(h->chol_hand); hipFree(h->Gbuf);
-    hipFree(h->fw_run);
+    acc_free(h->Vblk);
+    acc_free(h->Lbuf); acc_free(h->Wbuf); acc_free(h->Tbuf); acc_free(h->slabs); acc_free(h->tiles); acc_free(h->wg_ranges); acc_free(h->gram_cstart); acc_free(h->gram_contrib);
+    if (!h->dscal_ext) acc_free(h->dscal);
+    acc_free(h->vws); acc_free(h->xbuf); acc_free(h->ops); acc_free(h->chol_op); acc_free(h->red); acc_free(h->Pbuf);
+    acc_free(h->fw_x); acc_free(h->fw_w); acc_free(h->fw_H); acc_free(h->fw_hv);
+    acc_free(h->chol_jobs); acc_free(h->chol_ready); acc_free(h->chol_aux); acc_free(h->chol_hand); acc_free(h->Gbuf);
+    acc_free(h->fw_run);
     if (h->fw_steps_pin) hipHostFree(h->fw_steps_pin);
-    hipFree(h->fw_div_ws);
+    acc_free(h->fw_div_ws);
     if (h->fw_div_pin) hipHostFree(h->fw_div_pin);
     if (h->hpin) hipHostFree(h->hpin);
     if (h->ev_done) hipEventDestroy(h->ev_done);
@@ -192,9 +192,9 @@ static void value_forget(accbpg_dopt* h) {
 static int value_alloc(accbpg_dopt* h) {
     if (h->val_copy) return ACCBPG_OK;
     double* p = nullptr;
-    ACC_HIP(hipMalloc(&p, sizeof(double) * ((size_t)h->n + 2)));
+    ACC_HIP(acc_malloc(&p, sizeof(double) * ((size_t)h->n + 2), "val_copy"));
     if (hipMemsetAsync(p + h->n, 0, sizeof(double) * 2, h->stream) != hipSuccess) {
-        hipFree(p);
+        acc_free(p);
         set_last_error("accbpg_dopt_func_grad: could not clear the compare word");
         return ACCBPG_ERR_HIP;
     }
@@ -378,10 +378,10 @@ extern "C" int accbpg_dopt_burg_trial(accbpg_dopt* h, const double* x_prev_dev, 
     hipStream_t s = h->stream;
     if (!h->trial_stat) {
         double* p = nullptr;
-        ACC_HIP(hipMalloc(&p, sizeof(double) * TRIAL_DOUBLES));
+        ACC_HIP(acc_malloc(&p, sizeof(double) * TRIAL_DOUBLES, "trial_stat"));
         if (hipMemset(p, 0, sizeof(double) * TRIAL_DOUBLES) != hipSuccess ||
             hipHostMalloc(&h->trial_pin, sizeof(double) * TRIAL_DOUBLES, hipHostMallocDefault) != hipSuccess) {
-            hipFree(p);
+            acc_free(p);
             set_last_error("accbpg_dopt_burg_trial: could not allocate the status block");
             return ACCBPG_ERR_HIP;
         }
@@ -713,7 +713,7 @@ extern "C" int accbpg_debug_chol_trace(accbpg_dopt* h, const double* gram_dev, i
     }
     const int T = (int)((h->m + NB - 1) / NB);
     const size_t bytes = sizeof(long long) * (size_t)T * 32;
-    if (!h->chol_trace) ACC_HIP(hipMalloc(&h->chol_trace, bytes));
+    if (!h->chol_trace) ACC_HIP(acc_malloc(&h->chol_trace, bytes, "chol_trace"));
     ACC_HIP(hipMemsetAsync(h->chol_trace, 0, bytes, h->stream));
     int rc = launch_cholesky(h, h->Lbuf, with_inverse ? h->Wbuf : nullptr, nullptr, gram_dev);
     if (rc == ACCBPG_OK) {
@@ -721,7 +721,7 @@ extern "C" int accbpg_debug_chol_trace(accbpg_dopt* h, const double* gram_dev, i
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = ACCBPG_ERR_HIP;
     }
-    hipFree(h->chol_trace);
+    acc_free(h->chol_trace);
     h->chol_trace = nullptr;
     return rc;
 }

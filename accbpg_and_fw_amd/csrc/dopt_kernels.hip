@@ -2528,9 +2528,9 @@ static int with_gemm_loop(F&& f) {
 
 // copies a plan table to the device (an empty one: nothing allocated, *dev stays null)
 template <class T>
-static int upload(const std::vector<T>& v, T** dev) {
+static int upload(const std::vector<T>& v, T** dev, const char* label) {
     if (v.empty()) return ACCBPG_OK;
-    ACC_HIP(hipMalloc(dev, sizeof(T) * v.size()));
+    ACC_HIP(acc_malloc(dev, sizeof(T) * v.size(), label));
     ACC_HIP(hipMemcpy(*dev, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
     return ACCBPG_OK;
 }
@@ -2556,7 +2556,7 @@ int build_plans(accbpg_dopt* h) {
     if (gp.want_block_copy) {
         // the copy of V stored block by block ([block][row][gram_nc columns]) that the Gram launches then read
         const size_t bytes = sizeof(double) * (size_t)m * (size_t)h->n;
-        if (hipMalloc(&h->Vblk, bytes) == hipSuccess) {
+        if (acc_malloc(&h->Vblk, bytes, "Vblk") == hipSuccess) {
             for (int c = 0; c < gp.chunks; ++c)
                 ACC_HIP(hipMemcpy2DAsync(h->Vblk + (size_t)c * m * gp.nc, sizeof(double) * gp.nc,
                                          h->V + (size_t)c * gp.nc, sizeof(double) * (size_t)h->ldv,
@@ -2567,23 +2567,23 @@ int build_plans(accbpg_dopt* h) {
             h->Vblk = nullptr;
         }
     }
-    ACC_TRY(upload(gp.tiles, &h->tiles));
-    ACC_TRY(upload(gp.ranges, &h->wg_ranges));
-    ACC_TRY(upload(gp.cstart, &h->gram_cstart));
-    ACC_TRY(upload(gp.contrib, &h->gram_contrib));
+    ACC_TRY(upload(gp.tiles, &h->tiles, "tiles"));
+    ACC_TRY(upload(gp.ranges, &h->wg_ranges, "wg_ranges"));
+    ACC_TRY(upload(gp.cstart, &h->gram_cstart, "gram_cstart"));
+    ACC_TRY(upload(gp.contrib, &h->gram_contrib, "gram_contrib"));
     const size_t tile_doubles = h->big ? (size_t)TILE_BIG_M * TILE_BIG_N : (size_t)TILE_SMALL_M * TILE_SMALL_N;
-    ACC_HIP(hipMalloc(&h->slabs, sizeof(double) * (size_t)gp.grid * gp.nslot * tile_doubles));
+    ACC_HIP(acc_malloc(&h->slabs, sizeof(double) * (size_t)gp.grid * gp.nslot * tile_doubles, "slabs"));
 
     // ---- inverse merges: binary tree over the NB-blocks of L, long products split along K into Pbuf
-    ACC_HIP(hipMalloc(&h->Pbuf, sizeof(double) * (size_t)m * m));
+    ACC_HIP(acc_malloc(&h->Pbuf, sizeof(double) * (size_t)m * m, "Pbuf"));
     MergePlan mp = plan_merges(m, h->Lbuf, h->Wbuf, h->Tbuf, h->Pbuf);
     h->ops_host = std::move(mp.ops);
     h->red_host = std::move(mp.reds);
     h->merge_stages = std::move(mp.stages);
-    ACC_TRY(upload(h->ops_host, &h->ops));
-    ACC_TRY(upload(h->red_host, &h->red));
+    ACC_TRY(upload(h->ops_host, &h->ops, "ops"));
+    ACC_TRY(upload(h->red_host, &h->red, "red"));
     const int T = (int)((m + NB - 1) / NB);
-    ACC_HIP(hipMalloc(&h->chol_op, sizeof(GemmOp) * (size_t)(T + 1)));
+    ACC_HIP(acc_malloc(&h->chol_op, sizeof(GemmOp) * (size_t)(T + 1), "chol_op"));
 
     // ---- one-launch Cholesky: all its workgroups must be resident at once
     if (T <= CT_TMAX) {
@@ -2596,13 +2596,13 @@ int build_plans(accbpg_dopt* h) {
         h->chol_tiles_ok = per_cu >= 1 && (int64_t)jobs.size() <= (int64_t)h->chol_slots;
         if (h->chol_tiles_ok) {
             CholJob* jobs_dev = nullptr;
-            ACC_TRY(upload(jobs, &jobs_dev));
+            ACC_TRY(upload(jobs, &jobs_dev, "chol_jobs"));
             h->chol_jobs = jobs_dev;
-            ACC_HIP(hipMalloc(&h->chol_ready, sizeof(int) * (size_t)(T * T + 5 * T)));
+            ACC_HIP(acc_malloc(&h->chol_ready, sizeof(int) * (size_t)(T * T + 5 * T), "chol_ready"));
             ACC_HIP(hipMemset(h->chol_ready, 0, sizeof(int) * (size_t)(T * T + 5 * T)));
-            ACC_HIP(hipMalloc(&h->chol_hand, sizeof(double) * (size_t)T * NB * NB));
-            ACC_HIP(hipMalloc(&h->chol_aux, sizeof(double) * (size_t)T * CT_AUX));
-            ACC_HIP(hipMalloc(&h->Gbuf, sizeof(double) * (size_t)m * m));
+            ACC_HIP(acc_malloc(&h->chol_hand, sizeof(double) * (size_t)T * NB * NB, "chol_hand"));
+            ACC_HIP(acc_malloc(&h->chol_aux, sizeof(double) * (size_t)T * CT_AUX, "chol_aux"));
+            ACC_HIP(acc_malloc(&h->Gbuf, sizeof(double) * (size_t)m * m, "Gbuf"));
             ACC_HIP(hipMemset(h->Gbuf, 0, sizeof(double) * (size_t)m * m));
         }
     }
@@ -2734,7 +2734,7 @@ int launch_gram(accbpg_dopt* h, const double* x, double* gram) {
     bool xal = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     if (!xal && (h->has_duals || h->gram_chunks > 1)) {
         // the tile list was built for the direct-to-LDS kernel, which reads x in 16-byte pieces
-        if (!h->xbuf) ACC_HIP(hipMalloc(&h->xbuf, sizeof(double) * (size_t)h->n));
+        if (!h->xbuf) ACC_HIP(acc_malloc(&h->xbuf, sizeof(double) * (size_t)h->n, "xbuf"));
         ACC_TRY(device_copy(h->xbuf, x, (size_t)h->n, h->stream));
         x = h->xbuf;
         xal = true;
@@ -3100,11 +3100,11 @@ int launch_test_gemm(const double* A, int64_t lda, const double* B, int64_t ldb,
         }
     } else {
         GemmOp* d = nullptr;
-        ACC_HIP(hipMalloc(&d, sizeof(GemmOp)));
+        ACC_HIP(acc_malloc(&d, sizeof(GemmOp), "test_gemm op"));
         ACC_HIP(hipMemcpyAsync(d, &op, sizeof(GemmOp), hipMemcpyHostToDevice, s));
         int rc = launch_gemm_ops(d, 1, (int)M, (int)N, b_kmajor != 0, s);
         hipStreamSynchronize(s);
-        hipFree(d);
+        acc_free(d);
         return rc;
     }
     ACC_HIP(hipGetLastError());
@@ -3117,7 +3117,7 @@ int pipe_probe(int iters, int mode, double* ms_out, hipStream_t s) {
     ACC_HIP(hipGetDevice(&dev));
     ACC_HIP(hipGetDeviceProperties(&prop, dev));
     double* sink = nullptr;
-    ACC_HIP(hipMalloc(&sink, 8));
+    ACC_HIP(acc_malloc(&sink, 8, "sink"));
     hipEvent_t a, b;
     ACC_HIP(hipEventCreate(&a));
     ACC_HIP(hipEventCreate(&b));
@@ -3129,7 +3129,7 @@ int pipe_probe(int iters, int mode, double* ms_out, hipStream_t s) {
     float ms = 0.f;
     ACC_HIP(hipEventElapsedTime(&ms, a, b));
     *ms_out = ms;
-    hipEventDestroy(a); hipEventDestroy(b); hipFree(sink);
+    hipEventDestroy(a); hipEventDestroy(b); acc_free(sink);
     return ACCBPG_OK;
 }
 
@@ -3140,7 +3140,7 @@ int mfma_peak(int iters, double* tflops, hipStream_t s) {
     ACC_HIP(hipGetDeviceProperties(&prop, dev));
     const int blocks = prop.multiProcessorCount;
     double* sink = nullptr;
-    ACC_HIP(hipMalloc(&sink, 8));
+    ACC_HIP(acc_malloc(&sink, 8, "sink"));
     hipEvent_t a, b;
     ACC_HIP(hipEventCreate(&a));
     ACC_HIP(hipEventCreate(&b));
@@ -3155,7 +3155,7 @@ int mfma_peak(int iters, double* tflops, hipStream_t s) {
     *tflops = flops / (ms * 1e-3) * 1e-12;
     hipEventDestroy(a);
     hipEventDestroy(b);
-    hipFree(sink);
+    acc_free(sink);
     return ACCBPG_OK;
 }
 

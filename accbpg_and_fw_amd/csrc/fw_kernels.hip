@@ -887,10 +887,10 @@ using namespace accbpg;
 static int fw_alloc(accbpg_dopt* h) {
     if (h->fw_x) return ACCBPG_OK;
     ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_hpin_dev), h->hpin, 0));   // the pinned record, as the device addresses it
-    ACC_HIP(hipMalloc(&h->fw_x, sizeof(double) * h->n));
-    ACC_HIP(hipMalloc(&h->fw_w, sizeof(double) * h->n));
-    ACC_HIP(hipMalloc(&h->fw_H, sizeof(double) * h->m * h->m));
-    ACC_HIP(hipMalloc(&h->fw_hv, sizeof(double) * fw_scratch_doubles(h->m)));
+    ACC_HIP(acc_malloc(&h->fw_x, sizeof(double) * h->n, "fw_x"));
+    ACC_HIP(acc_malloc(&h->fw_w, sizeof(double) * h->n, "fw_w"));
+    ACC_HIP(acc_malloc(&h->fw_H, sizeof(double) * h->m * h->m, "fw_H"));
+    ACC_HIP(acc_malloc(&h->fw_hv, sizeof(double) * fw_scratch_doubles(h->m), "fw_hv"));
     h->fw = FwInst{h->fw_x, h->fw_w, h->fw_H, h->fw_hv, h->V, h->vws, h->dscal + 10, h->fw_hpin_dev, h->vec_ok ? 1 : 0};
     return ACCBPG_OK;
 }
@@ -1209,7 +1209,7 @@ static int fw_run_alloc(accbpg_dopt* h) {
                               hipHostMallocDefault));
         ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_steps_dev), h->fw_steps_pin, 0));
     }
-    if (!h->fw_run) ACC_HIP(hipMalloc(reinterpret_cast<void**>(&h->fw_run), sizeof(FwRunSlot)));
+    if (!h->fw_run) ACC_HIP(acc_malloc(reinterpret_cast<void**>(&h->fw_run), sizeof(FwRunSlot), "fw_run"));
     return ACCBPG_OK;
 }
 
@@ -1279,7 +1279,7 @@ static int fw_div_alloc(accbpg_dopt* h) {
         ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fw_div_pin), sizeof(double) * 16, hipHostMallocDefault));
         ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_div_pin_dev), h->fw_div_pin, 0));
     }
-    ACC_HIP(hipMalloc(&h->fw_div_ws, sizeof(double) * fw_div_ws_doubles(h->n)));
+    ACC_HIP(acc_malloc(&h->fw_div_ws, sizeof(double) * fw_div_ws_doubles(h->n), "fw_div_ws"));
     return ACCBPG_OK;
 }
 
@@ -1371,7 +1371,7 @@ static int fw_batch_table(accbpg_dopt_batch* b) {
         ACC_TRY(fw_alloc(h));
         tab[i] = h->fw;
     }
-    ACC_HIP(hipMalloc(&b->fw_table, sizeof(FwInst) * (size_t)b->K));
+    ACC_HIP(acc_malloc(&b->fw_table, sizeof(FwInst) * (size_t)b->K, "fw_table"));
     ACC_HIP(hipMemcpy(b->fw_table, tab.data(), sizeof(FwInst) * (size_t)b->K, hipMemcpyHostToDevice));
     return ACCBPG_OK;
 }
@@ -1490,7 +1490,7 @@ static int fw_div_batch_table(accbpg_dopt_batch* b) {
         ACC_TRY(fw_div_alloc(h));
         tab[i] = FwDivInst{h->fw_div_ws, h->fw_div_pin_dev};
     }
-    ACC_HIP(hipMalloc(&b->fw_div_table, sizeof(FwDivInst) * (size_t)b->K));
+    ACC_HIP(acc_malloc(&b->fw_div_table, sizeof(FwDivInst) * (size_t)b->K, "fw_div_table"));
     ACC_HIP(hipMemcpy(b->fw_div_table, tab.data(), sizeof(FwDivInst) * (size_t)b->K, hipMemcpyHostToDevice));
     return ACCBPG_OK;
 }
@@ -1611,7 +1611,7 @@ static int fw_batch_run_alloc(accbpg_dopt_batch* b) {
                               sizeof(accbpg_fw_step) * ACCBPG_FW_RUN_MAX * (size_t)b->K, hipHostMallocDefault));
         ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->fw_bsteps_dev), b->fw_bsteps_pin, 0));
     }
-    if (!b->fw_runs) ACC_HIP(hipMalloc(reinterpret_cast<void**>(&b->fw_runs), sizeof(FwRunSlot) * (size_t)b->K));
+    if (!b->fw_runs) ACC_HIP(acc_malloc(reinterpret_cast<void**>(&b->fw_runs), sizeof(FwRunSlot) * (size_t)b->K, "fw_runs"));
     return ACCBPG_OK;
 }
 

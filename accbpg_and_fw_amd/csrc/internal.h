@@ -16,6 +16,16 @@ namespace accbpg {
 void set_last_error(const char* fmt, ...);
 void note_tiles_fallback(const char* where);
 
+// Every device allocation of the library goes through this pair (guard_alloc.hip): hipMalloc / hipFree, unless
+// accbpg_debug_guard_bands is on, when the allocation gets a sentinel band on either side.  label names the buffer in
+// the report of accbpg_debug_guard_check.  Pinned host memory does not come from here.
+hipError_t acc_malloc(void** p, size_t bytes, const char* label);
+hipError_t acc_free(void* p);
+template <class T>
+inline hipError_t acc_malloc(T** p, size_t bytes, const char* label) {
+    return acc_malloc(reinterpret_cast<void**>(p), bytes, label);
+}
+
 #define ACC_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t e__ = (call);                                                              \

@@ -212,7 +212,7 @@ extern "C" int accbpg_dopt_kyinit(accbpg_dopt* h, const double* B_dev, int64_t* 
     const size_t qd = Q_dev ? 0 : m * m;
     const size_t doubles = qd + n + 3 * m + KY_MAXREC * sizeof(MinMaxRec) / sizeof(double) + 2 * m;
     double* buf = nullptr;
-    ACC_HIP(hipMalloc(&buf, doubles * sizeof(double)));
+    ACC_HIP(acc_malloc(&buf, doubles * sizeof(double), "kyinit scratch"));
     double* Q = Q_dev ? Q_dev : buf;
     double* w = buf + qd;
     double* q = w + n;
@@ -227,7 +227,7 @@ extern "C" int accbpg_dopt_kyinit(accbpg_dopt* h, const double* B_dev, int64_t* 
     };
     const int rc = run();
     const hipError_t waited = hipStreamSynchronize(h->stream);  // (also behind an error: nothing stays in flight)
-    hipFree(buf);
+    acc_free(buf);
     if (rc != ACCBPG_OK) return rc;
     ACC_HIP(waited);
     return ACCBPG_OK;
@@ -245,7 +245,7 @@ extern "C" int accbpg_dopt_batch_kyinit(accbpg_dopt_batch* b, const double* B_de
     const size_t per = qd + n + 3 * m + KY_MAXREC * sizeof(MinMaxRec) / sizeof(double);
     const size_t bytes = (K * per + K * 2 * m) * sizeof(double) + K * sizeof(KyInst);
     double* buf = nullptr;
-    ACC_HIP(hipMalloc(&buf, bytes));
+    ACC_HIP(acc_malloc(&buf, bytes, "batch kyinit scratch"));
     int64_t* picked = reinterpret_cast<int64_t*>(buf + K * per);
     KyInst* tab_dev = reinterpret_cast<KyInst*>(picked + K * 2 * m);
     std::vector<KyInst> tab(K);                                 // (alive until the stream has been waited for)
@@ -266,7 +266,7 @@ extern "C" int accbpg_dopt_batch_kyinit(accbpg_dopt_batch* b, const double* B_de
     };
     const int rc = run();
     const hipError_t waited = hipStreamSynchronize(s);          // (also behind an error: nothing stays in flight)
-    hipFree(buf);
+    acc_free(buf);
     if (rc != ACCBPG_OK) return rc;
     ACC_HIP(waited);
     return ACCBPG_OK;

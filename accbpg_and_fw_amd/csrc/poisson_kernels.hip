@@ -139,17 +139,17 @@ static int poisson_init(accbpg_poisson* h) {
     if (hold > prop.sharedMemPerBlock) hold = prop.sharedMemPerBlock;
     h->hold_lds = (unsigned)(hold & ~(size_t)255);
     h->vec_ok = ((reinterpret_cast<uintptr_t>(h->A) & 15) == 0) && ((h->lda & 1) == 0);
-    ACC_HIP(hipMalloc(&h->Ax, sizeof(double) * (size_t)h->m));
-    ACC_HIP(hipMalloc(&h->r, sizeof(double) * (size_t)h->m));
-    ACC_HIP(hipMalloc(&h->t, sizeof(double) * (size_t)h->m));
-    ACC_HIP(hipMalloc(&h->upart, sizeof(double) * (size_t)VT_MAXSPLIT * (size_t)h->n));
-    ACC_HIP(hipMalloc(&h->dout, sizeof(double) * 4));
+    ACC_HIP(acc_malloc(&h->Ax, sizeof(double) * (size_t)h->m, "Ax"));
+    ACC_HIP(acc_malloc(&h->r, sizeof(double) * (size_t)h->m, "r"));
+    ACC_HIP(acc_malloc(&h->t, sizeof(double) * (size_t)h->m, "t"));
+    ACC_HIP(acc_malloc(&h->upart, sizeof(double) * (size_t)VT_MAXSPLIT * (size_t)h->n, "upart"));
+    ACC_HIP(acc_malloc(&h->dout, sizeof(double) * 4, "dout"));
     ACC_HIP(hipHostMalloc(&h->hpin, sizeof(double) * 4, hipHostMallocDefault));
     return ACCBPG_OK;
 }
 
 static void objective_free(accbpg_poisson* h) {
-    hipFree(h->Ax); hipFree(h->r); hipFree(h->t); hipFree(h->upart); hipFree(h->dout);
+    acc_free(h->Ax); acc_free(h->r); acc_free(h->t); acc_free(h->upart); acc_free(h->dout);
     if (h->hpin) hipHostFree(h->hpin);
 }
 

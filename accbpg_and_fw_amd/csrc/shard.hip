@@ -121,7 +121,7 @@ extern "C" int accbpg_dopt_shard_destroy(accbpg_dopt_shard* s) {
         Rccl* r = rccl();
         if (r->ok) r->CommDestroy(s->comm);
     }
-    hipFree(s->gram); hipFree(s->msg); hipFree(s->gath);
+    acc_free(s->gram); acc_free(s->msg); acc_free(s->gath);
     if (s->hcount) hipHostFree(s->hcount);
     delete s;
     return ACCBPG_OK;
@@ -151,15 +151,15 @@ extern "C" int accbpg_dopt_shard_create(accbpg_dopt* local, int64_t n, int world
     s->msg_len = s->tri + 2 - (s->tri & 1);
     s->piece = (n + world - 1) / world;
     auto fail = [&](int rc) { accbpg_dopt_shard_destroy(s); return rc; };
-    if (hipMalloc(&s->gram, sizeof(double) * (size_t)m * m) != hipSuccess ||
-        hipMalloc(&s->msg, sizeof(double) * (size_t)s->msg_len) != hipSuccess ||
+    if (acc_malloc(&s->gram, sizeof(double) * (size_t)m * m, "gram") != hipSuccess ||
+        acc_malloc(&s->msg, sizeof(double) * (size_t)s->msg_len, "msg") != hipSuccess ||
         hipMemset(s->msg, 0, sizeof(double) * (size_t)s->msg_len) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&s->hcount), sizeof(double)) != hipSuccess) {
         set_last_error("accbpg_dopt_shard_create: out of device memory");
         return fail(ACCBPG_ERR_HIP);
     }
     if (n % world != 0 &&
-        hipMalloc(&s->gath, sizeof(double) * (size_t)world * s->piece) != hipSuccess) {
+        acc_malloc(&s->gath, sizeof(double) * (size_t)world * s->piece, "gath") != hipSuccess) {
         set_last_error("accbpg_dopt_shard_create: out of device memory");
         return fail(ACCBPG_ERR_HIP);
     }
@@ -235,9 +235,9 @@ extern "C" int accbpg_debug_shard_pad(accbpg_dopt_shard* s, int64_t extra) {
     if (!s || extra < 0) return ACCBPG_ERR_ARG;
     ACC_HIP(hipSetDevice(s->local->device));
     ACC_HIP(hipStreamSynchronize(s->local->stream));
-    hipFree(s->gath);
+    acc_free(s->gath);
     s->gath = nullptr;
     s->piece = (s->n + s->world - 1) / s->world + extra;
-    ACC_HIP(hipMalloc(&s->gath, sizeof(double) * (size_t)s->world * s->piece));
+    ACC_HIP(acc_malloc(&s->gath, sizeof(double) * (size_t)s->world * s->piece, "gath"));
     return ACCBPG_OK;
 }

@@ -209,7 +209,7 @@ void symnmf_plan(accbpg_symnmf* h) {
 using namespace accbpg;
 
 static void symnmf_free(accbpg_symnmf* h) {
-    hipFree(h->P); hipFree(h->S); hipFree(h->spart); hipFree(h->red); hipFree(h->dout);
+    acc_free(h->P); acc_free(h->S); acc_free(h->spart); acc_free(h->red); acc_free(h->dout);
     if (h->hpin) hipHostFree(h->hpin);
 }
 
@@ -227,11 +227,11 @@ extern "C" int accbpg_symnmf_create(const double* M_dev, int64_t n, int64_t ldm,
         h->num_cu = prop.multiProcessorCount;
         symnmf_plan(h);
         const size_t nr = (size_t)n * (size_t)r, rr = (size_t)r * (size_t)r;
-        if (hipMalloc(&h->P, sizeof(double) * nr * (size_t)h->nsplit) != hipSuccess ||
-            hipMalloc(&h->S, sizeof(double) * rr) != hipSuccess ||
-            hipMalloc(&h->spart, sizeof(double) * rr * (size_t)h->gchunks) != hipSuccess ||
-            hipMalloc(&h->red, sizeof(double) * (size_t)(h->sblocks + h->cblocks)) != hipSuccess ||
-            hipMalloc(&h->dout, sizeof(double) * 2) != hipSuccess ||
+        if (acc_malloc(&h->P, sizeof(double) * nr * (size_t)h->nsplit, "P") != hipSuccess ||
+            acc_malloc(&h->S, sizeof(double) * rr, "S") != hipSuccess ||
+            acc_malloc(&h->spart, sizeof(double) * rr * (size_t)h->gchunks, "spart") != hipSuccess ||
+            acc_malloc(&h->red, sizeof(double) * (size_t)(h->sblocks + h->cblocks), "red") != hipSuccess ||
+            acc_malloc(&h->dout, sizeof(double) * 2, "dout") != hipSuccess ||
             hipHostMalloc(&h->hpin, sizeof(double) * 2, hipHostMallocDefault) != hipSuccess) {
             set_last_error("accbpg_symnmf_create: out of memory");
             rc = ACCBPG_ERR_HIP;

@@ -551,8 +551,8 @@ static int ensure_scratch() {
         if (!b.pin) {
             ScratchBlock nb;
             ACC_HIP(hipHostMalloc(&nb.pin, 32 * sizeof(double), hipHostMallocDefault));
-            if (hipMalloc(&nb.flags, 8 * sizeof(int)) != hipSuccess || hipMalloc(&nb.out, 16 * sizeof(double)) != hipSuccess) {
-                hipHostFree(nb.pin); hipFree(nb.flags); hipFree(nb.out);
+            if (acc_malloc(&nb.flags, 8 * sizeof(int), "vec scratch flags") != hipSuccess || acc_malloc(&nb.out, 16 * sizeof(double), "vec scratch out") != hipSuccess) {
+                hipHostFree(nb.pin); acc_free(nb.flags); acc_free(nb.out);
                 set_last_error("accbpg: out of device memory for the vector-kernel scratch");
                 return ACCBPG_ERR_HIP;
             }
@@ -900,10 +900,10 @@ extern "C" int accbpg_burg_reg_div_prox(int kind, const double* y_dev, const dou
 // ------------------------------------------------------------------------------------------------------------
 static int batch_vec_scratch(accbpg_dopt_batch* b) {
     if (b->vflags) return ACCBPG_OK;
-    ACC_HIP(hipMalloc(&b->vflags, sizeof(int) * 8 * (size_t)b->K));
+    ACC_HIP(acc_malloc(&b->vflags, sizeof(int) * 8 * (size_t)b->K, "vflags"));
     ACC_HIP(hipMemset(b->vflags, 0, sizeof(int) * 8 * (size_t)b->K));
-    ACC_HIP(hipMalloc(&b->vout, sizeof(double) * 4 * (size_t)b->K));
-    ACC_HIP(hipMalloc(&b->vpart, sizeof(double) * 4 * RMAXBLK * (size_t)b->K));
+    ACC_HIP(acc_malloc(&b->vout, sizeof(double) * 4 * (size_t)b->K, "vout"));
+    ACC_HIP(acc_malloc(&b->vpart, sizeof(double) * 4 * RMAXBLK * (size_t)b->K, "vpart"));
     ACC_HIP(hipHostMalloc(&b->vpin, sizeof(double) * 8 * (size_t)b->K, hipHostMallocDefault));
     return ACCBPG_OK;
 }
@@ -940,7 +940,7 @@ extern "C" int accbpg_dopt_batch_burg_simplex_div_prox(accbpg_dopt_batch* b, con
         // summation of its own (burg_prox_multi_kernel), which the one-workgroup-per-instance kernel below does not
         // reproduce.  Run the single-instance prox itself, instance by instance, so that a batch stays bit for bit
         // equal to its instances evaluated on their own.
-        if (!b->vws) ACC_HIP(hipMalloc(&b->vws, sizeof(double) * (size_t)vec_ws_doubles(n)));
+        if (!b->vws) ACC_HIP(acc_malloc(&b->vws, sizeof(double) * (size_t)vec_ws_doubles(n), "vws"));
         for (int a = 0; a < act.n; ++a) {
             const int i = act.idx[a];
             int info[2] = {0, 0};

@@ -706,6 +706,20 @@ int accbpg_dopt_factor_in_small_launches(accbpg_dopt* h, int on);
  * tile list is longer than the grid (m >= 4096), instead of whole tiles per workgroup (A/B measurements). */
 int accbpg_debug_plan_flags(int flags);
 
+/* Debug switch, process wide: guard bands around the library's own device buffers.  While `bytes` > 0 (a multiple of
+ * 4096, so that the buffers keep their alignment and no kernel changes its form), every device buffer the library
+ * allocates gets `bytes` of the bit pattern 0x7FF8A5A5A5A5A5A5 in front of it and at least as many behind it (up to the
+ * end of the buffer's last 4096-byte page); the fill is synchronous.  0 turns the switch off (the default: the
+ * allocations are plain hipMalloc / hipFree); buffers made while it was on keep their bands until they are freed.
+ * ACCBPG_ERR_ARG for any other value. */
+int accbpg_debug_guard_bands(int64_t bytes);
+/* Synchronises the current device and compares the bands of every live banded buffer with the pattern.
+ * out3 = {live banded buffers, damaged bands, damaged bytes}.  When a band is damaged, accbpg_last_error names the first
+ * one (in address order): the buffer's label, the side, and the offset of the first damaged byte -- negative from the
+ * buffer's first byte for the front band, non-negative from the first byte past the buffer for the back band.  Returns
+ * ACCBPG_OK whether or not it found damage. */
+int accbpg_debug_guard_check(int64_t* out3);
+
 /* Development switch, process wide, read at every launch: the k-loop of the products on the 64x64 tile (the merges of
  * the triangular inverse, their batched form, the trailing updates of the m > 2048 Cholesky, accbpg_test_gemm config 0).
  * 0 = production (the global loads of three k-steps in flight), 1 = the loop with one k-step of look-ahead that

@@ -142,6 +142,11 @@ _SIGS = {
     "accbpg_kldiv_set_stream": (C.c_int, [_P, _P]),
     "accbpg_kldiv_func_grad": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_double), _P]),
     "accbpg_kldiv_get_ax": (C.c_int, [_P, _P]),
+    "accbpg_svm_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(_P)]),
+    "accbpg_svm_destroy": (C.c_int, [_P]),
+    "accbpg_svm_set_stream": (C.c_int, [_P, _P]),
+    "accbpg_svm_func_grad": (C.c_int, [_P, _P, C.c_double, C.c_int, C.POINTER(C.c_double), _P]),
+    "accbpg_svm_get_ax": (C.c_int, [_P, _P]),
     "accbpg_shannon_div_prox": (C.c_int, [C.c_int, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P]),
     "accbpg_shannon_ls_terms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double), _P, _P]),
     "accbpg_shannon_divergence": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double), _P, _P]),

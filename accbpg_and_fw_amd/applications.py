@@ -1,13 +1,14 @@
 """Problem factories (accbpg/applications.py): D-optimal design, Poisson and KL regression (on the orthant and on the
-simplex), and symmetric NMF."""
+simplex), symmetric NMF, and the soft-margin SVM on an l2 ball."""
 from __future__ import annotations
 
 import numpy as np
 
 from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, FrobeniusSymLoss,
-                        KLdivRegression, PoissonRegression, ShannonEntropyL1, SquaredL2Norm, SumOf2nd4thPowers,
-                        SumOf2nd4thPowersPositiveOrthant, vec_argminmax)
-from .utils import edge_point_on_simplex, load_libsvm_file, random_point_on_simplex
+                        KLdivRegression, PoissonRegression, PolyDiv, ShannonEntropyL1, SquaredL2Norm, SumOf2nd4thPowers,
+                        SumOf2nd4thPowersPositiveOrthant, SVM_fun, vec_argminmax)
+from .utils import (edge_point_on_simplex, generate_dataset_for_svm, load_libsvm_file, random_point_in_l2_ball,
+                    random_point_on_simplex)
 
 
 def D_opt_libsvm(filename):
@@ -345,3 +346,36 @@ def FrobeniusSymLossResMeasEx(M, r, noise=0.0):
     h_euklid = SquaredL2Norm()
     L = 1
     return f, [h, h_euklid], L, X0
+
+
+def _svm_ball_numbers(X, Y, lamda, center):
+    """The host arithmetic of svm_digits_ds_divs_ball (accbpg/applications.py:317-325) -> (radius, DS_mean,
+    DS_mean_quad, L, x0): the radius from the row norms of X without its last column, the reference's upper bound of
+    L, and x0 drawn from the global NumPy generator (random_point_in_l2_ball)."""
+    n = X.shape[1]
+    radius = min(n ** -1 * lamda ** -1 * np.sum(np.linalg.norm(X[:, :-1], axis=1)), (2 / lamda) ** 0.5)
+    if center is None:
+        center = np.zeros(n)
+    ds_mean = np.mean(np.linalg.norm(X, axis=1))
+    ds_mean_quad = np.mean(np.linalg.norm(X, axis=1) ** 2)
+    L = (ds_mean + min((2 * lamda) ** 0.5, ds_mean_quad)) * 0.08
+    x0 = random_point_in_l2_ball(center, radius, pos_dir=False)
+    return radius, ds_mean, ds_mean_quad, L, x0
+
+
+def svm_digits_ds_divs_ball(center=None, lamda=0.5, real_ds=False):
+    """Binary soft-margin SVM on an l2 ball (accbpg/applications.py:298-327): the two-class digits set of scikit-learn
+    (real_ds, labels -1 / +1) or generate_dataset_for_svm(700, 2000).  Returns f, [PolyDiv, SquaredL2Norm], L, x0,
+    radius with the reference's radius, L and x0 (one randn(n) and one uniform from the global generator)."""
+    if real_ds:
+        from sklearn.datasets import load_digits
+        X, Y = load_digits(n_class=2, return_X_y=True, as_frame=True)
+        Y = (Y > 0).astype(int) * 2 - 1
+        X = X.to_numpy()
+        Y = Y.to_numpy()
+    else:
+        X, Y = generate_dataset_for_svm(700, 2000)
+    f = SVM_fun(lamda, X, Y)
+    radius, _, _, L, x0 = _svm_ball_numbers(X, Y, lamda, center)
+    poly_h, sqL2_h = PolyDiv(X, lamda=lamda, radius=radius), SquaredL2Norm()
+    return f, [poly_h, sqL2_h], L, x0, radius

@@ -647,6 +647,103 @@ class KLdivRegression(PoissonRegression):
     _match_msg = "A and b size not matching"
 
 
+class SVM_fun(RSmoothFunction):
+    """f(x) = mean_i max(0, 1 - y_i (A x)_i) + (lamda/2) <x,x>, the soft-margin SVM (accbpg/functions.py:161-194).
+
+    ``A`` (m x n) and ``y`` (length m, any numeric type) may be NumPy arrays (copied to the GPU once) or CUDA tensors
+    (an fp64 ``A`` with unit column stride is borrowed with its row stride); ``self.lamda``, ``self.A`` and ``self.y``
+    stay readable as in the reference, and ``lamda`` is read at every call.  Each func_grad is two passes over A: A x
+    with the hinge terms in its epilogue, then A^T r with r_i = y_i where y_i (A x)_i < 1 (svm_kernels.hip).  The value
+    is formed on the host as sum_t / m + lamda / 2 * <x,x>, the reference's operation order."""
+
+    def __init__(self, lamda, A, y):
+        self.lamda = lamda
+        self.A = A
+        self.y = y
+        self.m = A.shape[0]
+        self.n = A.shape[1]
+        assert y.shape[0] == self.m, "SVM_fun: A and y sizes not matching"
+        if isinstance(A, torch.Tensor) and A.is_cuda and A.dtype == torch.float64 and A.dim() == 2 \
+                and (A.stride(1) == 1 or self.n == 1) and A.stride(0) >= self.n:
+            self._A = A                                         # borrowed with its row stride
+        else:
+            self._A, _ = to_dev(A)
+        self._y, _ = to_dev(y)
+        self._y = self._y.to(self._A.device)
+        lib = _lib.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self._A.device):
+            rc = lib.accbpg_svm_create(_ptr(self._A), self.m, self.n, self._A.stride(0), _ptr(self._y), _stream(),
+                                       C.byref(h))
+        _lib.check(rc, "accbpg_svm_create")
+        self._h = h
+        self._lib = lib
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.accbpg_svm_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def _eval(self, x, flag, lamda):
+        """The C entry at x: ((sum_t, <x,x>) or None, gradient tensor or None, x came from NumPy)."""
+        size = x.numel() if isinstance(x, torch.Tensor) else x.size
+        assert size == self.n, "SVM_fun: x.size not equal to n."
+        xd, was_np = to_dev(x)
+        xd = xd.reshape(-1)
+        g = torch.empty(self.n, dtype=torch.float64, device=self._A.device) if flag != 0 else None
+        fval = (C.c_double * 2)(0.0, 0.0)
+        with torch.cuda.device(self._A.device):
+            self._lib.accbpg_svm_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_svm_func_grad(self._h, _ptr(xd), float(lamda), int(flag), fval, _ptr(g))
+        _lib.check(rc, "accbpg_svm_func_grad")
+        sums = (np.float64(fval[0]), np.float64(fval[1])) if flag in (0, 2) else None
+        return sums, g, was_np
+
+    def _F_of(self, sums):
+        return sums[0] / self.m + self.lamda / 2 * sums[1]      # np.mean(...) + lamda/2 * np.dot(x, x)
+
+    def __call__(self, x):
+        return self.F(x)
+
+    def hinge_loss(self, x):
+        sums, _, _ = self._eval(x, 0, 0.0)
+        return sums[0] / self.m
+
+    def F(self, x):
+        sums, _, _ = self._eval(x, 0, 0.0)
+        return self._F_of(sums)
+
+    def gradient(self, x):
+        return self.func_grad(x, flag=1)
+
+    def subgradient_loss(self, x):
+        """mean_i 1[y_i (A x)_i < 1] y_i A_i (functions.py:179-181): the second pass without the lamda*x term."""
+        _, g, was_np = self._eval(x, 3, 0.0)
+        return from_dev(g, was_np)
+
+    def func_grad(self, x, flag=2):
+        """flag=0: function, flag=1: gradient, flag=2: function & gradient."""
+        assert flag in (0, 1, 2), "SVM_fun: flag must be 0, 1 or 2."
+        sums, g, was_np = self._eval(x, flag, self.lamda)
+        if flag == 0:
+            return self._F_of(sums)
+        if flag == 1:
+            return from_dev(g, was_np)
+        return self._F_of(sums), from_dev(g, was_np)
+
+    def margins(self):
+        """A x of the last evaluation (length m) as a NumPy vector: y * margins() are the margins the hinge saw."""
+        out = torch.empty(self.m, dtype=torch.float64, device=self._A.device)
+        with torch.cuda.device(self._A.device):
+            rc = self._lib.accbpg_svm_get_ax(self._h, _ptr(out))
+        _lib.check(rc, "accbpg_svm_get_ax")
+        return out.cpu().numpy()
+
+
 class FrobeniusSymLoss(RSmoothFunction):
     """f(X) = 0.5*||M - X X^T||_F^2 for symmetric nonnegative matrix factorisation (accbpg/functions.py:908-976).
 
@@ -1070,6 +1167,127 @@ class SquaredL2Norm(LegendreFunction):
         yd, was_np = to_dev(y)
         gd, _ = to_dev(g)
         return from_dev(vec_axpby(1.0, yd, -(1 / L), gd), was_np)
+
+
+def polydiv_prox_radius(L, lamda, ds_mean, ds_mean_quad, radius):
+    """t* = min(radius, t^) with t^ >= 0 the root of L*phi'(t) = radius, phi'(t) = lamda^2 t^3 + 2 lamda ds_mean t^2 +
+    ds_mean_quad t: the norm of the minimiser of L*phi(||x||) + <g', x> over ||x|| <= radius when ||g'|| = radius
+    (PolyDiv.prox_map).  phi' is increasing and convex on t >= 0, so Newton from the right end of [0, radius] descends
+    monotonically to the root; an iterate that leaves the bracket is replaced by its midpoint."""
+    a3, a2, a1 = float(lamda) ** 2, 2.0 * float(lamda) * float(ds_mean), float(ds_mean_quad)
+    L, radius = float(L), float(radius)
+
+    def resid(t):
+        return L * (((a3 * t + a2) * t + a1) * t) - radius
+
+    if not resid(radius) > 0.0:                     # t^ >= radius (or a NaN coefficient): the ball's boundary
+        return radius
+    lo, hi, t = 0.0, radius, radius                 # resid(lo) < 0 < resid(hi)
+    for _ in range(200):
+        r = resid(t)
+        if r > 0.0:
+            hi = t
+        elif r < 0.0:
+            lo = t
+        else:
+            return t
+        slope = L * ((3.0 * a3 * t + 2.0 * a2) * t + a1)
+        nxt = t - r / slope if slope > 0.0 else 0.5 * (lo + hi)
+        if not lo < nxt < hi:
+            nxt = 0.5 * (lo + hi)
+        if nxt == t or hi - lo <= 0.0:
+            return t
+        if abs(nxt - t) <= 1e-17 * abs(t):
+            return nxt
+        t = nxt
+    return t
+
+
+class PolyDiv(LegendreFunction):
+    """h(x) = lamda^2/4 ||x||^4 + 2 lamda DS_mean/3 ||x||^3 + DS_mean_quad/2 ||x||^2 on the ball ||x|| <= radius
+    (accbpg/functions.py:838-905; arXiv 1710.04718 (27)), DS_mean and DS_mean_quad the mean row norm of the dataset and
+    the mean of its square, computed on the host once.
+
+    The norms come from device sums; the scalar formulas run on the host in float64 as the reference writes them.
+    ``gradient`` keeps the reference's factor lamda**4*||x||**2 + 2*lamda*DS_mean + DS_mean_quad, which is not the
+    derivative of h, and ``divergence`` is built on it, as in the reference.  ``prox_map`` returns the exact minimiser
+    of the problem the reference hands to a conic solver: with g' = g/||g||*radius it is x = -t* g/||g||,
+    t* = polydiv_prox_radius(...)."""
+
+    def __init__(self, DS, lamda=0, radius=1):
+        self.lamda = lamda
+        self.radius = radius
+        self.DS = DS
+        ds = DS.detach().cpu().numpy() if isinstance(DS, torch.Tensor) else DS
+        self.DS_mean = np.mean(np.linalg.norm(ds, axis=1))
+        self.DS_mean_quad = np.mean(np.linalg.norm(ds, axis=1) ** 2)
+
+    def _h_of_norm(self, norm):
+        norm4 = 1 / 4 * norm ** 4
+        norm3 = 1 / 3 * norm ** 3
+        norm2 = 1 / 2 * norm ** 2
+        return self.lamda ** 2 * norm4 + 2 * self.lamda * self.DS_mean * norm3 + self.DS_mean_quad * norm2
+
+    def _grad_factor(self, sq):
+        """the scalar in front of x in gradient(x), from ||x||^2"""
+        return self.lamda ** 4 * np.sqrt(np.float64(sq)) ** 2 + 2 * self.lamda * self.DS_mean + self.DS_mean_quad
+
+    def __call__(self, x):
+        return self.h(x)
+
+    def h(self, x):
+        xd, _ = to_dev(x)
+        return self._h_of_norm(np.sqrt(np.float64(vec_dot(xd, xd))))
+
+    def extra_Psi(self, x):
+        return 0
+
+    def gradient(self, x):
+        xd, was_np = to_dev(x)
+        return from_dev(vec_axpby(self._grad_factor(vec_dot(xd, xd)), xd, 0.0, xd), was_np)
+
+    def _divergence_of(self, nx2, ny2, ydiff):
+        """h(x) - h(y) - <gradient(y), x - y> from ||x||^2, ||y||^2 and <y, x - y>"""
+        return self._h_of_norm(np.sqrt(np.float64(nx2))) - self._h_of_norm(np.sqrt(np.float64(ny2))) \
+            - self._grad_factor(ny2) * ydiff
+
+    def divergence(self, x, y):
+        assert x.shape == y.shape, "PolyDivBall: x and y not same shape."
+        xd, _ = to_dev(x)
+        yd, _ = to_dev(y)
+        o = quartic_ls_terms(None, xd, yd)
+        return self._divergence_of(o[1], o[2], o[3])
+
+    def ls_terms(self, g, x, y, z=None, z1=None):
+        """(<g,x-y>, D(x,y), D(z,z1)) in one launch and one readback."""
+        o = quartic_ls_terms(g, x, y, z, z1)
+        dzz = self._divergence_of(o[4], o[5], o[6]) if z is not None else 0.0
+        return np.float64(o[0]), self._divergence_of(o[1], o[2], o[3]), dzz
+
+    def _prox_radius(self, L):
+        return polydiv_prox_radius(L, self.lamda, self.DS_mean, self.DS_mean_quad, self.radius)
+
+    def prox_map(self, g, L):
+        gd, was_np = to_dev(g)
+        g_norm = np.sqrt(np.float64(vec_dot(gd, gd)))
+        if g_norm == 0.0:
+            g_norm = 1e-8                                                      # functions.py:873-874
+        return from_dev(vec_axpby(-(self._prox_radius(L) / g_norm), gd, 0.0, gd), was_np)
+
+    def div_prox_map(self, y, g, L):
+        """prox_map(g - L*gradient(y), L): out = c_y*y - g/L = -(g - L*c_y*y)/L and its norm from one launch, then
+        x = t* out/||out||."""
+        yd, was_np = to_dev(y)
+        gd, _ = to_dev(g)
+        c = self._grad_factor(vec_dot(yd, yd))
+        out = torch.empty_like(yd)
+        ssq = C.c_double(0.0)
+        _call("accbpg_quartic_prox_stage", yd, _ptr(yd), _ptr(gd), float(c), float(1 / L), 0, np.inf, yd.numel(),
+              _ptr(out), C.byref(ssq), _WS)
+        norm = np.sqrt(np.float64(ssq.value))
+        if norm == 0.0:
+            norm = 1e-8
+        return from_dev(vec_axpby(self._prox_radius(L) / norm, out, 0.0, out), was_np)
 
 
 # ------------------------------------------------------------------ vector helpers for the solver loops

@@ -108,3 +108,33 @@ def get_random_vector(size, range=1):
     vec = range * np.random.random_sample(size=size)
     assert vec.min() > 0
     return vec
+
+
+def generate_dataset_for_svm(m, n):
+    """m rows of 100*N(0,1) entries from a fresh np.random.default_rng() (one standard_normal(n) call per row), label
+    +1 where fewer than 0.53*n entries of the row are positive and -1 otherwise (accbpg/utils.py:161-192).  Returns
+    (data, labels); the generator is unseeded, as in the reference."""
+    data = []
+    labels = []
+    rng = np.random.default_rng()
+    variance = 100
+    for _ in range(m):
+        row = rng.standard_normal(n) * variance
+        labels.append(1 if (row > 0).sum() < n * 0.53 else -1)
+        data.append(row)
+    return np.array(data), np.array(labels)
+
+
+def random_point_in_l2_ball(center, radius, spread_btm=0.1, spread_up=0.99, pos_dir=False):
+    """center + rho*d with d = np.random.randn(n) normalised (made entrywise nonnegative when pos_dir) and rho =
+    np.random.uniform(radius*spread_btm, radius*spread_up), in this order of draws from the global generator
+    (accbpg/utils.py:195-212)."""
+    ndim = len(center)
+    direction = np.random.randn(ndim)
+    direction /= np.linalg.norm(direction)
+    if pos_dir:
+        direction = np.sign(direction) * direction
+    rho = np.random.uniform(radius * spread_btm, radius * spread_up)
+    point = center + rho * direction
+    assert np.linalg.norm(point - center) - radius <= 1e-15
+    return point

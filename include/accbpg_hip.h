@@ -548,6 +548,31 @@ int accbpg_kldiv_func_grad(accbpg_kldiv* h, const double* x_dev, int flag, doubl
 /* out_dev <- Ax of the last func_grad (length m). */
 int accbpg_kldiv_get_ax(accbpg_kldiv* h, double* out_dev);
 
+/* ---- Soft-margin SVM with the hinge loss (accbpg/functions.py:161-194) ------------------------------------ */
+
+typedef struct accbpg_svm accbpg_svm;
+
+/* f(x) = mean_i max(0, 1 - y_i (A x)_i) + (lamda/2) <x,x>: replaces SVM_fun.__init__ (accbpg/functions.py:162-165).
+ * Same layout and ownership rules as accbpg_poisson_create: A row-major m x n with leading dimension lda >= n (any
+ * base alignment), y length m as doubles (the labels, +-1 or anything else); both owned by the caller.  lamda is an
+ * argument of every evaluation.  A failed allocation leaves nothing of the handle behind. */
+int accbpg_svm_create(const double* A_dev, int64_t m, int64_t n, int64_t lda, const double* y_dev, void* stream,
+                      accbpg_svm** out);
+int accbpg_svm_destroy(accbpg_svm* h);
+int accbpg_svm_set_stream(accbpg_svm* h, void* stream);
+
+/* SVM_fun.func_grad (accbpg/functions.py:183-194).  flag 0 -> f_host[0..1] = { sum_i max(0, 1 - y_i (Ax)_i), <x,x> },
+ * one pass over A and no gradient work; the caller forms F = f_host[0]/m + lamda/2*f_host[1], the reference's
+ * operation order, and <x,x> has the bits of accbpg_vec_dot(x, x).  flag 1 -> g_dev = lamda*x - A^T r / m with
+ * r_i = (y_i (Ax)_i < 1) ? y_i : 0, nothing waits for the device; flag 2 -> both.  flag 3 -> g_dev = A^T r / m alone
+ * (subgradient_loss, :179-181), no wait.  A NaN margin keeps its NaN in the sum and counts as "not < 1" in r; every
+ * row enters A^T r, so 0*NaN propagates as in NumPy.  g_dev must not be x_dev.  Synchronises the stream when a value
+ * is returned. */
+int accbpg_svm_func_grad(accbpg_svm* h, const double* x_dev, double lamda, int flag, double* f_host, double* g_dev);
+
+/* out_dev <- A x of the last evaluation (length m), the margins before the labels. */
+int accbpg_svm_get_ax(accbpg_svm* h, double* out_dev);
+
 /* Shannon-entropy prox maps.  kind 0: ShannonEntropy, y_dev == NULL -> exp(-g/L - 1) (accbpg/functions.py:423-429),
  * y_dev != NULL -> y*exp(-g/L) (:431-438, asserts y >= 0); kind 1: ShannonEntropyL1, the same with lamda + g
  * (:456-466); kind 2: ShannonEntropySimplex, the kind-0 result divided by its sum (:475-490, the div form asserts

@@ -964,6 +964,49 @@ class _FWDivState(_FWState):
         """(trial, f(trial) or None) of the capped step a == 1 from the current x."""
         return _capped_trial(self.obj, self.x_dev(), rec.i, self.radius, valued)
 
+    # ---- what the device-decided solvers need on top (DESIGN.md 6h) ----
+    _snap = None
+    _div_steps = None
+
+    def snapshot(self):
+        """Keep (x, w, H) as they stand, in buffers of this object (accbpg_fw_get_state: synchronises)."""
+        if self._snap is None:
+            dev = self.obj.device
+            self._snap = (torch.empty(self.n, dtype=torch.float64, device=dev),
+                          torch.empty(self.n, dtype=torch.float64, device=dev),
+                          torch.empty(self.m, self.m, dtype=torch.float64, device=dev))
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_get_state(self.h, *[_ptr(t) for t in self._snap])
+        _lib.check(rc, "accbpg_fw_get_state")
+
+    def restore(self):
+        """Back to the last ``snapshot`` (accbpg_fw_set_state: no probe is pending afterwards)."""
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_set_state(self.h, *[_ptr(t) for t in self._snap])
+        _lib.check(rc, "accbpg_fw_set_state")
+
+    def run_div(self, mode, L, gamma, ls_ratio, epsilon, k0, F_prev, nsteps):
+        """``nsteps`` iterations predicted on the device behind one synchronisation (accbpg_fw_div_run) from the book as
+        it stands: the records of the iterations that ran.  A record whose pivot lies outside [0, n) is returned, not
+        raised: the replay reaches it in its turn and calls ``bad_div_pivot``."""
+        if self._div_steps is None:
+            self._div_steps = (_lib.FwDivStep * _lib.FW_RUN_MAX)()
+        prm = _lib.FwDivParams(int(mode), 0, int(k0), float(L), float(gamma), float(ls_ratio), float(epsilon),
+                               float(self.book.ld), float(self.book.q), float(F_prev))
+        nrun = C.c_int(0)
+        with torch.cuda.device(self.obj.device):
+            rc = self.lib.accbpg_fw_div_run(self.h, _LMO_FILL, self.radius, C.byref(prm), int(nsteps), self._div_steps,
+                                            C.byref(nrun))
+        recs = [_lib.FwDivStep.from_buffer_copy(self._div_steps[j]) for j in range(nrun.value)]     # (copies: a replay keeps the last probe)
+        if rc and not (rc == _lib.ERR_ARG and any(not 0 <= r.probe.i < self.n for r in recs)):
+            _lib.check(rc, "accbpg_fw_div_run")
+        return recs
+
+    def bad_div_pivot(self):
+        """The exception of the sequential solver's probe with such a pivot (the library's last error is still the
+        message accbpg_fw_div_run left)."""
+        _lib.check(_lib.ERR_ARG, "accbpg_fw_div_probe_step")
+
 
 def D_opt_FW_div_step(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2,
                       verbose=True, verbskip=1, radius=1, refresh=REFRESH_DEFAULT):
@@ -1032,6 +1075,228 @@ def D_opt_FW_descent_step_steps(f, x0, maxitrs, epsilon=1e-14, verbose=True, ver
         if stop:
             break
         yield k
+
+    return run.result(st.x())
+
+
+# ---- the Bregman-step solvers with the line search predicted on the device ----------------------------
+# The generators reach the device through a state object alone -- book, refresh_if_due, probe_div, apply_step, capped,
+# reinit, snapshot, restore, run_div, bad_div_pivot, x -- (tests/test_fw_div_device_cpu.py drives them with a NumPy
+# stand-in) and take every decision in the _DivStepRun / _DescentRun of the sequential solvers: the device predicts a
+# chunk (accbpg_fw_div_run), the host replays its records and owns the result.
+class _Capped(Exception):
+    """The replay of a record met the capped step: that iteration belongs to the sequential path."""
+
+
+def _replay_capped(rec):
+    raise _Capped()
+
+
+def _same_bits(mine, theirs, fmt):
+    return all(struct.pack(f, a) == struct.pack(f, b) or (a != a and b != b) for f, a, b in zip(fmt, mine, theirs))
+
+
+def _div_chunk(k, maxitrs, sync_every, book, lead=0):
+    """Iterations of the chunk that starts at k: ``sync_every`` (None: SYNC_EVERY_DEFAULT), cut at maxitrs, at what one
+    call holds and so that no refresh falls inside it (``lead``: steps the chunk applies before its first probe)."""
+    S = SYNC_EVERY_DEFAULT if sync_every is None else int(sync_every)
+    if S < 1:
+        raise ValueError("sync_every must be at least 1")
+    S = min(S, maxitrs - k, _lib.FW_RUN_MAX)
+    if book.refresh:
+        S = min(S, book.refresh - book.since - lead)
+    return S
+
+
+def _device_stats(stats):
+    stats = {} if stats is None else stats
+    for name in ("chunks", "rollbacks", "handed_back"):
+        stats.setdefault(name, 0)
+    return stats
+
+
+def D_opt_FW_div_step_device(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2, verbose=True,
+                             verbskip=1, radius=1, refresh=REFRESH_DEFAULT, sync_every=SYNC_EVERY_DEFAULT, stats=None):
+    """D_opt_FW_div_step with ``sync_every`` iterations per host round trip.  The device predicts the line search of
+    every iteration of a chunk with its own log and pow (accbpg_fw_div_run); the host replays the chunk's records
+    through ``_DivStepRun.decide`` -- its ld, q, F and Ls are the ones returned -- and compares its (p, a, hcoef, hdiv),
+    L and stop decision with the device's bit for bit.  Where they differ (a decision within a rounding of a tie: not an
+    error) the state of the chunk's start is restored and the iterations up to that one are redone step by step with
+    the host's decisions (``stats["rollbacks"]``); an iteration the device hands back -- the capped step, a failed
+    check -- runs on the sequential path (``stats["handed_back"]``); where only the HOST's replay of a record meets the
+    cap, the chunk is rolled back and that iteration runs on the sequential path, counted under ``rollbacks`` alone.  A
+    chunk never spans a refresh.  Returns
+    D_opt_FW_div_step's tuple; x, F, Ls and the iteration count are bit-identical to D_opt_FW_div_step's for every
+    argument set; T[k] is the arrival time of the chunk, table rows are printed per chunk.
+
+    gamma == 2 (every driver of the reference): ``** 1.0`` is exact, only log and a ** 2 stand between the device and
+    the host, and rollbacks are near-ties.  Other gamma: the step length itself goes through pow, rollbacks may be
+    frequent and the form may not pay; the result is the sequential solver's all the same."""
+    return _drain(D_opt_FW_div_step_device_steps(f, L, x0, maxitrs, gamma, epsilon, linesearch, ls_ratio, verbose,
+                                                 verbskip, radius, refresh, sync_every, stats))
+
+
+def D_opt_FW_div_step_device_steps(f, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2, verbose=True,
+                                   verbskip=1, radius=1, refresh=REFRESH_DEFAULT, sync_every=SYNC_EVERY_DEFAULT,
+                                   stats=None):
+    """Generator form: yields the last k of each chunk, returns D_opt_FW_div_step_device's tuple."""
+    _check_options(L, epsilon, ls_ratio)
+    if verbose:
+        print("\nFW adaptive algorithm")
+        print("     k      F(x)         Lk       time")
+    t_start = time.time()
+    st = _FWDivState(f, x0, radius, refresh)
+    run = _DivStepRun(st.book, L, maxitrs, gamma, epsilon, linesearch, ls_ratio)
+    return _div_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, _device_stats(stats), t_start)
+
+
+def _div_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats, t_start):
+    """D_opt_FW_div_step_device_steps on a state object and the sequential solver's ``_DivStepRun``."""
+    mode = _lib.FW_DIV_LINESEARCH if run.linesearch else _lib.FW_DIV_FIXED_L
+
+    def sequential(k):                                          # one iteration of D_opt_FW_div_step
+        st.refresh_if_due()
+        rec = st.probe_div()
+        step, trial, stop = run.decide(k, rec, time.time() - t_start, lambda r: st.capped(r, run.linesearch))
+        if trial is None:
+            st.apply_step(*step)
+        else:
+            st.reinit(trial)
+        return stop
+
+    def row(k):
+        if verbose and k % verbskip == 0:
+            print(f"{k:6d}  {run.F[k]:10.3e}  {run.Ls[k]:10.3e}  {run.T[k]:6.1f}")
+
+    k = 0
+    stop = False
+    while k < maxitrs and not stop:
+        st.refresh_if_due()
+        nsteps = _div_chunk(k, maxitrs, sync_every, st.book)
+        st.snapshot()
+        recs = st.run_div(mode, run.L, run.gamma, run.ls_ratio, run.epsilon, k, run.F[k - 1] if k else 0.0, nsteps)
+        now = time.time() - t_start
+        stats["chunks"] += 1
+        mine = []                                               # the host's steps of this chunk
+        for r in recs:
+            if r.status == _lib.FW_DIV_HANDED_BACK:             # nothing applied: the state is that of iteration k
+                stats["handed_back"] += 1
+                if r.reason == _lib.FW_DIV_HB_PIVOT:
+                    st.bad_div_pivot()
+                stop = sequential(k)
+            else:
+                try:
+                    step, _, stop = run.decide(k, r.probe, now, _replay_capped)
+                except _Capped:
+                    step = None
+                if step is not None and stop == (r.status == _lib.FW_DIV_STOPPED) and _same_bits(
+                        step + (run.Ls[k],), (r.probe.i, r.a, r.hcoef, r.hdiv, r.L), "qdddd"):
+                    mine.append(step)
+                    row(k)
+                    k += 1
+                    if stop:
+                        break
+                    continue
+                stats["rollbacks"] += 1                         # redo the chunk up to k with the host's decisions
+                st.restore()
+                for s in mine:
+                    st.probe_div()
+                    st.apply_step(*s)
+                if step is None:
+                    stop = sequential(k)
+                else:
+                    st.probe_div()
+                    st.apply_step(*step)
+            row(k)
+            k += 1
+            break
+        if not stop:
+            yield k - 1
+
+    return run.result(st.x())
+
+
+def D_opt_FW_descent_step_device(f, x0, maxitrs, epsilon=1e-14, verbose=True, verbskip=1, radius=1,
+                                 refresh=REFRESH_DEFAULT, sync_every=SYNC_EVERY_DEFAULT, stats=None):
+    """D_opt_FW_descent_step with ``sync_every`` iterations per host round trip, by the contract of
+    ``D_opt_FW_div_step_device``: the device applies the classical steps 2 / (k + 2) of a chunk and predicts the stop
+    test, the host replays the records through ``_DescentRun``.  Returns D_opt_FW_descent_step's tuple; x, F, G and the
+    iteration count are bit-identical to D_opt_FW_descent_step's."""
+    return _drain(D_opt_FW_descent_step_device_steps(f, x0, maxitrs, epsilon, verbose, verbskip, radius, refresh,
+                                                     sync_every, stats))
+
+
+def D_opt_FW_descent_step_device_steps(f, x0, maxitrs, epsilon=1e-14, verbose=True, verbskip=1, radius=1,
+                                       refresh=REFRESH_DEFAULT, sync_every=SYNC_EVERY_DEFAULT, stats=None):
+    """Generator form: yields the last k of each chunk, returns D_opt_FW_descent_step_device's tuple."""
+    if verbose:
+        print("\nFW descent step size algorithm")
+        print("     k      F(x)         alpha_k       time")
+    t_start = time.time()
+    st = _FWDivState(f, x0, radius, refresh)
+    run = _DescentRun(st.book, maxitrs, epsilon)
+    return _descent_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, _device_stats(stats), t_start)
+
+
+def _descent_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats, t_start):
+    """D_opt_FW_descent_step_device_steps on a state object and the sequential solver's ``_DescentRun``."""
+    def sequential(k):                                          # one iteration of D_opt_FW_descent_step
+        st.apply_step(*run.step(k))
+        st.refresh_if_due()
+        return run.probed(k, st.probe_div(), time.time() - t_start)
+
+    def row(k):
+        if verbose and (k % verbskip == 0 or k == 1):
+            print(f"{k:6d}  {run.F[k]:10.3e}  {run.alpha:10.3e}  {run.T[k]:6.1f}")
+
+    run.first(st.probe_div(), time.time() - t_start)
+    k = 1
+    stop = False
+    while k < maxitrs and not stop:
+        nsteps = _div_chunk(k, maxitrs, sync_every, st.book, lead=1)
+        if nsteps < 1:                                          # the refresh falls between this step and its probe
+            stop = sequential(k)
+            row(k)
+            k += 1
+            if not stop:
+                yield k - 1
+            continue
+        st.snapshot()
+        recs = st.run_div(_lib.FW_DIV_CLASSICAL, 0.0, 0.0, 0.0, run.epsilon, k, run.F[k - 1], nsteps)
+        now = time.time() - t_start
+        stats["chunks"] += 1
+        mine = []
+        for r in recs:
+            if r.status == _lib.FW_DIV_HANDED_BACK:             # nothing applied: the probe before step k is pending
+                stats["handed_back"] += 1
+                stop = sequential(k)
+            else:
+                step = run.step(k)
+                mine.append(step)
+                agree = _same_bits(step[1:], (r.a, r.hcoef, r.hdiv), "ddd")
+                if agree:                                       # (else the record's probe saw another state)
+                    if not 0 <= r.probe.i < st.n:
+                        st.bad_div_pivot()
+                    stop = run.probed(k, r.probe, now)
+                    agree = stop == (r.status == _lib.FW_DIV_STOPPED)
+                if agree:
+                    row(k)
+                    k += 1
+                    if stop:
+                        break
+                    continue
+                stats["rollbacks"] += 1                         # redo the chunk up to k with the host's decisions
+                st.restore()
+                rec = st.probe_div()
+                for s in mine:
+                    st.apply_step(*s)
+                    rec = st.probe_div()
+                stop = run.probed(k, rec, time.time() - t_start)
+            row(k)
+            k += 1
+            break
+        if not stop:
+            yield k - 1
 
     return run.result(st.x())
 

@@ -38,6 +38,21 @@ class FwStep(C.Structure):
                 ("hcoef", C.c_double), ("hdiv", C.c_double), ("kind", C.c_int32), ("status", C.c_int32)]
 
 
+class FwDivParams(C.Structure):
+    """accbpg_fw_div_params: the run parameters and the host's exact book at the start of an accbpg_fw_div_run call."""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("k0", C.c_int64), ("L", C.c_double),
+                ("gamma", C.c_double), ("ls_ratio", C.c_double), ("epsilon", C.c_double), ("ld", C.c_double),
+                ("q", C.c_double), ("F_prev", C.c_double)]
+
+
+class FwDivStep(C.Structure):
+    """One record of accbpg_fw_div_run (accbpg_fw_div_step): the probe record, the step the device predicted with its
+    own book behind it, and what became of it."""
+    _fields_ = [("probe", FwDivProbe), ("L", C.c_double), ("a", C.c_double), ("hcoef", C.c_double),
+                ("hdiv", C.c_double), ("ld1", C.c_double), ("q1", C.c_double), ("f1", C.c_double),
+                ("trials", C.c_int32), ("status", C.c_int32), ("reason", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TrialOut(C.Structure):
     """accbpg_trial_out: what a clean accbpg_dopt_burg_trial returns."""
     _fields_ = [("fy", C.c_double), ("lin", C.c_double), ("dxy", C.c_double), ("dzz", C.c_double), ("fx", C.c_double),
@@ -47,6 +62,11 @@ class TrialOut(C.Structure):
 TRIAL_REPLAY = 5            # ACCBPG_TRIAL_REPLAY
 FW_RUN_MAX = 1024           # ACCBPG_FW_RUN_MAX
 FW_APPLIED, FW_STOPPED, FW_BAD_PIVOT, FW_NOT_RUN = 0, 1, 2, 3      # accbpg_fw_step.status
+FW_DIV_TRIALS_MAX = 64      # ACCBPG_FW_DIV_TRIALS_MAX
+FW_DIV_LINESEARCH, FW_DIV_FIXED_L, FW_DIV_CLASSICAL = 0, 1, 2      # accbpg_fw_div_params.mode
+FW_DIV_APPLIED, FW_DIV_STOPPED, FW_DIV_HANDED_BACK, FW_DIV_NOT_RUN = 0, 1, 2, 3    # accbpg_fw_div_step.status
+(FW_DIV_HB_NONE, FW_DIV_HB_BUDGET, FW_DIV_HB_L_INF, FW_DIV_HB_SLOPE, FW_DIV_HB_MIN_X, FW_DIV_HB_PIVOT, FW_DIV_HB_CAP,
+ FW_DIV_HB_ARITH) = range(8)                                        # accbpg_fw_div_step.reason
 
 _P = C.c_void_p
 _SIGS = {
@@ -121,6 +141,9 @@ _SIGS = {
     "accbpg_fw_div_apply": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "accbpg_fw_logdet_snapshot": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "accbpg_fw_run": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, C.POINTER(FwStep), C.POINTER(C.c_int)]),
+    "accbpg_fw_div_run": (C.c_int, [_P, C.c_double, C.c_double, C.POINTER(FwDivParams), C.c_int, C.POINTER(FwDivStep),
+                                    C.POINTER(C.c_int)]),
+    "accbpg_fw_set_state": (C.c_int, [_P, _P, _P, _P]),
     "accbpg_dopt_batch_fw_init": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                             C.POINTER(C.c_int)]),
     "accbpg_dopt_batch_fw_probe": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(FwProbe)]),

@@ -118,6 +118,8 @@ extern "C" int accbpg_dopt_destroy(accbpg_dopt* h) {
     if (h->fw_steps_pin) hipHostFree(h->fw_steps_pin);
     acc_free(h->fw_div_ws);
     if (h->fw_div_pin) hipHostFree(h->fw_div_pin);
+    acc_free(h->fw_div_run);
+    if (h->fw_div_steps_pin) hipHostFree(h->fw_div_steps_pin);
     if (h->hpin) hipHostFree(h->hpin);
     if (h->ev_done) hipEventDestroy(h->ev_done);
     for (auto& sl : h->fw_ring) {

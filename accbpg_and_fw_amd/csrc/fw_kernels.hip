@@ -5,6 +5,7 @@
 // passes over the length-n vectors.  Compiled with -ffp-contract=off (NumPy ufunc rounding).
 #include "internal.h"
 #include "reduce.hpp"
+#include "fw_div_decide.hpp"
 
 namespace accbpg {
 
@@ -798,6 +799,150 @@ __global__ __launch_bounds__(FB) void fw_div_xupdate_kernel(double* __restrict__
     fw_div_xupdate_body(x, n, p, a, fill, value);
 }
 
+// ---- the Bregman-step kernels: several iterations per host round trip (accbpg_fw_div_run) ------------------------
+// The "run" forms of the four bodies above on the single handle's grids (Hv, u, the rank-one update and the update of
+// w are the run forms of accbpg_fw_run, which read the FwRun in front of the slot).  Thread 0 of the last stage of the
+// probe -- after sum u^2, which the trial values need -- predicts the decisions of the iteration with the text of
+// fw_div_decide.hpp on the book the slot keeps (ld advanced with the device's own log), writes the step for the update
+// kernels and the record straight into the pinned host array.  The host replays and checks every record: see the header.
+__device__ __forceinline__ int fw_div_run_halted(const FwRun* run) {
+    const volatile int32_t* r = reinterpret_cast<const volatile int32_t*>(run);
+    return r[0] | r[1];                                         // stop | pad
+}
+struct FwDivRunArgs {       // what does not change inside a call
+    int mode;
+    double gamma, ls_ratio, epsilon;
+    int64_t n;
+    int nsteps;
+};
+// the probe record of a slot (or of the pinned one: the same layout) as fw_div_decide.hpp reads it
+struct FwDivRecView {
+    int64_t i;
+    double w_i, x_i, sum_w, sum_w2, slope, div, min_x, sum_u2;
+};
+__device__ __forceinline__ FwDivRecView fw_div_view(const double* rec) {
+    FwDivRecView v;
+    v.i = reinterpret_cast<const int64_t*>(rec)[0];
+    v.w_i = rec[1]; v.x_i = rec[2]; v.sum_w = rec[3]; v.sum_w2 = rec[4]; v.slope = rec[5]; v.div = rec[6];
+    v.min_x = rec[7]; v.sum_u2 = rec[8];
+    return v;
+}
+__device__ __forceinline__ void fw_div_record(accbpg_fw_div_step* __restrict__ out, const FwDivRecView& v,
+                                              const FwdOut& o, double L, int status) {
+    accbpg_fw_div_step st;
+    st.probe.i = v.i; st.probe.w_i = v.w_i; st.probe.x_i = v.x_i; st.probe.sum_w = v.sum_w; st.probe.sum_w2 = v.sum_w2;
+    st.probe.slope = v.slope; st.probe.div = v.div; st.probe.min_x = v.min_x; st.probe.sum_u2 = v.sum_u2;
+    st.L = L; st.a = o.a; st.hcoef = o.hcoef; st.hdiv = o.hdiv; st.ld1 = o.ld1; st.q1 = o.q1; st.f1 = o.f1;
+    st.trials = o.trials; st.status = status; st.reason = o.reason; st.reserved = 0;
+    *out = st;
+}
+__device__ __forceinline__ FwdBook fw_div_book(const FwDivRunSlot* sl, int64_t m, double fill, double value) {
+    FwdBook b;
+    b.ld = sl->ld; b.q = sl->q; b.m = (double)m; b.radius = value; b.fill = fill; b.F_prev = sl->F_prev;
+    return b;
+}
+__device__ __forceinline__ void fw_div_set_stop(FwRun* run, int32_t v) {
+    *reinterpret_cast<volatile int32_t*>(&run->stop) = v;
+}
+// the classical step of iteration k from the probe record `v`: into the slot for the update kernels, or a hand-back
+// into `out` (the record of iteration k; null when the call has no such record)
+__device__ __forceinline__ void fw_div_next_classical(FwDivRunSlot* sl, FwdBook* b, const FwDivRecView& v, int64_t n,
+                                                      int64_t k, FwdOut* o, accbpg_fw_div_step* out) {
+    fw_descent_step(v, (long long)n, b, (long long)k, o);
+    if (o->status == FWD_HANDED_BACK) {
+        fw_div_set_stop(&sl->run, 2);
+        if (out) fw_div_record(out, v, *o, 0.0, FWD_HANDED_BACK);
+        return;
+    }
+    sl->run.p = v.i; sl->run.xscale = o->a; sl->run.xadd = 0.0; sl->run.hcoef = o->hcoef; sl->run.hdiv = o->hdiv;
+    sl->ld = b->ld; sl->q = b->q;
+}
+// one thread: the slot at the start of a call; in the classical mode the step of iteration k0 from the pending probe
+__global__ void fw_div_run_init_kernel(FwDivRunSlot* sl, FwDivRunArgs ra, int64_t m, double fill, double value,
+                                       double L, double ld, double q, double F_prev, int64_t k0,
+                                       const double* __restrict__ pin, accbpg_fw_div_step* __restrict__ out0) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    sl->run.stop = 0; sl->run.pad = 0; sl->run.p = -1;
+    sl->run.xscale = 0.0; sl->run.xadd = 0.0; sl->run.hcoef = 0.0; sl->run.hdiv = 1.0;
+    sl->ld = ld; sl->q = q; sl->F_prev = F_prev; sl->L = L;
+    if (ra.mode == FWD_CLASSICAL) {
+        for (int c = 0; c < 9; ++c) sl->rec[c] = pin[c];
+        FwdBook b = fw_div_book(sl, m, fill, value);
+        FwdOut o;
+        fw_div_next_classical(sl, &b, fw_div_view(sl->rec), ra.n, k0, &o, out0);
+    }
+}
+__global__ __launch_bounds__(FB) void fw_div_probe_partial_run_kernel(const FwRun* run, const ValIdx* __restrict__ part,
+                                                                     int nblk, const double* __restrict__ w,
+                                                                     const double* __restrict__ x, int64_t n,
+                                                                     double fill, double value, double* __restrict__ rec,
+                                                                     ValIdx* __restrict__ mxslot) {
+    if (fw_div_run_halted(run)) return;
+    fw_div_probe_partial_body(part, nblk, w, x, n, fill, value, rec, mxslot);
+}
+// (one workgroup: every thread reads the two words before thread 0 turns "stop after this apply" into stop)
+__global__ __launch_bounds__(FB) void fw_div_probe_final_run_kernel(FwRun* run, const double* __restrict__ rec, int nb,
+                                                                   const ValIdx* __restrict__ mxslot,
+                                                                   const double* __restrict__ x, int64_t n,
+                                                                   const double* __restrict__ V, int64_t ldv, int64_t m,
+                                                                   double* __restrict__ vp, double* __restrict__ scratch) {
+    const int halted = fw_div_run_halted(run);
+    __syncthreads();
+    if (halted) {
+        if (threadIdx.x == 0 && run->stop == 0) fw_div_set_stop(run, 1);
+        return;
+    }
+    fw_div_probe_final_body(rec, nb, mxslot, x, n, V, ldv, m, vp, scratch);
+}
+__global__ __launch_bounds__(FB) void fw_div_usum_run_kernel(const FwRun* __restrict__ run,
+                                                            const double* __restrict__ upart, int nsplit, int64_t n,
+                                                            double* __restrict__ u, double* __restrict__ u2part) {
+    if (run->stop) return;
+    fw_div_usum_body(upart, nsplit, n, u, u2part);
+}
+__global__ __launch_bounds__(FB) void fw_div_u2final_run_kernel(FwDivRunSlot* sl, const double* __restrict__ u2part,
+                                                               int nb, FwDivRunArgs ra, int64_t m, double fill,
+                                                               double value, int64_t k, int j,
+                                                               accbpg_fw_div_step* __restrict__ steps) {
+    if (fw_run_stop(&sl->run)) return;
+    reduce_final_body<FB, 1, false>(u2part, nb, sl->rec + 8);
+    if (threadIdx.x != 0) return;
+    const FwDivRecView v = fw_div_view(sl->rec);                // (doubles 0..7 by the stage before, 8 by this thread)
+    FwdBook b = fw_div_book(sl, m, fill, value);
+    FwdOut o;
+    if (ra.mode != FWD_CLASSICAL) {
+        double L = sl->L;
+        fw_div_decide(v, (long long)ra.n, &b, &L, ra.mode, ra.gamma, ra.ls_ratio, ra.epsilon, (long long)k, &o);
+        if (o.status == FWD_HANDED_BACK) {
+            fw_div_set_stop(&sl->run, 2);
+        } else {
+            sl->run.p = v.i; sl->run.xscale = o.a; sl->run.xadd = 0.0; sl->run.hcoef = o.hcoef; sl->run.hdiv = o.hdiv;
+            sl->ld = b.ld; sl->q = b.q; sl->F_prev = b.F_prev; sl->L = L;
+            if (o.status == FWD_STOPPED) *reinterpret_cast<volatile int32_t*>(&sl->run.pad) = 1;
+        }
+        fw_div_record(steps + j, v, o, o.L, o.status);
+        return;
+    }
+    // classical: this is the probe behind step k, whose scalars the slot still holds
+    o.trials = 0; o.reason = FWD_HB_NONE;
+    o.a = sl->run.xscale; o.hcoef = sl->run.hcoef; o.hdiv = sl->run.hdiv; o.ld1 = sl->ld; o.q1 = sl->q;
+    const bool stop = fw_descent_probed(v, &b, ra.epsilon, &o.f1);
+    sl->F_prev = b.F_prev;
+    fw_div_record(steps + j, v, o, 0.0, stop ? FWD_STOPPED : FWD_APPLIED);
+    if (stop) {
+        fw_div_set_stop(&sl->run, 1);
+        return;
+    }
+    FwdOut o2;
+    fw_div_next_classical(sl, &b, v, ra.n, k + 1, &o2, (j + 1 < ra.nsteps) ? steps + j + 1 : nullptr);
+}
+__global__ __launch_bounds__(FB) void fw_div_xupdate_run_kernel(const FwRun* __restrict__ run, double* __restrict__ x,
+                                                               int64_t n, double fill, double value) {
+    const FwRun r = *run;
+    if (r.stop) return;
+    fw_div_xupdate_body(x, n, r.p, r.xscale, fill, value);
+}
+
 // The active instances of a batch in lock-step (accbpg_dopt_batch_fw_div_probe / _fw_div_apply), by the convention of
 // the step kernels above: blockIdx.y is the position among the active instances, blockIdx.x and gridDim.x are the single
 // launch's, so the fixed tree adds every instance's entries in the single handle's order.  The state comes from the
@@ -1356,6 +1501,134 @@ extern "C" int accbpg_fw_div_apply(accbpg_dopt* h, int64_t p, double a, double f
     fw_wupdate_probe_kernel<<<g.wb, FB, 0, s>>>(t.w, n, h->fw_div_ws, 1, hcoef, hdiv, t.x, 0, fw_part_of(t, m));
     h->fw_part_nblk = (int)g.wb;
     ACC_HIP(hipGetLastError());
+    return ACCBPG_OK;
+}
+
+// ---- several Bregman-step iterations per synchronisation (accbpg_fw_div_run) ------------------------------------
+static int fw_div_run_alloc(accbpg_dopt* h) {
+    if (!h->fw_div_steps_pin) {
+        ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fw_div_steps_pin),
+                              sizeof(accbpg_fw_div_step) * ACCBPG_FW_RUN_MAX, hipHostMallocDefault));
+        ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fw_div_steps_dev), h->fw_div_steps_pin, 0));
+    }
+    if (!h->fw_div_run)
+        ACC_HIP(acc_malloc(reinterpret_cast<void**>(&h->fw_div_run), sizeof(FwDivRunSlot), "fw_div_run"));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_fw_div_run(accbpg_dopt* h, double fill, double value, const accbpg_fw_div_params* prm, int nsteps,
+                                 accbpg_fw_div_step* steps_host, int* nrun_host) {
+    if (!h || !h->fw_ready || !prm || !steps_host || !nrun_host || nsteps < 1 || nsteps > ACCBPG_FW_RUN_MAX ||
+        prm->mode < FWD_LINESEARCH || prm->mode > FWD_CLASSICAL)
+        return ACCBPG_ERR_ARG;
+    const bool classical = prm->mode == FWD_CLASSICAL;
+    if (classical && (h->fw_div_i < 0 || h->fw_part_nblk != 0 || prm->k0 < 1)) {
+        set_last_error("accbpg_fw_div_run: the classical step needs the probe of accbpg_fw_div_probe_step pending on this "
+                       "state, and k0 >= 1");
+        return ACCBPG_ERR_ARG;
+    }
+    ACC_TRY(fw_div_alloc(h));
+    ACC_TRY(fw_div_run_alloc(h));
+    const FwGrids g = fw_grids(h->m, h->n, h->num_cu);
+    const FwInst& t = h->fw;
+    const int64_t m = h->m, n = h->n;
+    hipStream_t s = h->stream;
+    accbpg_fw_div_step* pinned = h->fw_div_steps_pin;           // (nothing of an earlier call is in flight: it synchronised)
+    for (int k = 0; k < nsteps; ++k) {
+        pinned[k] = accbpg_fw_div_step{};
+        pinned[k].probe.i = -1;
+        pinned[k].status = FWD_NOT_RUN;
+    }
+    FwDivRunSlot* sl = h->fw_div_run;
+    FwRun* run = &sl->run;
+    accbpg_fw_div_step* steps = h->fw_div_steps_dev;
+    const FwDivRunArgs ra{prm->mode, prm->gamma, prm->ls_ratio, prm->epsilon, n, nsteps};
+    ValIdx* part = fw_part_of(t, m);
+    double* vp = fw_vp_of(t, m);
+    const int nb = red_blocks(n, FW_DIV_CAP);
+    double *rec = fw_div_rec_of(h->fw_div_ws, n), *u2part = fw_div_u2part_of(h->fw_div_ws, n), *u = h->fw_div_ws;
+    ValIdx* mxslot = fw_div_mxslot_of(h->fw_div_ws, n);
+    const int64_t pending = h->fw_div_i;
+    int nblk = 0;
+    if (!classical) {
+        nblk = fw_part_waiting(h, 0);
+        if (!nblk) {                                            // (else stage 1 came with the last update of w)
+            nblk = (int)g.nblk;
+            fw_probe_partial_kernel<<<g.nblk, FB, 0, s>>>(t.w, t.x, n, 0, part);
+        }
+    }
+    h->fw_part_nblk = 0;                                        // (no claim survives an error return below)
+    h->fw_part_away = false;
+    h->fw_div_i = -1;
+    fw_div_run_init_kernel<<<1, 1, 0, s>>>(sl, ra, m, fill, value, prm->L, prm->ld, prm->q, prm->F_prev, prm->k0,
+                                           h->fw_div_pin_dev, steps);
+    for (int j = 0; j < nsteps; ++j) {
+        if (classical) {                                        // apply step k, then the probe behind it
+            fw_div_xupdate_run_kernel<<<g.gb, FB, 0, s>>>(run, t.x, n, fill, value);
+            fw_rank1_run_kernel<<<g.rb, FB, 0, s>>>(run, t.H, m, t.hv, vp, t.q);
+            fw_wupdate_probe_run_kernel<<<g.wb, FB, 0, s>>>(run, t.w, n, u, 1, t.x, 0, part);
+            nblk = (int)g.wb;
+        }
+        fw_div_probe_partial_run_kernel<<<nb, FB, 0, s>>>(run, part, nblk, t.w, t.x, n, fill, value, rec, mxslot);
+        fw_div_probe_final_run_kernel<<<1, FB, 0, s>>>(run, rec, nb, mxslot, t.x, n, t.V, h->ldv, m, vp, sl->rec);
+        fw_gemv_h_run_kernel<<<g.hb, FB, 0, s>>>(run, t.H, m, vp, t.hv);
+        fw_vgemv_partial_run_kernel<<<dim3(g.vgx, (unsigned)g.ns), FB, 0, s>>>(run, t.V, h->ldv, m, n, t.hv, g.ns, t.vws, h->vec_ok);
+        fw_div_usum_run_kernel<<<nb, FB, 0, s>>>(run, t.vws, g.ns, n, u, u2part);
+        fw_div_u2final_run_kernel<<<1, FB, 0, s>>>(sl, u2part, nb, ra, m, fill, value, prm->k0 + j, j, steps);
+        if (!classical) {                                       // the step the record describes
+            fw_div_xupdate_run_kernel<<<g.gb, FB, 0, s>>>(run, t.x, n, fill, value);
+            fw_rank1_run_kernel<<<g.rb, FB, 0, s>>>(run, t.H, m, t.hv, vp, t.q);
+            fw_wupdate_probe_run_kernel<<<g.wb, FB, 0, s>>>(run, t.w, n, u, 1, t.x, 0, part);
+            nblk = (int)g.wb;
+        }
+    }
+    ACC_HIP(hipGetLastError());
+    ACC_HIP(hipStreamSynchronize(s));
+    // copy the row out; leave on the handle what the step-by-step entries would have left where the call ended
+    int nrun = 0, last = -1;                                    // last: the last record behind which the state moved
+    const accbpg_fw_div_step* bad = nullptr;
+    for (int k = 0; k < nsteps; ++k) {
+        steps_host[k] = pinned[k];
+        if (pinned[k].status == FWD_NOT_RUN) continue;
+        ++nrun;
+        const bool in_range = pinned[k].probe.i >= 0 && pinned[k].probe.i < n;
+        if (!in_range && !bad) bad = pinned + k;
+        if (pinned[k].status != FWD_HANDED_BACK || !classical) last = k;
+    }
+    *nrun_host = nrun;
+    if (last < 0) {                                             // (classical: the first step was handed back)
+        h->fw_div_i = pending;
+    } else {
+        const accbpg_fw_div_step& r = pinned[last];
+        const bool ends_on_probe = classical || r.status == FWD_HANDED_BACK;
+        if (ends_on_probe) {
+            const bool in_range = r.probe.i >= 0 && r.probe.i < n;
+            h->fw_div_i = in_range ? r.probe.i : -1;
+            double* pin = h->fw_div_pin;                        // the pending probe's record, as _probe_step leaves it
+            reinterpret_cast<int64_t*>(pin)[0] = r.probe.i;
+            pin[1] = r.probe.w_i; pin[2] = r.probe.x_i; pin[3] = r.probe.sum_w; pin[4] = r.probe.sum_w2;
+            pin[5] = r.probe.slope; pin[6] = r.probe.div; pin[7] = r.probe.min_x; pin[8] = r.probe.sum_u2;
+        } else {
+            h->fw_part_nblk = (int)g.wb;                        // the stage-1 records of the last update of w
+        }
+    }
+    if (bad) {
+        set_last_error("accbpg_fw_div_probe_step: pivot index %lld outside [0, n)", (long long)bad->probe.i);
+        return ACCBPG_ERR_ARG;
+    }
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_fw_set_state(accbpg_dopt* h, const double* x_dev, const double* w_dev, const double* H_dev) {
+    if (!h || !h->fw_ready || !x_dev || !w_dev || !H_dev) {
+        set_last_error("accbpg_fw_set_state: no Frank-Wolfe state (call accbpg_fw_init) or a null argument");
+        return ACCBPG_ERR_ARG;
+    }
+    h->fw_part_nblk = 0;
+    h->fw_div_i = -1;
+    ACC_TRY(device_copy(h->fw_x, x_dev, (size_t)h->n, h->stream));
+    ACC_TRY(device_copy(h->fw_w, w_dev, (size_t)h->n, h->stream));
+    ACC_TRY(device_copy(h->fw_H, H_dev, (size_t)h->m * h->m, h->stream));
     return ACCBPG_OK;
 }
 

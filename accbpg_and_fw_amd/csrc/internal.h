@@ -180,6 +180,16 @@ struct FwRunSlot {
     double rec[16];
 };
 
+// One handle's Bregman-step run (accbpg_fw_div_run).  run is what the reused "run" kernels read: p, hcoef, hdiv as there,
+// xscale carries the step length a; run.stop != 0: every later kernel of the call returns at once; run.pad != 0: the stop
+// test held with an applied step -- the kernels of that apply still run, the final stage of the next probe turns it into
+// stop.  book and L are the predictor's (fw_div_decide.hpp), rec the scratch probe record laid out as the pinned one.
+struct FwDivRunSlot {
+    FwRun run;
+    double ld, q, F_prev, L;
+    double rec[16];
+};
+
 struct CholInst {                                  // one factorisation (one entry per instance of a batched launch)
     const double* src;      // matrix to factor (lower triangle significant), leading dimension ld
     double* L;              // off-diagonal tiles of the factor (may be src: in place)
@@ -285,6 +295,11 @@ struct accbpg_dopt {
     double* fw_div_pin = nullptr;
     double* fw_div_pin_dev = nullptr;           // ... as the device addresses it
     int64_t fw_div_i = -1;                      // index of the last probe while its Hv and u are current, else -1
+    // accbpg_fw_div_run: the predictor's slot on the device, the records of a call in pinned host memory (allocated by
+    // the first call, freed with the handle)
+    accbpg::FwDivRunSlot* fw_div_run = nullptr;
+    accbpg_fw_div_step* fw_div_steps_pin = nullptr;     // ACCBPG_FW_RUN_MAX records
+    accbpg_fw_div_step* fw_div_steps_dev = nullptr;     // ... as the device addresses them
 
     bool use_glds = true;       // direct-to-LDS staging for interior big tiles (debug switch)
     int kern_variant = 0;       // schedule of the direct-to-LDS Gram / gradient kernels (development switch)

@@ -430,6 +430,56 @@ typedef struct accbpg_fw_step {
 } accbpg_fw_step;
 int accbpg_fw_run(accbpg_dopt* h, int away, double eps, int nsteps, accbpg_fw_step* steps_host, int* nrun_host);
 
+/* Several iterations of the Bregman-step solvers per host round trip.  The device PREDICTS the decisions of an
+ * iteration -- thread 0 of the last stage of the probe, after sum u^2, with the text of csrc/fw_div_decide.hpp: the
+ * slope band, div == 0 -> 1e-6, L / ls_ratio and the trial loop a -> (hcoef, hdiv, ld1, q1, f1) ->
+ * f1 <= fx + a*slope + a^gamma * L * div, L * ls_ratio, the stop tests -- and the caller CHECKS: the device's log and
+ * pow need not round as the host's do, so the caller replays every record with its own arithmetic and, where a decision
+ * differs, restores an earlier state (accbpg_fw_set_state) and redoes the steps with accbpg_fw_div_probe_step /
+ * accbpg_fw_div_apply.  prm carries the caller's exact ld, q and F[k0 - 1] at the start of the call; inside the call
+ * the device advances its own.
+ *   mode 0 (line search) and 1 (fixed L), FW_alg_div_step: iteration k = the kernels of accbpg_fw_div_probe_step,
+ *       the decision, the kernels of accbpg_fw_div_apply.  status 0: step applied; 1: step applied and the stop test
+ *       k > 0 && |F[k] - F[k-1]| < epsilon held (the solver applies, then stops); 2: handed back, NOTHING applied --
+ *       `reason` says why (1 the trial budget ACCBPG_FW_DIV_TRIALS_MAX ran out, 2 L became infinite, 3 slope > 0,
+ *       4 min_x is not > 0, 5 pivot outside [0, n), 6 a is not < 1: the capped step or a NaN, 7 the host's arithmetic
+ *       raises there); 3: not run.
+ *   mode 2 (classical step a = 2 / (k + 2)), FW_alg_descent_step: needs the probe of accbpg_fw_div_probe_step (or of an
+ *       earlier call in this mode) pending, as accbpg_fw_div_apply does (ACCBPG_ERR_ARG otherwise); iteration k >= 1 =
+ *       apply step k, probe, stop test |F[k] - F[k-1]| < epsilon || sqrt(sum_w2) < epsilon.  The record holds that
+ *       probe, the step that led to it, f1 = F[k].  status 0: applied and probed; 1: the same and the stop test held (the
+ *       state stays as the probe found it, its direction pending); 2: the step could not be decided, nothing applied.
+ * One C loop of plain launches -- the bodies, grids, block caps and summation orders of the step-by-step entries, so
+ * the probe fields, x, w and H are bit for bit theirs -- ONE synchronisation, and the records copied out once.  After
+ * a stop or a hand-back every later kernel of the call returns before it touches x, w, H, u, the stage-1 records or the
+ * pending pivot; later records read status 3.  *nrun_host <- the number of records with status != 3.  A record whose
+ * pivot lies outside [0, n) makes the call return ACCBPG_ERR_ARG with accbpg_fw_div_probe_step's message, the records
+ * filled in all the same.  1 <= nsteps <= ACCBPG_FW_RUN_MAX.  Mixes freely with accbpg_fw_div_probe_step /
+ * accbpg_fw_div_apply / accbpg_fw_init. */
+#define ACCBPG_FW_DIV_TRIALS_MAX 64
+typedef struct accbpg_fw_div_params {
+    int32_t mode;              /* 0 line search, 1 fixed L, 2 classical step */
+    int32_t reserved;
+    int64_t k0;                /* iteration number of the first step of the call */
+    double  L, gamma, ls_ratio, epsilon;
+    double  ld, q, F_prev;     /* the caller's book at the start of the call, F[k0 - 1] */
+} accbpg_fw_div_params;
+typedef struct accbpg_fw_div_step {
+    accbpg_fw_div_probe probe;
+    double  L;                 /* accepted (modes 0, 1) */
+    double  a, hcoef, hdiv;    /* the step */
+    double  ld1, q1, f1;       /* the device's own book behind the step; f1: trial value (modes 0, 1), F[k] (mode 2) */
+    int32_t trials, status, reason, reserved;
+} accbpg_fw_div_step;
+int accbpg_fw_div_run(accbpg_dopt* h, double fill, double value, const accbpg_fw_div_params* prm, int nsteps,
+                      accbpg_fw_div_step* steps_host, int* nrun_host);
+
+/* The inverse of accbpg_fw_get_state: x (n), w (n), H (m*m, row-major) from device buffers of the caller, device to
+ * device on the handle's stream (no synchronisation).  Leaves the stage-1 records and the pending pivot of
+ * accbpg_fw_div_probe_step cleared, as accbpg_fw_init leaves them: accbpg_fw_div_apply without a new probe is
+ * ACCBPG_ERR_ARG.  A null argument, or a handle without Frank-Wolfe state, is ACCBPG_ERR_ARG. */
+int accbpg_fw_set_state(accbpg_dopt* h, const double* x_dev, const double* w_dev, const double* H_dev);
+
 /* Lock-step Frank-Wolfe steps for the instances of a batch (accbpg_dopt_batch_create): ONE launch per step kernel
  * covers the active instances (active_host[i] != 0; NULL = all) and ONE synchronisation returns all probe records.
  * The state lives in the instance handles: after a batched step, x, w and H of instance i are bit for bit those of

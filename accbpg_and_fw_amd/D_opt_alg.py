@@ -8,6 +8,7 @@ reference writes them, and issues one rank-one update.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 import struct
@@ -1154,16 +1155,6 @@ def _div_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats, t_
     """D_opt_FW_div_step_device_steps on a state object and the sequential solver's ``_DivStepRun``."""
     mode = _lib.FW_DIV_LINESEARCH if run.linesearch else _lib.FW_DIV_FIXED_L
 
-    def sequential(k):                                          # one iteration of D_opt_FW_div_step
-        st.refresh_if_due()
-        rec = st.probe_div()
-        step, trial, stop = run.decide(k, rec, time.time() - t_start, lambda r: st.capped(r, run.linesearch))
-        if trial is None:
-            st.apply_step(*step)
-        else:
-            st.reinit(trial)
-        return stop
-
     def row(k):
         if verbose and k % verbskip == 0:
             print(f"{k:6d}  {run.F[k]:10.3e}  {run.Ls[k]:10.3e}  {run.T[k]:6.1f}")
@@ -1177,43 +1168,63 @@ def _div_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats, t_
         recs = st.run_div(mode, run.L, run.gamma, run.ls_ratio, run.epsilon, k, run.F[k - 1] if k else 0.0, nsteps)
         now = time.time() - t_start
         stats["chunks"] += 1
-        mine = []                                               # the host's steps of this chunk
-        for r in recs:
-            if r.status == _lib.FW_DIV_HANDED_BACK:             # nothing applied: the state is that of iteration k
-                stats["handed_back"] += 1
-                if r.reason == _lib.FW_DIV_HB_PIVOT:
-                    st.bad_div_pivot()
-                stop = sequential(k)
-            else:
-                try:
-                    step, _, stop = run.decide(k, r.probe, now, _replay_capped)
-                except _Capped:
-                    step = None
-                if step is not None and stop == (r.status == _lib.FW_DIV_STOPPED) and _same_bits(
-                        step + (run.Ls[k],), (r.probe.i, r.a, r.hcoef, r.hdiv, r.L), "qdddd"):
-                    mine.append(step)
-                    row(k)
-                    k += 1
-                    if stop:
-                        break
-                    continue
-                stats["rollbacks"] += 1                         # redo the chunk up to k with the host's decisions
-                st.restore()
-                for s in mine:
-                    st.probe_div()
-                    st.apply_step(*s)
-                if step is None:
-                    stop = sequential(k)
-                else:
-                    st.probe_div()
-                    st.apply_step(*step)
-            row(k)
-            k += 1
-            break
+        k, stop = _div_replay_records(st, run, recs, k, now, stats, t_start, row, [])
         if not stop:
             yield k - 1
 
     return run.result(st.x())
+
+
+def _div_sequential(st, run, k, t_start):
+    """One iteration of D_opt_FW_div_step on the state object; True when the stop test holds."""
+    st.refresh_if_due()
+    rec = st.probe_div()
+    step, trial, stop = run.decide(k, rec, time.time() - t_start, lambda r: st.capped(r, run.linesearch))
+    if trial is None:
+        st.apply_step(*step)
+    else:
+        st.reinit(trial)
+    return stop
+
+
+def _div_replay_records(st, run, recs, k, now, stats, t_start, row, mine):
+    """The host's replay of the records ``recs`` of a chunk from iteration k on, up to and including the first that is
+    not an agreed step: that one is redone from the snapshot (a disagreement) or run on the sequential path (a
+    hand-back).  ``mine``: the host's steps of the chunk before ``recs``.  Returns (the next k, stop)."""
+    stop = False
+    for r in recs:
+        if r.status == _lib.FW_DIV_HANDED_BACK:                 # nothing applied: the state is that of iteration k
+            stats["handed_back"] += 1
+            if r.reason == _lib.FW_DIV_HB_PIVOT:
+                st.bad_div_pivot()
+            stop = _div_sequential(st, run, k, t_start)
+        else:
+            try:
+                step, _, stop = run.decide(k, r.probe, now, _replay_capped)
+            except _Capped:
+                step = None
+            if step is not None and stop == (r.status == _lib.FW_DIV_STOPPED) and _same_bits(
+                    step + (run.Ls[k],), (r.probe.i, r.a, r.hcoef, r.hdiv, r.L), "qdddd"):
+                mine.append(step)
+                row(k)
+                k += 1
+                if stop:
+                    break
+                continue
+            stats["rollbacks"] += 1                             # redo the chunk up to k with the host's decisions
+            st.restore()
+            for s in mine:
+                st.probe_div()
+                st.apply_step(*s)
+            if step is None:
+                stop = _div_sequential(st, run, k, t_start)
+            else:
+                st.probe_div()
+                st.apply_step(*step)
+        row(k)
+        k += 1
+        break
+    return k, stop
 
 
 def D_opt_FW_descent_step_device(f, x0, maxitrs, epsilon=1e-14, verbose=True, verbskip=1, radius=1,
@@ -1240,11 +1251,6 @@ def D_opt_FW_descent_step_device_steps(f, x0, maxitrs, epsilon=1e-14, verbose=Tr
 
 def _descent_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats, t_start):
     """D_opt_FW_descent_step_device_steps on a state object and the sequential solver's ``_DescentRun``."""
-    def sequential(k):                                          # one iteration of D_opt_FW_descent_step
-        st.apply_step(*run.step(k))
-        st.refresh_if_due()
-        return run.probed(k, st.probe_div(), time.time() - t_start)
-
     def row(k):
         if verbose and (k % verbskip == 0 or k == 1):
             print(f"{k:6d}  {run.F[k]:10.3e}  {run.alpha:10.3e}  {run.T[k]:6.1f}")
@@ -1255,7 +1261,7 @@ def _descent_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats
     while k < maxitrs and not stop:
         nsteps = _div_chunk(k, maxitrs, sync_every, st.book, lead=1)
         if nsteps < 1:                                          # the refresh falls between this step and its probe
-            stop = sequential(k)
+            stop = _descent_sequential(st, run, k, t_start)
             row(k)
             k += 1
             if not stop:
@@ -1265,40 +1271,54 @@ def _descent_device_steps(st, run, maxitrs, verbose, verbskip, sync_every, stats
         recs = st.run_div(_lib.FW_DIV_CLASSICAL, 0.0, 0.0, 0.0, run.epsilon, k, run.F[k - 1], nsteps)
         now = time.time() - t_start
         stats["chunks"] += 1
-        mine = []
-        for r in recs:
-            if r.status == _lib.FW_DIV_HANDED_BACK:             # nothing applied: the probe before step k is pending
-                stats["handed_back"] += 1
-                stop = sequential(k)
-            else:
-                step = run.step(k)
-                mine.append(step)
-                agree = _same_bits(step[1:], (r.a, r.hcoef, r.hdiv), "ddd")
-                if agree:                                       # (else the record's probe saw another state)
-                    if not 0 <= r.probe.i < st.n:
-                        st.bad_div_pivot()
-                    stop = run.probed(k, r.probe, now)
-                    agree = stop == (r.status == _lib.FW_DIV_STOPPED)
-                if agree:
-                    row(k)
-                    k += 1
-                    if stop:
-                        break
-                    continue
-                stats["rollbacks"] += 1                         # redo the chunk up to k with the host's decisions
-                st.restore()
-                rec = st.probe_div()
-                for s in mine:
-                    st.apply_step(*s)
-                    rec = st.probe_div()
-                stop = run.probed(k, rec, time.time() - t_start)
-            row(k)
-            k += 1
-            break
+        k, stop = _descent_replay_records(st, run, recs, k, now, stats, t_start, row, [])
         if not stop:
             yield k - 1
 
     return run.result(st.x())
+
+
+def _descent_sequential(st, run, k, t_start):
+    """One iteration of D_opt_FW_descent_step on the state object; True when the stop test holds."""
+    st.apply_step(*run.step(k))
+    st.refresh_if_due()
+    return run.probed(k, st.probe_div(), time.time() - t_start)
+
+
+def _descent_replay_records(st, run, recs, k, now, stats, t_start, row, mine):
+    """``_div_replay_records`` for the classical step: the record of iteration k holds the step the device applied and
+    the probe behind it."""
+    stop = False
+    for r in recs:
+        if r.status == _lib.FW_DIV_HANDED_BACK:                 # nothing applied: the probe before step k is pending
+            stats["handed_back"] += 1
+            stop = _descent_sequential(st, run, k, t_start)
+        else:
+            step = run.step(k)
+            mine.append(step)
+            agree = _same_bits(step[1:], (r.a, r.hcoef, r.hdiv), "ddd")
+            if agree:                                           # (else the record's probe saw another state)
+                if not 0 <= r.probe.i < st.n:
+                    st.bad_div_pivot()
+                stop = run.probed(k, r.probe, now)
+                agree = stop == (r.status == _lib.FW_DIV_STOPPED)
+            if agree:
+                row(k)
+                k += 1
+                if stop:
+                    break
+                continue
+            stats["rollbacks"] += 1                             # redo the chunk up to k with the host's decisions
+            st.restore()
+            rec = st.probe_div()
+            for s in mine:
+                st.apply_step(*s)
+                rec = st.probe_div()
+            stop = run.probed(k, rec, time.time() - t_start)
+        row(k)
+        k += 1
+        break
+    return k, stop
 
 
 # ---- the Bregman-step solvers on the instances of a batch in lock-step (DESIGN.md 6g) --------------------------------
@@ -1417,4 +1437,220 @@ def D_opt_FW_descent_step_batch_steps(batch, x0, maxitrs, epsilon=1e-14, radius=
         if not any(active):
             break
         yield k
+    return [runs[i].result(batch.fw_x(i, as_numpy)) for i in range(K)]
+
+
+# ---- the lock-step Bregman-step batches with the line search predicted on the device ------------------
+# The generators reach the device through the batch alone -- the methods of the 6g solvers plus fw_div_run, fw_snapshot,
+# fw_restore, fw_div_replay and bad_div_pivot -- and every instance's records go through the per-record code of the
+# single-handle device solvers above (``_div_replay_records`` / ``_descent_replay_records``) on a view of that instance.
+REPLAYS = ("c", "python")
+
+
+class _BatchInstance:
+    """Instance i of a batch as the state object the per-record code of the device solvers works on: every call is a
+    masked call of the batch on this instance alone, so a roll-back or a hand-back moves no other instance."""
+
+    def __init__(self, batch, i, X, books, radius):
+        self.batch, self.i, self.X, self.books, self.radius = batch, i, X, books, radius
+        self.book = books[i]
+        self.n = batch.n
+        self.only = [j == i for j in range(batch.K)]
+
+    def refresh_if_due(self):
+        _div_refresh(self.batch, self.X, self.books, self.only)
+
+    def probe_div(self):
+        return copy.copy(self.batch.fw_div_probe(self.only, self.radius)[self.i])
+
+    def apply_step(self, p, a, hcoef, hdiv):
+        steps = [None] * self.batch.K
+        steps[self.i] = (p, a, hcoef, hdiv)
+        self.batch.fw_div_apply(self.only, steps)
+
+    def capped(self, rec, valued):
+        return self.batch.fw_div_capped(self.i, rec.i, self.radius, valued)
+
+    def reinit(self, trial):
+        self.X[self.i] = trial
+        _div_reinit(self.batch, self.X, self.books, self.only)
+
+    def restore(self):
+        self.batch.fw_restore(self.i)
+
+    def bad_div_pivot(self):
+        self.batch.bad_div_pivot(self.i)
+
+
+def _named_once(i, call, *args):
+    """``_named`` for calls that may already have named the instance (the masked re-initialisation does)."""
+    try:
+        return call(*args)
+    except (ValueError, AssertionError) as err:
+        head = "instance %d: " % i
+        raise type(err)(str(err) if str(err).startswith(head) else head + str(err)) from None
+
+
+def _no_row(k):
+    pass
+
+
+def _replay_fast_forward(st, prm, recs, pending=None):
+    """The C replay of one instance's records (``accbpg_fw_div_replay``) from the book ``prm``; the book is advanced
+    past the agreed records.  Returns (agreed, verdict, F, Ls or step lengths, the book as the C side returns it)."""
+    agreed, verdict, F, LA, bk = st.batch.fw_div_replay(st.i, prm, recs, pending)
+    st.book.ld, st.book.q = bk.ld, bk.q
+    st.book.since += agreed
+    return agreed, verdict, F, LA, bk
+
+
+def _div_replay_chunk(st, run, mode, recs, k, now, stats, replay, t_start):
+    """One instance's records of a chunk that started at its iteration k: (the next k, stop)."""
+    mine = []
+    if replay == "c":
+        prm = _lib.FwDivParams(mode, 0, k, run.L, run.gamma, run.ls_ratio, run.epsilon, st.book.ld, st.book.q,
+                               run.F[k - 1] if k else 0.0)
+        agreed, verdict, F, Ls, bk = _replay_fast_forward(st, prm, recs)
+        if agreed:
+            run.F[k:k + agreed], run.Ls[k:k + agreed], run.T[k:k + agreed] = F, Ls, now
+            run.L, run.done = bk.L, k + agreed
+            k += agreed
+        if verdict in (_lib.FW_DIV_RP_END, _lib.FW_DIV_RP_STOP):
+            return k, verdict == _lib.FW_DIV_RP_STOP
+        if verdict in (_lib.FW_DIV_RP_HOST_HB, _lib.FW_DIV_RP_DISAGREE):     # a roll-back redoes the agreed steps
+            for j in range(agreed):
+                r = recs[j]
+                mine.append((r.probe.i, r.a, r.hcoef, r.hdiv))
+        recs = [recs[agreed]]
+    return _div_replay_records(st, run, recs, k, now, stats, t_start, _no_row, mine)
+
+
+def _descent_replay_chunk(st, run, recs, k, now, stats, replay, t_start):
+    """``_div_replay_chunk`` for the classical step; the probe before the chunk's first step is ``run.rec``."""
+    mine = []
+    if replay == "c":
+        prm = _lib.FwDivParams(_lib.FW_DIV_CLASSICAL, 0, k, 0.0, 0.0, 0.0, run.epsilon, st.book.ld, st.book.q, run.F[k - 1])
+        agreed, verdict, F, alphas, bk = _replay_fast_forward(st, prm, recs, run.rec)
+        if agreed:
+            if verdict in (_lib.FW_DIV_RP_HOST_HB, _lib.FW_DIV_RP_DISAGREE, _lib.FW_DIV_RP_PIVOT):
+                prev = run.rec                                  # a roll-back redoes the agreed steps
+                for j in range(agreed):
+                    r = recs[j]
+                    mine.append((prev.i, r.a, r.hcoef, r.hdiv))
+                    prev = r.probe
+            run.F[k:k + agreed], run.T[k:k + agreed] = F, now
+            run.k, run.alpha, run.rec = k + agreed - 1, float(alphas[-1]), recs[agreed - 1].probe
+            k += agreed
+        if verdict in (_lib.FW_DIV_RP_END, _lib.FW_DIV_RP_STOP):
+            return k, verdict == _lib.FW_DIV_RP_STOP
+        recs = [recs[agreed]]
+    return _descent_replay_records(st, run, recs, k, now, stats, t_start, _no_row, mine)
+
+
+def _batch_device_setup(batch, x0, radius, refresh, replay):
+    if replay not in REPLAYS:
+        raise ValueError("replay must be one of %s" % (REPLAYS,))
+    X, as_numpy = batch.fw_rows(x0)
+    logdet = batch.fw_init(X)
+    books = [_DivBook(batch.m, radius, refresh, logdet[i]) for i in range(batch.K)]
+    return X, as_numpy, books, [_BatchInstance(batch, i, X, books, radius) for i in range(batch.K)]
+
+
+def D_opt_FW_div_step_batch_device(batch, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2, radius=1,
+                                   refresh=REFRESH_DEFAULT, sync_every=SYNC_EVERY_DEFAULT, stats=None, replay="c"):
+    """D_opt_FW_div_step_batch with ``sync_every`` iterations per host round trip, by the contract of
+    ``D_opt_FW_div_step_device`` per instance: the device predicts a chunk of every running instance in lock-step
+    (accbpg_dopt_batch_fw_div_run), the host replays each instance's records -- ``replay="c"``: the agreed records in C
+    (accbpg_fw_div_replay), the first that is not an agreed step through the Python text; ``replay="python"``: every
+    record through the Python text -- and owns the result.  A chunk is as long as the shortest of the running
+    instances' own limits (maxitrs, its refresh); a disagreement restores and redoes that instance alone, a hand-back
+    runs that iteration of that instance on the sequential path, and the instances then carry different iteration
+    numbers.  ``stats``: ``chunks`` (per instance and call), ``rollbacks``, ``handed_back``, summed over the instances.
+    Silent.  Returns a list of K tuples (x, F, Ls, T); x, F, Ls and the iteration count of instance i are bit-identical
+    to ``D_opt_FW_div_step(batch.instance(i), L_i, x0_i, maxitrs, gamma, ...)``, and what that raises is raised with
+    "instance i: " in front."""
+    return _drain(D_opt_FW_div_step_batch_device_steps(batch, L, x0, maxitrs, gamma, epsilon, linesearch, ls_ratio,
+                                                       radius, refresh, sync_every, stats, replay))
+
+
+def D_opt_FW_div_step_batch_device_steps(batch, L, x0, maxitrs, gamma, epsilon=1e-14, linesearch=True, ls_ratio=2,
+                                         radius=1, refresh=REFRESH_DEFAULT, sync_every=SYNC_EVERY_DEFAULT, stats=None,
+                                         replay="c"):
+    """Generator form: yields the largest iteration number reached after each chunk, returns the list."""
+    K = batch.K
+    Lv = _batch_eps(batch, L)
+    for i in range(K):
+        _named(i, _check_options, Lv[i], epsilon, ls_ratio)
+    stats = _device_stats(stats)
+    t_start = time.time()
+    X, as_numpy, books, insts = _batch_device_setup(batch, x0, radius, refresh, replay)
+    runs = [_DivStepRun(books[i], Lv[i], maxitrs, gamma, epsilon, linesearch, ls_ratio) for i in range(K)]
+    mode = _lib.FW_DIV_LINESEARCH if linesearch else _lib.FW_DIV_FIXED_L
+    ks = [0] * K
+    running = [maxitrs > 0] * K
+    while any(running):
+        _div_refresh(batch, X, books, running)
+        nsteps = min(_div_chunk(ks[i], maxitrs, sync_every, books[i]) for i in range(K) if running[i])
+        batch.fw_snapshot(running)
+        params = [(ks[i], runs[i].L, gamma, ls_ratio, epsilon, books[i].ld, books[i].q,
+                   runs[i].F[ks[i] - 1] if ks[i] else 0.0) if running[i] else None for i in range(K)]
+        recs = batch.fw_div_run(mode, params, nsteps, running, radius)
+        now = time.time() - t_start
+        for i in range(K):
+            if running[i]:
+                stats["chunks"] += 1
+                ks[i], stop = _named_once(i, _div_replay_chunk, insts[i], runs[i], mode, recs[i], ks[i], now, stats,
+                                          replay, t_start)
+                running[i] = not stop and ks[i] < maxitrs
+        yield max(ks) - 1
+    return [runs[i].result(batch.fw_x(i, as_numpy)) for i in range(K)]
+
+
+def D_opt_FW_descent_step_batch_device(batch, x0, maxitrs, epsilon=1e-14, radius=1, refresh=REFRESH_DEFAULT,
+                                       sync_every=SYNC_EVERY_DEFAULT, stats=None, replay="c"):
+    """D_opt_FW_descent_step_batch with ``sync_every`` iterations per host round trip (see
+    ``D_opt_FW_div_step_batch_device``).  Silent.  Returns a list of K tuples (x, F, T, G); x, F, G and the iteration
+    count of instance i are bit-identical to ``D_opt_FW_descent_step(batch.instance(i), x0_i, maxitrs, ...)``."""
+    return _drain(D_opt_FW_descent_step_batch_device_steps(batch, x0, maxitrs, epsilon, radius, refresh, sync_every,
+                                                           stats, replay))
+
+
+def D_opt_FW_descent_step_batch_device_steps(batch, x0, maxitrs, epsilon=1e-14, radius=1, refresh=REFRESH_DEFAULT,
+                                             sync_every=SYNC_EVERY_DEFAULT, stats=None, replay="c"):
+    """Generator form: yields the largest iteration number reached after each chunk, returns the list."""
+    K = batch.K
+    stats = _device_stats(stats)
+    t_start = time.time()
+    X, as_numpy, books, insts = _batch_device_setup(batch, x0, radius, refresh, replay)
+    runs = [_DescentRun(books[i], maxitrs, epsilon) for i in range(K)]
+    first = batch.fw_div_probe([True] * K, radius)
+    now = time.time() - t_start
+    for i in range(K):
+        runs[i].first(copy.copy(first[i]), now)
+    ks = [1] * K
+    running = [maxitrs > 1] * K
+    while any(running):
+        limit = [_div_chunk(ks[i], maxitrs, sync_every, books[i], lead=1) if running[i] else 0 for i in range(K)]
+        due = [running[i] and limit[i] < 1 for i in range(K)]   # the refresh falls between this step and its probe
+        if any(due):
+            for i in range(K):
+                if due[i]:
+                    stop = _named_once(i, _descent_sequential, insts[i], runs[i], ks[i], t_start)
+                    ks[i] += 1
+                    running[i] = not stop and ks[i] < maxitrs
+            yield max(ks) - 1
+            continue
+        nsteps = min(limit[i] for i in range(K) if running[i])
+        batch.fw_snapshot(running)
+        params = [(ks[i], 0.0, 0.0, 0.0, epsilon, books[i].ld, books[i].q, runs[i].F[ks[i] - 1]) if running[i] else None
+                  for i in range(K)]
+        recs = batch.fw_div_run(_lib.FW_DIV_CLASSICAL, params, nsteps, running, radius)
+        now = time.time() - t_start
+        for i in range(K):
+            if running[i]:
+                stats["chunks"] += 1
+                ks[i], stop = _named_once(i, _descent_replay_chunk, insts[i], runs[i], recs[i], ks[i], now, stats, replay,
+                                          t_start)
+                running[i] = not stop and ks[i] < maxitrs
+        yield max(ks) - 1
     return [runs[i].result(batch.fw_x(i, as_numpy)) for i in range(K)]

@@ -19,7 +19,8 @@ from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball, lmo_l2_ball_
 from .D_opt_alg import (D_opt_FW, D_opt_FW_away, D_opt_FW_batch, D_opt_FW_away_batch, D_opt_FW_device,
                         D_opt_FW_away_device, D_opt_FW_batch_device, D_opt_FW_away_batch_device,
                         D_opt_FW_div_step, D_opt_FW_descent_step, D_opt_FW_div_step_batch,
-                        D_opt_FW_descent_step_batch, D_opt_FW_div_step_device, D_opt_FW_descent_step_device)
+                        D_opt_FW_descent_step_batch, D_opt_FW_div_step_device, D_opt_FW_descent_step_device,
+                        D_opt_FW_div_step_batch_device, D_opt_FW_descent_step_batch_device)
 from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, D_opt_KYinit_device, D_opt_KYinit_batch,
                            Poisson_regrL1, Poisson_regrL2, KL_nonneg_regr, FrobeniusSymLossExL2Ball,
                            FrobeniusSymLossExLInfBall, FrobeniusSymLossResMeasEx, Poisson_regr_simplex,
@@ -41,6 +42,7 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "D_opt_FW_batch", "D_opt_FW_away_batch", "D_opt_FW_device", "D_opt_FW_away_device",
            "D_opt_FW_batch_device", "D_opt_FW_away_batch_device", "D_opt_KYinit_device",
            "D_opt_KYinit_batch", "D_opt_FW_div_step", "D_opt_FW_descent_step", "D_opt_FW_div_step_batch",
-           "D_opt_FW_descent_step_batch", "D_opt_FW_div_step_device", "D_opt_FW_descent_step_device", "SVM_fun",
+           "D_opt_FW_descent_step_batch", "D_opt_FW_div_step_device", "D_opt_FW_descent_step_device",
+           "D_opt_FW_div_step_batch_device", "D_opt_FW_descent_step_batch_device", "SVM_fun",
            "PolyDiv", "svm_digits_ds_divs_ball", "random_point_in_l2_ball", "generate_dataset_for_svm"]
 __version__ = "0.1.0"

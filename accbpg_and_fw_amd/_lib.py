@@ -67,6 +67,8 @@ FW_DIV_LINESEARCH, FW_DIV_FIXED_L, FW_DIV_CLASSICAL = 0, 1, 2      # accbpg_fw_d
 FW_DIV_APPLIED, FW_DIV_STOPPED, FW_DIV_HANDED_BACK, FW_DIV_NOT_RUN = 0, 1, 2, 3    # accbpg_fw_div_step.status
 (FW_DIV_HB_NONE, FW_DIV_HB_BUDGET, FW_DIV_HB_L_INF, FW_DIV_HB_SLOPE, FW_DIV_HB_MIN_X, FW_DIV_HB_PIVOT, FW_DIV_HB_CAP,
  FW_DIV_HB_ARITH) = range(8)                                        # accbpg_fw_div_step.reason
+(FW_DIV_RP_END, FW_DIV_RP_STOP, FW_DIV_RP_DEVICE_HB, FW_DIV_RP_HOST_HB, FW_DIV_RP_DISAGREE,
+ FW_DIV_RP_PIVOT) = range(6)                                        # accbpg_fw_div_replay: *verdict_out
 
 _P = C.c_void_p
 _SIGS = {
@@ -154,6 +156,11 @@ _SIGS = {
                                                  C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "accbpg_dopt_batch_fw_run": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int),
                                            C.POINTER(FwStep), C.POINTER(C.c_int)]),
+    "accbpg_dopt_batch_fw_div_run": (C.c_int, [_P, C.c_double, C.c_double, C.POINTER(FwDivParams), C.c_int,
+                                               C.POINTER(C.c_int), C.POINTER(FwDivStep), C.POINTER(C.c_int)]),
+    "accbpg_fw_div_replay": (C.c_int, [C.POINTER(FwDivParams), C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                       C.POINTER(FwDivStep), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(FwDivParams), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "accbpg_dopt_batch_kyinit": (C.c_int, [_P, _P, C.POINTER(C.c_int64), _P]),
     "accbpg_poisson_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(_P)]),
     "accbpg_poisson_destroy": (C.c_int, [_P]),

@@ -22,6 +22,62 @@ from . import _lib
 from .functions import DOptimalObj, _ptr, _stream, from_dev, to_dev
 
 
+class _FwDivRecords:
+    """The records of one instance of a ``fw_div_run`` call: ``count`` entries of a ctypes array of ``_lib.FwDivStep``
+    from ``first`` on.  The buffer belongs to the batch and the next call overwrites it: indexing copies a record out."""
+
+    def __init__(self, array, first, count):
+        self.array, self.first, self.count = array, first, count
+
+    def __len__(self):
+        return self.count
+
+    def __getitem__(self, j):
+        if not 0 <= j < self.count:
+            raise IndexError(j)
+        return _lib.FwDivStep.from_buffer_copy(self.array[self.first + j])
+
+    def pivot(self, j):
+        return self.array[self.first + j].probe.i
+
+    def address(self):
+        return C.addressof(self.array) + self.first * C.sizeof(_lib.FwDivStep)
+
+
+def _lib_fw_div_replay(lib, prm, n, m, fill, radius, recs, pending=None):
+    """``accbpg_fw_div_replay`` on the records ``recs`` (a ``_FwDivRecords``, or any sequence of objects with the fields
+    of ``_lib.FwDivStep``) from the book ``prm``; see ``DOptimalBatch.fw_div_replay``."""
+    nrun = len(recs)
+    classical = prm.mode == _lib.FW_DIV_CLASSICAL
+    if isinstance(recs, _FwDivRecords) and not classical:
+        steps = C.cast(recs.address(), C.POINTER(_lib.FwDivStep))
+    else:                                           # (classical: the pending probe in front of the records)
+        lead = 1 if classical else 0
+        arr = (_lib.FwDivStep * (nrun + lead))()
+        if classical:
+            for name, _ in _lib.FwDivProbe._fields_:
+                setattr(arr[0].probe, name, getattr(pending, name))
+        if isinstance(recs, _FwDivRecords):
+            C.memmove(C.addressof(arr) + lead * C.sizeof(_lib.FwDivStep), recs.address(), nrun * C.sizeof(_lib.FwDivStep))
+        else:
+            for j, r in enumerate(recs):
+                s = arr[lead + j]
+                for name, _ in _lib.FwDivProbe._fields_:
+                    setattr(s.probe, name, getattr(r.probe, name))
+                for name in ("L", "a", "hcoef", "hdiv", "ld1", "q1", "f1", "trials", "status", "reason"):
+                    setattr(s, name, getattr(r, name))
+        steps = arr
+    F = np.empty(nrun)
+    LA = np.empty(nrun)
+    book = _lib.FwDivParams()
+    agreed, verdict = C.c_int(0), C.c_int(0)
+    rc = lib.accbpg_fw_div_replay(C.byref(prm), n, m, fill, radius, steps, nrun,
+                                  F.ctypes.data_as(C.POINTER(C.c_double)), LA.ctypes.data_as(C.POINTER(C.c_double)),
+                                  C.byref(book), C.byref(agreed), C.byref(verdict))
+    _lib.check(rc, "accbpg_fw_div_replay")
+    return agreed.value, verdict.value, F[:agreed.value], LA[:agreed.value], book
+
+
 class DOptimalBatch:
     """K D-optimal objectives of ONE shape evaluated together (C-ABI ``accbpg_dopt_batch_*``): every call covers the
     active instances with one launch per kernel family and one readback.  Vectors are K x n CUDA tensors, row i =
@@ -56,6 +112,9 @@ class DOptimalBatch:
         self._fw_div_probes = (_lib.FwDivProbe * self.K)()      # records of fw_div_probe
         self._fw_div_radius = 1.0                   # ... and the vertex value of the last one (fw_div_apply steps towards it)
         self._fw_bad_pivot = ""                     # the library's message of the last fw_run that returned a status 2
+        self._fw_div_steps = None                   # K x FW_RUN_MAX records of fw_div_run (allocated by the first call)
+        self._fw_bad_div_pivot = ""                 # the library's message of the last fw_div_run with such a record
+        self._fw_snaps = {}                         # instance -> (x, w, H) of its last fw_snapshot
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -329,6 +388,74 @@ class DOptimalBatch:
         as the sequential solver forms them; f is None unless ``valued``."""
         from .D_opt_alg import _capped_trial
         return _capped_trial(self.instance(i), self.fw_x(i, False), p, radius, valued)
+
+    # ---- what the device-decided Bregman-step batches need on top (DESIGN.md 6i) ----
+    def fw_div_run(self, mode, params, nsteps, active=None, radius=1):
+        """``nsteps`` iterations of the active instances predicted on the device behind one synchronisation
+        (``accbpg_dopt_batch_fw_div_run``).  params[i] = (k0, L, gamma, ls_ratio, epsilon, ld, q, F_prev) of instance i:
+        its own iteration number and the host's exact book.  Returns a list of K entries: for an active instance the
+        records of the iterations that ran (a ``_FwDivRecords`` over a buffer the next call overwrites; indexing copies
+        a record out), None for an inactive one.  A record whose pivot lies outside [0, n) is returned, not raised: the
+        replay reaches it in its turn and calls ``bad_div_pivot``."""
+        from .D_opt_alg import _LMO_FILL
+        mask, idx = self._mask(active)
+        K, nsteps = self.K, int(nsteps)
+        if self._fw_div_steps is None:
+            self._fw_div_steps = (_lib.FwDivStep * (K * _lib.FW_RUN_MAX))()
+            self._fw_div_prm = (_lib.FwDivParams * K)()
+        prm = self._fw_div_prm
+        for i in idx:
+            k0, L, gamma, ls_ratio, epsilon, ld, q, F_prev = params[i]
+            prm[i] = _lib.FwDivParams(int(mode), 0, int(k0), float(L), float(gamma), float(ls_ratio), float(epsilon),
+                                      float(ld), float(q), float(F_prev))
+        nrun = (C.c_int * K)()
+        self._fw_div_radius = float(radius)
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_dopt_batch_fw_div_run(self._h, _LMO_FILL, self._fw_div_radius, prm, nsteps, mask,
+                                                        self._fw_div_steps, nrun)
+        out = [None] * K
+        for i in idx:
+            out[i] = _FwDivRecords(self._fw_div_steps, i * _lib.FW_RUN_MAX, nrun[i])
+        if rc:
+            bad = [i for i in idx if any(not 0 <= out[i].pivot(j) < self.n for j in range(nrun[i]))]
+            if not (rc == _lib.ERR_ARG and bad):
+                _lib.check(rc, "accbpg_dopt_batch_fw_div_run")
+            self._fw_bad_div_pivot = _lib.last_error()          # (kept for bad_div_pivot)
+        return out
+
+    def fw_div_replay(self, i, prm, recs, pending=None):
+        """The host's replay of instance i's records in C (``accbpg_fw_div_replay``) from the book ``prm`` (a
+        ``_lib.FwDivParams``); ``pending``: in the classical mode, the probe record that was pending when the chunk
+        started.  Returns (agreed, verdict, F, L_or_alpha, book) with F and L_or_alpha NumPy arrays of ``agreed``
+        entries and book the ``_lib.FwDivParams`` BEFORE record ``agreed``."""
+        from .D_opt_alg import _LMO_FILL
+        return _lib_fw_div_replay(self._lib, prm, self.n, self.m, _LMO_FILL, self._fw_div_radius, recs, pending)
+
+    def bad_div_pivot(self, i):
+        """The exception of the sequential solver's probe of instance i with a pivot outside [0, n), with the message of
+        the ``fw_div_run`` call that returned the record."""
+        raise ValueError("instance %d: accbpg_fw_div_probe_step: bad argument (%s)" % (i, self._fw_bad_div_pivot))
+
+    def fw_snapshot(self, active=None):
+        """Keep (x, w, H) of the active instances as they stand, in buffers of the batch (``accbpg_fw_get_state`` on the
+        instance handles: synchronises)."""
+        _, idx = self._mask(active)
+        with torch.cuda.device(self.device):
+            for i in idx:
+                if i not in self._fw_snaps:
+                    self._fw_snaps[i] = (torch.empty(self.n, dtype=torch.float64, device=self.device),
+                                         torch.empty(self.n, dtype=torch.float64, device=self.device),
+                                         torch.empty(self.m, self.m, dtype=torch.float64, device=self.device))
+                rc = self._lib.accbpg_fw_get_state(self._inst_h(i), *[_ptr(t) for t in self._fw_snaps[i]])
+                if rc:
+                    _lib.check(rc, "accbpg_fw_get_state")
+
+    def fw_restore(self, i):
+        """Instance i back to its last ``fw_snapshot`` (``accbpg_fw_set_state``: no probe is pending afterwards); the
+        other instances stay as they are."""
+        with torch.cuda.device(self.device):
+            rc = self._lib.accbpg_fw_set_state(self._inst_h(i), *[_ptr(t) for t in self._fw_snaps[i]])
+        _lib.check(rc, "accbpg_fw_set_state")
 
     def fw_run(self, away, eps, nsteps, active=None):
         """``nsteps`` iterations of the active instances decided on the device behind one synchronisation

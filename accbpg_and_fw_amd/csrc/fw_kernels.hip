@@ -6,6 +6,7 @@
 #include "internal.h"
 #include "reduce.hpp"
 #include "fw_div_decide.hpp"
+#include "fw_div_replay.hpp"
 
 namespace accbpg {
 
@@ -630,23 +631,28 @@ __global__ __launch_bounds__(FB) void fw_xupdate_gather_brun_kernel(const FwInst
     const FwInst t = tab[i];
     fw_xupdate_gather_body(t.x, n, r.p, r.xscale, r.xadd, t.V, ldv, m, fw_vp_of(t, m));
 }
+// (Hv, the pass over V and the rank-one update take the slot type of the caller: FwRunSlot here, FwDivRunSlot in the
+//  Bregman-step family below -- both begin with the FwRun these kernels read)
+template <class Slot>
 __global__ __launch_bounds__(FB) void fw_gemv_h_brun_kernel(const FwInst* __restrict__ tab,
-                                                           const FwRunSlot* __restrict__ runs, BatchAct act, int64_t m) {
+                                                           const Slot* __restrict__ runs, BatchAct act, int64_t m) {
     const int i = act.idx[blockIdx.y];
     if (runs[i].run.stop) return;
     const FwInst t = tab[i];
     fw_gemv_h_body(t.H, m, fw_vp_of(t, m), t.hv);
 }
+template <class Slot>
 __global__ __launch_bounds__(FB) void fw_rank1_brun_kernel(const FwInst* __restrict__ tab,
-                                                          const FwRunSlot* __restrict__ runs, BatchAct act, int64_t m) {
+                                                          const Slot* __restrict__ runs, BatchAct act, int64_t m) {
     const int i = act.idx[blockIdx.y];
     const FwRun r = runs[i].run;
     if (r.stop) return;
     const FwInst t = tab[i];
     fw_rank1_body(t.H, m, t.hv, r.hcoef, r.hdiv, fw_vp_of(t, m), t.q);
 }
+template <class Slot>
 __global__ __launch_bounds__(FB) void fw_vgemv_partial_brun_kernel(const FwInst* __restrict__ tab,
-                                                                  const FwRunSlot* __restrict__ runs, BatchAct act,
+                                                                  const Slot* __restrict__ runs, BatchAct act,
                                                                   int64_t ldv, int64_t m, int64_t n, int nsplit) {
     const int i = act.idx[blockIdx.z];
     if (runs[i].run.stop) return;
@@ -900,13 +906,11 @@ __global__ __launch_bounds__(FB) void fw_div_usum_run_kernel(const FwRun* __rest
     if (run->stop) return;
     fw_div_usum_body(upart, nsplit, n, u, u2part);
 }
-__global__ __launch_bounds__(FB) void fw_div_u2final_run_kernel(FwDivRunSlot* sl, const double* __restrict__ u2part,
-                                                               int nb, FwDivRunArgs ra, int64_t m, double fill,
-                                                               double value, int64_t k, int j,
-                                                               accbpg_fw_div_step* __restrict__ steps) {
-    if (fw_run_stop(&sl->run)) return;
-    reduce_final_body<FB, 1, false>(u2part, nb, sl->rec + 8);
-    if (threadIdx.x != 0) return;
+// one thread, behind sum u^2: the decisions of iteration k from the slot's probe record, the step for the update kernels
+// and record j of the row `steps`
+__device__ __forceinline__ void fw_div_run_decide(FwDivRunSlot* sl, const FwDivRunArgs& ra, int64_t m, double fill,
+                                                  double value, int64_t k, int j,
+                                                  accbpg_fw_div_step* __restrict__ steps) {
     const FwDivRecView v = fw_div_view(sl->rec);                // (doubles 0..7 by the stage before, 8 by this thread)
     FwdBook b = fw_div_book(sl, m, fill, value);
     FwdOut o;
@@ -936,12 +940,121 @@ __global__ __launch_bounds__(FB) void fw_div_u2final_run_kernel(FwDivRunSlot* sl
     FwdOut o2;
     fw_div_next_classical(sl, &b, v, ra.n, k + 1, &o2, (j + 1 < ra.nsteps) ? steps + j + 1 : nullptr);
 }
+__global__ __launch_bounds__(FB) void fw_div_u2final_run_kernel(FwDivRunSlot* sl, const double* __restrict__ u2part,
+                                                               int nb, FwDivRunArgs ra, int64_t m, double fill,
+                                                               double value, int64_t k, int j,
+                                                               accbpg_fw_div_step* __restrict__ steps) {
+    if (fw_run_stop(&sl->run)) return;
+    reduce_final_body<FB, 1, false>(u2part, nb, sl->rec + 8);
+    if (threadIdx.x != 0) return;
+    fw_div_run_decide(sl, ra, m, fill, value, k, j, steps);
+}
 __global__ __launch_bounds__(FB) void fw_div_xupdate_run_kernel(const FwRun* __restrict__ run, double* __restrict__ x,
                                                                int64_t n, double fill, double value) {
     const FwRun r = *run;
     if (r.stop) return;
     fw_div_xupdate_body(x, n, r.p, r.xscale, fill, value);
 }
+
+// ---- the Bregman-step kernels: several iterations per host round trip for the active instances of a batch -------
+// (accbpg_dopt_batch_fw_div_run)  The "batch-run" forms of the same bodies: the instance is the grid dimension of the
+// lock-step forms, its pointers come from the batch's FwInst and FwDivInst tables, its step and its predictor's book from
+// its own FwDivRunSlot.  A workgroup returns before it touches anything when ITS instance has stopped, is marked "stop
+// after this apply" or was handed back (one load per workgroup, the same for all its threads) while the workgroups of the
+// other instances go on.  blockIdx.x / gridDim.x, the FW_DIV_CAP block cap, the row split and the fixed summation tree
+// are the single handle's; Hv, the pass over V and the rank-one update are the batch-run kernels of accbpg_dopt_batch_
+// fw_run on this family's slots.  Thread 0 of an instance's last probe stage calls fw_div_run_decide with that instance's
+// own k0, gamma, ls_ratio and epsilon and writes record j of that instance's row of the pinned array.
+__global__ void fw_div_brun_init_kernel(FwDivRunSlot* runs, const FwDivInst* __restrict__ dtab, FwDivInitArgs ia,
+                                        int mode, int64_t m, int64_t n, double fill, double value,
+                                        accbpg_fw_div_step* __restrict__ steps) {
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;        // one thread per active instance
+    if (a >= ia.n) return;
+    const int i = ia.idx[a];
+    FwDivRunSlot* sl = runs + i;
+    sl->run.stop = 0; sl->run.pad = 0; sl->run.p = -1;
+    sl->run.xscale = 0.0; sl->run.xadd = 0.0; sl->run.hcoef = 0.0; sl->run.hdiv = 1.0;
+    sl->ld = ia.ld[a]; sl->q = ia.q[a]; sl->F_prev = ia.F_prev[a]; sl->L = ia.L[a]; sl->k0 = ia.k0[a];
+    if (mode == FWD_CLASSICAL) {                                // the step of iteration k0 from the pending probe
+        const double* pin = dtab[i].pin;
+        for (int c = 0; c < 9; ++c) sl->rec[c] = pin[c];
+        FwdBook b = fw_div_book(sl, m, fill, value);
+        FwdOut o;
+        fw_div_next_classical(sl, &b, fw_div_view(sl->rec), n, ia.k0[a], &o, steps + (size_t)i * ACCBPG_FW_RUN_MAX);
+    }
+}
+__global__ __launch_bounds__(FB) void fw_div_probe_partial_brun_kernel(const FwInst* __restrict__ tab,
+                                                                      const FwDivInst* __restrict__ dtab,
+                                                                      const FwDivRunSlot* runs, FwProbeArgs pa,
+                                                                      int64_t m, int64_t n, double fill, double value) {
+    const int a = blockIdx.y, i = pa.idx[a];
+    if (fw_div_run_halted(&runs[i].run)) return;
+    const FwInst t = tab[i];
+    double* ws = dtab[i].ws;
+    fw_div_probe_partial_body(fw_part_of(t, m), pa.nblk[a], t.w, t.x, n, fill, value, fw_div_rec_of(ws, n),
+                              fw_div_mxslot_of(ws, n));
+}
+// (one workgroup per instance: every thread reads the two words before thread 0 turns "stop after this apply" into stop)
+__global__ __launch_bounds__(FB) void fw_div_probe_final_brun_kernel(const FwInst* __restrict__ tab,
+                                                                    const FwDivInst* __restrict__ dtab,
+                                                                    FwDivRunSlot* runs, BatchAct act, int nb,
+                                                                    int64_t ldv, int64_t m, int64_t n) {
+    const int i = act.idx[blockIdx.y];
+    FwDivRunSlot* sl = runs + i;
+    const int halted = fw_div_run_halted(&sl->run);
+    __syncthreads();
+    if (halted) {
+        if (threadIdx.x == 0 && sl->run.stop == 0) fw_div_set_stop(&sl->run, 1);
+        return;
+    }
+    const FwInst t = tab[i];
+    double* ws = dtab[i].ws;
+    fw_div_probe_final_body(fw_div_rec_of(ws, n), nb, fw_div_mxslot_of(ws, n), t.x, n, t.V, ldv, m, fw_vp_of(t, m),
+                            sl->rec);
+}
+__global__ __launch_bounds__(FB) void fw_div_usum_brun_kernel(const FwInst* __restrict__ tab,
+                                                             const FwDivInst* __restrict__ dtab,
+                                                             const FwDivRunSlot* __restrict__ runs, BatchAct act,
+                                                             int nsplit, int64_t n) {
+    const int i = act.idx[blockIdx.y];
+    if (runs[i].run.stop) return;
+    double* ws = dtab[i].ws;
+    fw_div_usum_body(tab[i].vws, nsplit, n, ws, fw_div_u2part_of(ws, n));
+}
+__global__ __launch_bounds__(FB) void fw_div_u2final_brun_kernel(const FwDivInst* __restrict__ dtab, FwDivRunSlot* runs,
+                                                                FwDivDecideArgs da, int mode, int nsteps, int nb,
+                                                                int64_t m, int64_t n, double fill, double value, int j,
+                                                                accbpg_fw_div_step* __restrict__ steps) {
+    const int a = blockIdx.y, i = da.idx[a];
+    FwDivRunSlot* sl = runs + i;
+    if (fw_run_stop(&sl->run)) return;
+    reduce_final_body<FB, 1, false>(fw_div_u2part_of(dtab[i].ws, n), nb, sl->rec + 8);
+    if (threadIdx.x != 0) return;
+    const FwDivRunArgs ra{mode, da.gamma[a], da.ls_ratio[a], da.epsilon[a], n, nsteps};
+    fw_div_run_decide(sl, ra, m, fill, value, sl->k0 + j, j, steps + (size_t)i * ACCBPG_FW_RUN_MAX);
+}
+__global__ __launch_bounds__(FB) void fw_div_xupdate_brun_kernel(const FwInst* __restrict__ tab,
+                                                                const FwDivRunSlot* __restrict__ runs, BatchAct act,
+                                                                int64_t n, double fill, double value) {
+    const int i = act.idx[blockIdx.y];
+    const FwRun r = runs[i].run;
+    if (r.stop) return;
+    fw_div_xupdate_body(tab[i].x, n, r.p, r.xscale, fill, value);
+}
+// w <- (w + hcoef u^2) / hdiv from the kept u (one "split") with stage 1 of the next probe, as accbpg_fw_div_apply
+__global__ __launch_bounds__(FB) void fw_div_wupdate_probe_brun_kernel(const FwInst* __restrict__ tab,
+                                                                      const FwDivInst* __restrict__ dtab,
+                                                                      const FwDivRunSlot* __restrict__ runs,
+                                                                      BatchAct act, int64_t m, int64_t n) {
+    const int i = act.idx[blockIdx.y];
+    const FwRun r = runs[i].run;
+    if (r.stop) return;
+    const FwInst t = tab[i];
+    fw_wupdate_probe_body(t.w, n, dtab[i].ws, 1, r.hcoef, r.hdiv, t.x, 0, fw_part_of(t, m));
+}
+// what a launch of the family carries by value at most, inside the 4 KiB of kernel arguments at K = ACCBPG_BATCH_MAX
+static_assert(sizeof(FwDivInitArgs) + 128 <= 4096 && sizeof(FwDivDecideArgs) + 128 <= 4096 &&
+              sizeof(FwProbeArgs) + 128 <= 4096, "batched div-run kernel arguments");
 
 // The active instances of a batch in lock-step (accbpg_dopt_batch_fw_div_probe / _fw_div_apply), by the convention of
 // the step kernels above: blockIdx.y is the position among the active instances, blockIdx.x and gridDim.x are the single
@@ -1515,6 +1628,9 @@ static int fw_div_run_alloc(accbpg_dopt* h) {
         ACC_HIP(acc_malloc(reinterpret_cast<void**>(&h->fw_div_run), sizeof(FwDivRunSlot), "fw_div_run"));
     return ACCBPG_OK;
 }
+static const accbpg_fw_div_step* fw_div_steps_harvest(accbpg_dopt* h, const accbpg_fw_div_step* pinned, int nsteps,
+                                                      bool classical, int64_t pending, unsigned wb,
+                                                      accbpg_fw_div_step* steps_host, int* nrun_host);
 
 extern "C" int accbpg_fw_div_run(accbpg_dopt* h, double fill, double value, const accbpg_fw_div_params* prm, int nsteps,
                                  accbpg_fw_div_step* steps_host, int* nrun_host) {
@@ -1584,7 +1700,29 @@ extern "C" int accbpg_fw_div_run(accbpg_dopt* h, double fill, double value, cons
     }
     ACC_HIP(hipGetLastError());
     ACC_HIP(hipStreamSynchronize(s));
-    // copy the row out; leave on the handle what the step-by-step entries would have left where the call ended
+    const accbpg_fw_div_step* bad = fw_div_steps_harvest(h, pinned, nsteps, classical, pending, g.wb, steps_host, nrun_host);
+    if (bad) {
+        set_last_error("accbpg_fw_div_probe_step: pivot index %lld outside [0, n)", (long long)bad->probe.i);
+        return ACCBPG_ERR_ARG;
+    }
+    return ACCBPG_OK;
+}
+
+// a row of pinned records before a run: "not reached"
+static void fw_div_steps_reset(accbpg_fw_div_step* row, int nsteps) {
+    for (int k = 0; k < nsteps; ++k) {
+        row[k] = accbpg_fw_div_step{};
+        row[k].probe.i = -1;
+        row[k].status = FWD_NOT_RUN;
+    }
+}
+// ... and after it: copy the row out, count the records that ran and leave on the handle what the step-by-step entries
+// would have left where the call ended (`pending`: the handle's fw_div_i when the call started).  Returns the first
+// record whose pivot lay outside [0, n).
+static const accbpg_fw_div_step* fw_div_steps_harvest(accbpg_dopt* h, const accbpg_fw_div_step* pinned, int nsteps,
+                                                      bool classical, int64_t pending, unsigned wb,
+                                                      accbpg_fw_div_step* steps_host, int* nrun_host) {
+    const int64_t n = h->n;
     int nrun = 0, last = -1;                                    // last: the last record behind which the state moved
     const accbpg_fw_div_step* bad = nullptr;
     for (int k = 0; k < nsteps; ++k) {
@@ -1609,14 +1747,10 @@ extern "C" int accbpg_fw_div_run(accbpg_dopt* h, double fill, double value, cons
             pin[1] = r.probe.w_i; pin[2] = r.probe.x_i; pin[3] = r.probe.sum_w; pin[4] = r.probe.sum_w2;
             pin[5] = r.probe.slope; pin[6] = r.probe.div; pin[7] = r.probe.min_x; pin[8] = r.probe.sum_u2;
         } else {
-            h->fw_part_nblk = (int)g.wb;                        // the stage-1 records of the last update of w
+            h->fw_part_nblk = (int)wb;                          // the stage-1 records of the last update of w
         }
     }
-    if (bad) {
-        set_last_error("accbpg_fw_div_probe_step: pivot index %lld outside [0, n)", (long long)bad->probe.i);
-        return ACCBPG_ERR_ARG;
-    }
-    return ACCBPG_OK;
+    return bad;
 }
 
 extern "C" int accbpg_fw_set_state(accbpg_dopt* h, const double* x_dev, const double* w_dev, const double* H_dev) {
@@ -1962,6 +2096,135 @@ extern "C" int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const do
         return ACCBPG_ERR_ARG;
     }
     return ACCBPG_OK;
+}
+
+// ---- several Bregman-step iterations per synchronisation for the active instances (accbpg_dopt_batch_fw_div_run) --
+static int fw_div_batch_run_alloc(accbpg_dopt_batch* b) {
+    if (!b->fw_div_bsteps_pin) {
+        ACC_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->fw_div_bsteps_pin),
+                              sizeof(accbpg_fw_div_step) * ACCBPG_FW_RUN_MAX * (size_t)b->K, hipHostMallocDefault));
+        ACC_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->fw_div_bsteps_dev), b->fw_div_bsteps_pin, 0));
+    }
+    if (!b->fw_div_runs)
+        ACC_HIP(acc_malloc(reinterpret_cast<void**>(&b->fw_div_runs), sizeof(FwDivRunSlot) * (size_t)b->K, "fw_div_runs"));
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_dopt_batch_fw_div_run(accbpg_dopt_batch* b, double fill, double value,
+                                            const accbpg_fw_div_params* prm_host, int nsteps, const int* active_host,
+                                            accbpg_fw_div_step* steps_host, int* nrun_host) {
+    if (!b || !prm_host || !steps_host || !nrun_host || nsteps < 1 || nsteps > ACCBPG_FW_RUN_MAX) return ACCBPG_ERR_ARG;
+    accbpg_dopt* h0 = b->inst[0];                               // one shape, one device: every instance's own partition
+    const FwGrids g = fw_grids(h0->m, h0->n, h0->num_cu);
+    const int64_t m = h0->m, n = h0->n, ldv = h0->ldv;
+    FwProbeArgs pa;                                             // the active set, and each instance's nblk at iteration 0
+    BatchAct act, fresh;
+    FwDivInitArgs ia;
+    FwDivDecideArgs da;
+    int mode = -1;
+    for (int i = 0; i < b->K; ++i) {                            // (every refusal below: nothing has been launched)
+        if (active_host && !active_host[i]) continue;
+        const accbpg_dopt* h = b->inst[i];
+        const accbpg_fw_div_params& p = prm_host[i];
+        if (!h->fw_ready || !b->fw_table) {
+            set_last_error("accbpg_dopt_batch_fw_div_run: instance %d has no Frank-Wolfe state (accbpg_dopt_batch_fw_init)", i);
+            return ACCBPG_ERR_ARG;
+        }
+        if (p.mode < FWD_LINESEARCH || p.mode > FWD_CLASSICAL || (mode >= 0 && p.mode != mode)) {
+            set_last_error("accbpg_dopt_batch_fw_div_run: instance %d: mode %d (one mode of 0, 1, 2 for all active instances)",
+                           i, (int)p.mode);
+            return ACCBPG_ERR_ARG;
+        }
+        mode = p.mode;
+        if (mode == FWD_CLASSICAL && (h->fw_div_i < 0 || h->fw_part_nblk != 0 || p.k0 < 1)) {
+            set_last_error("accbpg_dopt_batch_fw_div_run: instance %d: the classical step needs a div probe pending on this "
+                           "state, and k0 >= 1", i);
+            return ACCBPG_ERR_ARG;
+        }
+        const int a = pa.n++;
+        pa.idx[a] = act.idx[a] = ia.idx[a] = da.idx[a] = i;
+        ia.k0[a] = p.k0; ia.L[a] = p.L; ia.ld[a] = p.ld; ia.q[a] = p.q; ia.F_prev[a] = p.F_prev;
+        da.gamma[a] = p.gamma; da.ls_ratio[a] = p.ls_ratio; da.epsilon[a] = p.epsilon;
+    }
+    if (pa.n == 0) return ACCBPG_OK;
+    act.n = ia.n = da.n = pa.n;
+    const bool classical = mode == FWD_CLASSICAL;
+    ACC_TRY(fw_div_batch_table(b));
+    ACC_TRY(fw_div_batch_run_alloc(b));
+    int64_t pending[BATCH_MAX];
+    for (int a = 0; a < pa.n; ++a) {                            // (nothing of an earlier call is in flight: it synchronised)
+        accbpg_dopt* h = b->inst[pa.idx[a]];
+        fw_div_steps_reset(b->fw_div_bsteps_pin + (size_t)pa.idx[a] * ACCBPG_FW_RUN_MAX, nsteps);
+        pending[a] = h->fw_div_i;
+        pa.nblk[a] = (int)g.wb;
+        if (!classical) {
+            pa.nblk[a] = fw_part_waiting(h, 0);                 // stage 1 came with the last update of w
+            if (!pa.nblk[a]) {
+                pa.nblk[a] = (int)g.nblk;
+                fresh.idx[fresh.n++] = pa.idx[a];
+            }
+        }
+        h->fw_part_nblk = 0;                                    // (no claim survives an error return below)
+        h->fw_part_away = false;
+        h->fw_div_i = -1;
+    }
+    const unsigned na = (unsigned)pa.n;
+    const unsigned nb = (unsigned)red_blocks(n, FW_DIV_CAP);
+    hipStream_t s = b->stream;
+    const FwInst* tab = b->fw_table;
+    const FwDivInst* dtab = b->fw_div_table;
+    FwDivRunSlot* runs = b->fw_div_runs;
+    accbpg_fw_div_step* steps = b->fw_div_bsteps_dev;
+    if (fresh.n > 0) fw_probe_partial_batch_kernel<<<dim3(g.nblk, (unsigned)fresh.n), FB, 0, s>>>(tab, fresh, m, n, 0);
+    fw_div_brun_init_kernel<<<1, BATCH_MAX, 0, s>>>(runs, dtab, ia, mode, m, n, fill, value, steps);
+    for (int j = 0; j < nsteps; ++j) {
+        if (classical) {                                        // apply step k, then the probe behind it
+            fw_div_xupdate_brun_kernel<<<dim3(g.gb, na), FB, 0, s>>>(tab, runs, act, n, fill, value);
+            fw_rank1_brun_kernel<<<dim3(g.rb, na), FB, 0, s>>>(tab, runs, act, m);
+            fw_div_wupdate_probe_brun_kernel<<<dim3(g.wb, na), FB, 0, s>>>(tab, dtab, runs, act, m, n);
+        }
+        fw_div_probe_partial_brun_kernel<<<dim3(nb, na), FB, 0, s>>>(tab, dtab, runs, pa, m, n, fill, value);
+        fw_div_probe_final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(tab, dtab, runs, act, (int)nb, ldv, m, n);
+        fw_gemv_h_brun_kernel<<<dim3(g.hb, na), FB, 0, s>>>(tab, runs, act, m);
+        fw_vgemv_partial_brun_kernel<<<dim3(g.vgx, (unsigned)g.ns, na), FB, 0, s>>>(tab, runs, act, ldv, m, n, g.ns);
+        fw_div_usum_brun_kernel<<<dim3(nb, na), FB, 0, s>>>(tab, dtab, runs, act, g.ns, n);
+        fw_div_u2final_brun_kernel<<<dim3(1, na), FB, 0, s>>>(dtab, runs, da, mode, nsteps, (int)nb, m, n, fill, value, j,
+                                                              steps);
+        if (!classical) {                                       // the step the record describes
+            fw_div_xupdate_brun_kernel<<<dim3(g.gb, na), FB, 0, s>>>(tab, runs, act, n, fill, value);
+            fw_rank1_brun_kernel<<<dim3(g.rb, na), FB, 0, s>>>(tab, runs, act, m);
+            fw_div_wupdate_probe_brun_kernel<<<dim3(g.wb, na), FB, 0, s>>>(tab, dtab, runs, act, m, n);
+            if (j == 0)
+                for (int a = 0; a < pa.n; ++a) pa.nblk[a] = (int)g.wb;   // the next probe's stage 1 came with this update
+        }
+    }
+    const hipError_t launched = hipGetLastError();
+    ACC_HIP(hipStreamSynchronize(s));                           // (also behind a launch error: nothing stays in flight)
+    ACC_HIP(launched);
+    int bad_inst = -1;
+    long long bad_p = 0;
+    for (int a = 0; a < pa.n; ++a) {
+        const int i = pa.idx[a];
+        const size_t row = (size_t)i * ACCBPG_FW_RUN_MAX;
+        const accbpg_fw_div_step* bad = fw_div_steps_harvest(b->inst[i], b->fw_div_bsteps_pin + row, nsteps, classical,
+                                                             pending[a], g.wb, steps_host + row, nrun_host + i);
+        if (bad && bad_inst < 0) {
+            bad_inst = i;
+            bad_p = (long long)bad->probe.i;
+        }
+    }
+    if (bad_inst >= 0) {
+        set_last_error("accbpg_dopt_batch_fw_div_run: instance %d: pivot index %lld outside [0, n)", bad_inst, bad_p);
+        return ACCBPG_ERR_ARG;
+    }
+    return ACCBPG_OK;
+}
+
+// the host's replay of one instance's records (fw_div_replay.hpp): no stream, no device call
+extern "C" int accbpg_fw_div_replay(const accbpg_fw_div_params* prm, int64_t n, int64_t m, double fill, double value,
+                                    const accbpg_fw_div_step* steps, int nrun, double* F_out, double* L_or_alpha_out,
+                                    accbpg_fw_div_params* book_out, int* agreed_out, int* verdict_out) {
+    return fw_div_replay(prm, n, m, fill, value, steps, nrun, F_out, L_or_alpha_out, book_out, agreed_out, verdict_out);
 }
 
 namespace accbpg {

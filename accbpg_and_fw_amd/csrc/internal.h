@@ -184,10 +184,26 @@ struct FwRunSlot {
 // xscale carries the step length a; run.stop != 0: every later kernel of the call returns at once; run.pad != 0: the stop
 // test held with an applied step -- the kernels of that apply still run, the final stage of the next probe turns it into
 // stop.  book and L are the predictor's (fw_div_decide.hpp), rec the scratch probe record laid out as the pinned one.
+// A batch (accbpg_dopt_batch_fw_div_run) owns K of these, entry i = instance i; k0 is that instance's iteration number
+// at the start of the call (the instances of a batch drift apart), unused on a single handle.
 struct FwDivRunSlot {
     FwRun run;
     double ld, q, F_prev, L;
     double rec[16];
+    int64_t k0;
+};
+// What a batched Bregman-step run carries by value: the slot of every active instance at the start of the call (the
+// one-thread-per-instance init kernel), and what its decisions read in every iteration (the last stage of the probe)
+struct FwDivInitArgs {
+    int n = 0;
+    int idx[BATCH_MAX] = {};
+    int64_t k0[BATCH_MAX] = {};
+    double L[BATCH_MAX] = {}, ld[BATCH_MAX] = {}, q[BATCH_MAX] = {}, F_prev[BATCH_MAX] = {};
+};
+struct FwDivDecideArgs {
+    int n = 0;
+    int idx[BATCH_MAX] = {};
+    double gamma[BATCH_MAX] = {}, ls_ratio[BATCH_MAX] = {}, epsilon[BATCH_MAX] = {};
 };
 
 struct CholInst {                                  // one factorisation (one entry per instance of a batched launch)
@@ -377,6 +393,11 @@ struct accbpg_dopt_batch {
     accbpg::FwRunSlot* fw_runs = nullptr;
     accbpg_fw_step* fw_bsteps_pin = nullptr;
     accbpg_fw_step* fw_bsteps_dev = nullptr;    // ... as the device addresses them
+    // accbpg_dopt_batch_fw_div_run (allocated by the first call): every instance's predictor slot on the device, and the
+    // records of a call in pinned host memory, row i (ACCBPG_FW_RUN_MAX records) = instance i
+    accbpg::FwDivRunSlot* fw_div_runs = nullptr;
+    accbpg_fw_div_step* fw_div_bsteps_pin = nullptr;
+    accbpg_fw_div_step* fw_div_bsteps_dev = nullptr;    // ... as the device addresses them
     // the evaluation in flight between _begin and _end
     accbpg::BatchAct pend_act;
     const double* pend_x = nullptr;

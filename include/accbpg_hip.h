@@ -545,6 +545,48 @@ int accbpg_dopt_batch_fw_div_apply(accbpg_dopt_batch* b, const int* active_host,
 int accbpg_dopt_batch_fw_run(accbpg_dopt_batch* b, int away, const double* eps_host, int nsteps, const int* active_host,
                              accbpg_fw_step* steps_host, int* nrun_host);
 
+/* accbpg_fw_div_run for the active instances of a batch in lock-step: ONE launch per step kernel covers the active
+ * instances (active_host[i] != 0; NULL = all; the set is fixed for the call), every instance's decisions are predicted
+ * on the device from its own slot, and ONE synchronisation returns all records.  One C loop of plain launches on the
+ * batch's stream.  prm_host and nrun_host have K entries, steps_host K * ACCBPG_FW_RUN_MAX: row i (the first nsteps of
+ * its ACCBPG_FW_RUN_MAX records) belongs to instance i; entries and rows of inactive instances are neither read nor
+ * written.  prm_host[i] carries instance i's own k0, L, gamma, ls_ratio, epsilon, ld, q and F_prev (instances drift
+ * apart after a roll-back or a hand-back; the decisions read k only in k > 0 and in 2 / (k + 2)); fill and value are
+ * shared.  mode must be the same on every active instance, and in mode 2 every active instance needs its div probe
+ * pending and k0 >= 1, as accbpg_fw_div_run does; so must every active instance have Frank-Wolfe state, and
+ * 1 <= nsteps <= ACCBPG_FW_RUN_MAX: ACCBPG_ERR_ARG otherwise, before anything is launched -- no instance moves.
+ * An instance that stops or is handed back in mid-call idles through the rest of the call while the others go on: its
+ * workgroups return before they touch x, w, H, u, the stage-1 records or the pending pivot, and its later records read
+ * status 3.  Grids, the 512-block cap, the row split and the fixed summation tree of every instance are the single
+ * handle's, so x, w, H and the records of instance i are bit for bit those of accbpg_fw_div_run(
+ * accbpg_dopt_batch_instance(b, i), fill, value, prm_host + i, nsteps, ...), and what the call leaves on the handle
+ * (stage-1 records, pending pivot, pinned probe record) is what that call leaves: it mixes freely with
+ * accbpg_fw_div_run, accbpg_fw_div_probe_step / accbpg_fw_div_apply on the instance handles and the other
+ * accbpg_dopt_batch_fw_* calls.  A record whose pivot lies outside [0, n) on any instance makes the call return
+ * ACCBPG_ERR_ARG with the (first such) instance named in the message; all records are filled in all the same and the
+ * other instances' records are valid.  Scratch is allocated by the first call and freed by accbpg_dopt_batch_destroy. */
+int accbpg_dopt_batch_fw_div_run(accbpg_dopt_batch* b, double fill, double value, const accbpg_fw_div_params* prm_host,
+                                 int nsteps, const int* active_host, accbpg_fw_div_step* steps_host, int* nrun_host);
+
+/* The host's replay of one instance's records of accbpg_fw_div_run / accbpg_dopt_batch_fw_div_run
+ * (csrc/fw_div_replay.hpp): a pure host function -- no stream, no device call, callable with no GPU present.  From the
+ * caller's book (prm: mode, k0, L, gamma, ls_ratio, epsilon, ld, q, F_prev; n, m, fill, value) it walks the records with
+ * the host's libm: per record it copies the book, takes the host's decision on the record's probe, compares it with the
+ * record bit for bit (NaN equal to NaN) -- modes 0 and 1: (a, hcoef, hdiv, L, status); mode 2: (a, hcoef, hdiv), then
+ * the stop test -- and commits the book only if they agree.  It stops at the first record that is not an agreed step:
+ *   *verdict_out: 0 end of records; 1 agreed stop (that record is counted in *agreed_out); 2 the device handed the
+ *   iteration back; 3 the host's decision is itself a hand-back (the cap, an arithmetic error); 4 disagreement;
+ *   5 pivot outside [0, n).
+ * It decides nothing about that record: *book_out is the book BEFORE record *agreed_out (k0 advanced by *agreed_out),
+ * for the caller to decide it.  F_out[j] <- F[k0 + j] and L_or_alpha_out[j] <- the accepted L (modes 0, 1) or the step
+ * length (mode 2) of the agreed records.
+ * steps: modes 0 and 1, the nrun records of the call.  Mode 2: nrun + 1 entries -- steps[0].probe is the probe that was
+ * pending when the call started (nothing else of steps[0] is read: the step of a record is decided from the probe of the
+ * record before it), steps[1 .. nrun] are the records.  0 <= nrun <= ACCBPG_FW_RUN_MAX. */
+int accbpg_fw_div_replay(const accbpg_fw_div_params* prm, int64_t n, int64_t m, double fill, double value,
+                         const accbpg_fw_div_step* steps, int nrun, double* F_out, double* L_or_alpha_out,
+                         accbpg_fw_div_params* book_out, int* agreed_out, int* verdict_out);
+
 /* accbpg_dopt_kyinit for all K instances of a batch in lock-step on the batch's stream: every launch of a step covers
  * the K instances (8 launches per step, 4 at step 0, whatever K is), all m steps are enqueued, one copy returns the
  * indices and the host waits once.

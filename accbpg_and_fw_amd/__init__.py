@@ -27,7 +27,8 @@ from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, D_opt_KYini
                            Poisson_regr_simplex_acc, svm_digits_ds_divs_ball)
 from .utils import (load_libsvm_file, random_point_on_simplex, edge_point_on_simplex, get_random_float,
                     get_random_vector, random_point_in_l2_ball, generate_dataset_for_svm)
-from .batched import DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, solve_batch, solve_instances
+from .batched import (DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, ABPG_expo_batch, ABPG_expo_batch_steps,
+                      ABDA_batch, ABDA_batch_steps, solve_batch, solve_instances)
 
 __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunction", "BurgEntropy",
            "BurgEntropyL1", "BurgEntropyL2", "BurgEntropySimplex", "Poisson_regrL1", "Poisson_regrL2",
@@ -44,5 +45,6 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "D_opt_KYinit_batch", "D_opt_FW_div_step", "D_opt_FW_descent_step", "D_opt_FW_div_step_batch",
            "D_opt_FW_descent_step_batch", "D_opt_FW_div_step_device", "D_opt_FW_descent_step_device",
            "D_opt_FW_div_step_batch_device", "D_opt_FW_descent_step_batch_device", "SVM_fun",
-           "PolyDiv", "svm_digits_ds_divs_ball", "random_point_in_l2_ball", "generate_dataset_for_svm"]
+           "PolyDiv", "svm_digits_ds_divs_ball", "random_point_in_l2_ball", "generate_dataset_for_svm",
+           "ABPG_expo_batch", "ABPG_expo_batch_steps", "ABDA_batch", "ABDA_batch_steps"]
 __version__ = "0.1.0"

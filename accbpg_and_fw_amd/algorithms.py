@@ -23,7 +23,8 @@ from .functions import (BurgEntropy, BurgEntropySimplex, DOptimalObj, PolyDiv, S
                         SumOf2nd4thPowers,
                         combine_ls_terms, from_dev, ls_terms, shannon_ls_terms, to_dev, vec_axpby, vec_div_scalar,
                         vec_dot_diff)
-from .solver_runs import ACCEPT, BREAK, NEEDS_VALUE, _ABPGRun, _BPGRun, _GainRun, next_theta, solve_theta  # noqa: F401
+from .solver_runs import (ACCEPT, BREAK, NEEDS_VALUE, _ABDARun, _ABPGRun, _BPGRun, _ExpoRun, _GainRun,  # noqa: F401
+                          next_theta, solve_theta)
 from .utils import get_random_float
 
 
@@ -356,64 +357,42 @@ def ABPG_expo_steps(f, h, L, x0, gamma0, maxitrs, epsilon=1e-14, delta=0.2,
               "        TSG       D(x+,y)     D(z+,z)     time")
 
     t_start = time.time()
-    F = np.zeros(maxitrs)
-    G = np.zeros(maxitrs)
-    Gamma = np.ones(maxitrs) * gamma0
-    T = np.zeros(maxitrs)
+    run = _ExpoRun(L, gamma0, maxitrs, epsilon, delta, theta_eq, checkdiv, Gmargin, restart, restart_rule)
 
-    gamma = gamma0
     x, as_numpy = to_dev(x0)
     x = x.clone()
     z = x.clone()
-    theta = 1.0
-    kk = 0
-    k = -1
     for k in range(maxitrs):
-        F[k] = f(x) + h.extra_Psi(x)                            # :231-232
-        T[k] = time.time() - t_start
-
+        Fk = f(x) + h.extra_Psi(x)                              # :231-232
         z_prev, x_prev = z, x
-        theta = next_theta(theta, kk, gamma, theta_eq)          # :238-241
+        theta = run.begin(k)                                    # :238-241
+        run.record(Fk, time.time() - t_start)
 
         y = vec_axpby(1 - theta, x_prev, theta, z_prev)         # :243
         fy, g = f.func_grad(y)                                  # :245
 
-        trying = True
-        while trying:                                           # :248
-            z = h.div_prox_map(z_prev, g, theta ** (gamma - 1) * L)   # :249
+        while True:                                             # :248
+            z = h.div_prox_map(z_prev, g, run.prox_coef())      # :249
             x = vec_axpby(1 - theta, x_prev, theta, z)          # :250
             lin, dxy, dzz = _divergences(h, g, x, y, z, z_prev)  # :253-254 and the dot of :260
-            Gdr = dxy / dzz / theta ** gamma                    # :255
+            verdict = run.divergences(lin, dxy, dzz)            # :255-258
+            if verdict == NEEDS_VALUE:
+                verdict = run.value(f(x), fy)                   # :260
+            if verdict == ACCEPT:                               # :262-265
+                break
 
-            if checkdiv:
-                trying = (dxy > Gmargin * (theta ** gamma) * dzz)    # :258
-            else:
-                trying = (f(x) > fy + lin + theta ** gamma * L * dzz)   # :260
-
-            if trying and gamma > 1:                            # :262-265
-                gamma = max(gamma - delta, 1)
-            else:
-                trying = False
-
-        G[k] = Gdr
-        Gamma[k] = gamma
+        restarted, stop = run.finish(vec_dot_diff(g, x, x_prev) if run.needs_dot() else None)   # :267-282
         if verbose and k % verbskip == 0:
             print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:10.3e}  {4:10.3e}  {5:10.3e}  {6:10.3e}  {7:6.1f}".format(
-                k, F[k], theta, gamma, Gdr, dxy, dzz, T[k]))
+                k, run.F[k], theta, run.gamma, run.Gdr, dxy, dzz, run.T[k]))
+        if restarted:
+            z = x
 
-        kk += 1
-        if restart:                                             # :276-282
-            if (restart_rule == 'f' and F[k] > F[k - 1]) or \
-               (restart_rule == 'g' and vec_dot_diff(g, x, x_prev) > 0):
-                theta = 1.0
-                kk = 0
-                z = x
-
-        if dzz < epsilon:                                       # :285
+        if stop:                                                # :285
             break
         yield k
 
-    return from_dev(x, as_numpy), F[0:k + 1], Gamma[0:k + 1], G[0:k + 1], T[0:k + 1]
+    return run.result(from_dev(x, as_numpy))
 
 
 def ABDA(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, theta_eq=True,
@@ -432,47 +411,37 @@ def ABDA_steps(f, h, L, x0, gamma, maxitrs, epsilon=1e-14, theta_eq=True,
               "        TSG       D(x+,y)     D(z+,z)     time")
 
     t_start = time.time()
-    F = np.zeros(maxitrs)
-    G = np.zeros(maxitrs)
-    T = np.zeros(maxitrs)
+    run = _ABDARun(L, gamma, maxitrs, epsilon, theta_eq)
 
     x, as_numpy = to_dev(x0)
     x = x.clone()
     z = x.clone()
-    theta = 1.0
-    kk = 0
     gavg = torch.zeros_like(x)
-    csum = 0
-    k = -1
     for k in range(maxitrs):
-        F[k] = f(x) + h.extra_Psi(x)                            # :465-466
-        T[k] = time.time() - t_start
-
+        Fk = f(x) + h.extra_Psi(x)                              # :465-466
         z_prev, x_prev = z, x
-        theta = next_theta(theta, kk, gamma, theta_eq)          # :472-475
+        theta = run.begin(k)                                    # :472-475
+        run.record(Fk, time.time() - t_start)
 
         y = vec_axpby(1 - theta, x_prev, theta, z_prev)         # :477
         g = f.gradient(y)                                       # :478
-        wgt = theta ** (1 - gamma)
+        wgt, csum, Lc = run.weight()                            # :480
         gavg = vec_axpby(1.0, gavg, wgt, g)                     # :479  (1.0*gavg is exact)
-        csum = csum + wgt                                       # :480
-        z = h.prox_map(vec_div_scalar(gavg, csum), L / csum)    # :481
+        z = h.prox_map(vec_div_scalar(gavg, csum), Lc)          # :481
         x = vec_axpby(1 - theta, x_prev, theta, z)              # :482
 
         _, dxy, dzz = _divergences(h, None, x, y, z, z_prev)    # :485-486
-        Gdr = dxy / dzz / theta ** gamma
-
-        G[k] = Gdr
+        Gdr = run.divergences(dxy, dzz)
         if verbose and k % verbskip == 0:
             print("{0:6d}  {1:10.3e}  {2:10.3e}  {3:10.3e}  {4:10.3e}  {5:10.3e}  {6:6.1f}".format(
-                k, F[k], theta, Gdr, dxy, dzz, T[k]))
+                k, run.F[k], theta, Gdr, dxy, dzz, run.T[k]))
 
-        kk += 1
-        if dzz < epsilon:                                       # :508
+        _, stop = run.finish()
+        if stop:                                                # :508
             break
         yield k
 
-    return from_dev(x, as_numpy), F[0:k + 1], G[0:k + 1], T[0:k + 1]
+    return run.result(from_dev(x, as_numpy))
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from .algorithms import _drain
 from .functions import DOptimalObj, _ptr, _stream, from_dev, to_dev
-from .solver_runs import NEEDS_VALUE, RETRY, _ABPGRun, _BPGRun, _GainRun
+from .solver_runs import NEEDS_VALUE, RETRY, _ABDARun, _ABPGRun, _BPGRun, _ExpoRun, _GainRun
 
 
 class _FwDivRecords:
@@ -254,6 +254,35 @@ class DOptimalBatch:
         _lib.check(rc, "accbpg_dopt_batch_burg_simplex_div_prox")
         self._raise(st, idx, "accbpg_dopt_batch_burg_simplex_div_prox", "Either y or L is not positive.")
         return out
+
+    def avg_prox(self, Gavg, G, wgt, csum, Lc, eps, active=None, out_avg=None, out=None, info=False):
+        """ABDA's dual-averaging step (accbpg/algorithms.py:483-485), one launch for the active instances.  Returns
+        (Gavg_new, Z): row i of Gavg_new = Gavg[i] + wgt[i] * G[i], row i of Z =
+        BurgEntropySimplex(eps).prox_map(Gavg_new[i] / csum[i], Lc[i]) -- bit for bit ``vec_axpby(1.0, Gavg[i], wgt[i],
+        G[i])``, ``vec_div_scalar`` and ``prox_map`` in a row.  Lc[i] is L / csum[i] as the caller computed it.  Only the
+        rows of the active instances are written (`out_avg`, `out`: existing K x n tensors for them; `out_avg` must not be
+        Gavg).  Nothing is read back, unless `info` asks for ``self.last_info[i]`` = (bisection steps, Newton steps) of
+        the active instances i."""
+        self._rows(Gavg=Gavg, G=G, out_avg=out_avg, out=out)
+        if out_avg is not None and (out_avg is Gavg or out_avg.data_ptr() == Gavg.data_ptr()):
+            raise ValueError("DOptimalBatch.avg_prox: out_avg must not be Gavg (the sum is read and written in one pass)")
+        mask, idx = self._mask(active)
+        vals = [(C.c_double * self.K)(*[float(v) for v in seq]) for seq in (wgt, csum, Lc)]
+        st = (C.c_int * self.K)()
+        steps = (C.c_int * (2 * self.K))() if info else None
+        new = lambda: torch.empty(self.K, self.n, dtype=torch.float64, device=self.device)
+        out_avg = new() if out_avg is None else out_avg
+        out = new() if out is None else out
+        with torch.cuda.device(self.device):
+            self._lib.accbpg_dopt_batch_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_dopt_batch_burg_simplex_avg_prox(self._h, _ptr(Gavg), _ptr(G), self.n, vals[0], vals[1],
+                                                                   vals[2], float(eps), _ptr(out_avg), _ptr(out), mask, st,
+                                                                   steps)
+        _lib.check(rc, "accbpg_dopt_batch_burg_simplex_avg_prox")
+        self._raise(st, idx, "accbpg_dopt_batch_burg_simplex_avg_prox", "BergEntropySimplex prox_map only takes positive L.")
+        if info:
+            self.last_info = {i: (steps[2 * i], steps[2 * i + 1]) for i in idx}
+        return out_avg, out
 
     def ls_terms(self, G, X, Y, Z=None, Z1=None, active=None):
         """K x 3 NumPy array: (<g, x-y>, D(x,y), D(z,z1)) per instance."""
@@ -812,3 +841,128 @@ def ABPG_gain_batch_steps(batch, h, L, x0, gamma, maxitrs, epsilon=1e-14, G0=1, 
 def ABPG_gain_batch(batch, h, L, x0, gamma, maxitrs, **kwargs):
     """Drain ``ABPG_gain_batch_steps``: list of (x, F, Gain, Gdiv, Gavg, T), one per instance."""
     return _drain(ABPG_gain_batch_steps(batch, h, L, x0, gamma, maxitrs, **kwargs))
+
+
+def ABPG_expo_batch_steps(batch, h, L, x0, gamma0, maxitrs, epsilon=1e-14, delta=0.2, theta_eq=True, checkdiv=False,
+                          Gmargin=10, restart=False, restart_rule='g', overlap=True):
+    """ABPG_expo (accbpg/algorithms.py:183-292) on the K instances of a ``DOptimalBatch`` in lock-step per ORACLE
+    PASS: one evaluation of (f, grad) at y for all running instances per outer iteration (:245), then passes of prox,
+    vector combination, divergences and -- unless `checkdiv` -- a trial value for the instances that are still lowering
+    their exponent; the others have accepted their point and their rows are not touched again in this outer iteration.
+    The exponent, theta, the restart state and the stopping test are kept per instance on the host.  Yields k after
+    every outer iteration; returns, per instance, ABPG_expo's (x, F, Gamma, G, T) -- bit-identical to
+    ``ABPG_expo(batch.instance(i), ...)``.  Where the value test accepted x+ it evaluated f there, and that number is
+    F[k+1] (the same kernel on the same vector: the same bits), so F[k] is evaluated only for the instances that have none
+    -- at k = 0 and with `checkdiv`; with `overlap` (default) on a second stream beside the evaluations at y_i."""
+    K, n = batch.K, batch.n
+    t_start = time.time()
+    X, as_numpy = batch.fw_rows(x0)
+    Z = X.clone()
+    runs = [_ExpoRun(L, gamma0, maxitrs, epsilon, delta, theta_eq, checkdiv, Gmargin, restart, restart_rule)
+            for _ in range(K)]
+    active = [True] * K
+    result_x = [None] * K
+    eps_prox = getattr(h, "eps", 1e-8)
+    new = lambda: torch.empty(K, n, dtype=torch.float64, device=batch.device)
+    carried = [None] * K                        # f at the rows of X that the accepting value test of the last iteration left
+    for k in range(maxitrs):
+        if not any(active):
+            break
+        due = [active[i] and carried[i] is None for i in range(K)]
+        side = overlap and any(due) and not getattr(batch, "_prof", False)   # (kernel timing keeps everything on one stream)
+        ticket = batch.value_async(X, due) if side else None                # :231 (beside the evaluation below)
+        fx = batch.func_grad(X, 0, due) if any(due) and not side else None
+        now = time.time() - t_start
+        running = [i for i in range(K) if active[i]]
+        for i in running:
+            runs[i].begin(k)                                                # :238-241
+        theta = [run.theta for run in runs]
+        one_m = [1 - t for t in theta]
+        Y = batch.axpby(one_m, X, theta, Z, active)                         # :243
+        fy, Gr = batch.func_grad(Y, 2, active)                              # :245
+        if side:
+            fx = batch.value_wait(ticket)
+            now = time.time() - t_start
+        for i in running:
+            runs[i].record((fx[i] if due[i] else carried[i]) + h.extra_Psi(None), now)      # :232
+        carried = [None] * K
+        search = list(active)
+        Zt, Xt = new(), new()                                               # rows are written by the passes that need them
+        while any(search):                                                  # :248, one pass = one trial per searching instance
+            batch.prox(Z, Gr, [run.prox_coef() for run in runs], eps_prox, search, out=Zt)   # :249
+            batch.axpby(one_m, X, theta, Zt, search, out=Xt)                # :250
+            terms = batch.ls_terms(Gr, Xt, Y, Zt, Z, search)                # :253-254 and the dot of :260
+            need_value = [False] * K
+            for i in running:
+                if search[i]:
+                    verdict = runs[i].divergences(*terms[i])                # :255-258
+                    need_value[i] = verdict == NEEDS_VALUE
+                    search[i] = verdict in (NEEDS_VALUE, RETRY)
+            if any(need_value):
+                ft = batch.func_grad(Xt, 0, need_value)                     # :260
+                for i in running:
+                    if need_value[i]:
+                        search[i] = runs[i].value(ft[i], fy[i]) == RETRY    # :262-265
+                        carried[i] = None if search[i] else ft[i]
+        X, Z = Xt, _finish_rows(batch, runs, running, active, result_x, Gr, Xt, X, Zt)     # :267-285
+        yield k
+    return _results(runs, result_x, X, as_numpy)
+
+
+def ABPG_expo_batch(batch, h, L, x0, gamma0, maxitrs, **kwargs):
+    """Drain ``ABPG_expo_batch_steps``: list of (x, F, Gamma, G, T), one per instance."""
+    return _drain(ABPG_expo_batch_steps(batch, h, L, x0, gamma0, maxitrs, **kwargs))
+
+
+def ABDA_batch_steps(batch, h, L, x0, gamma, maxitrs, epsilon=1e-14, theta_eq=True, overlap=True):
+    """ABDA (accbpg/algorithms.py:423-514) on the K instances of a ``DOptimalBatch`` in lock-step: per outer iteration
+    one vector combination for y, one gradient call, one ``avg_prox`` -- the weighted gradient average, its quotient by
+    the sum of the weights and the prox of that in a single launch --, one combination for x and one pass for the
+    divergences, each over all instances that are still running.  The averages ping-pong between two K x n buffers.
+    theta, the sum of the weights and the stopping test are kept per instance on the host.  Yields k after every outer
+    iteration; returns, per instance, ABDA's (x, F, G, T) -- bit-identical to ``ABDA(batch.instance(i), ...)``.  With
+    `overlap` (default) the values F[k] = f(x_i) run on a second stream beside the gradient evaluations at y_i."""
+    K, n = batch.K, batch.n
+    t_start = time.time()
+    X, as_numpy = batch.fw_rows(x0)
+    Z = X.clone()
+    runs = [_ABDARun(L, gamma, maxitrs, epsilon, theta_eq) for _ in range(K)]
+    active = [True] * K
+    result_x = [None] * K
+    eps_prox = getattr(h, "eps", 1e-8)
+    Gavg = torch.zeros(K, n, dtype=torch.float64, device=batch.device)
+    Gavg_next = torch.empty(K, n, dtype=torch.float64, device=batch.device)
+    for k in range(maxitrs):
+        if not any(active):
+            break
+        side = overlap and not getattr(batch, "_prof", False)                # (kernel timing keeps everything on one stream)
+        ticket = batch.value_async(X, active) if side else None             # :465 (beside the gradients below)
+        fx = None if side else batch.func_grad(X, 0, active)
+        now = time.time() - t_start
+        running = [i for i in range(K) if active[i]]
+        for i in running:
+            runs[i].begin(k)                                                # :472-475
+        theta = [run.theta for run in runs]
+        one_m = [1 - t for t in theta]
+        Y = batch.axpby(one_m, X, theta, Z, active)                         # :477
+        Gr = batch.func_grad(Y, 1, active)                                  # :478
+        if side:
+            fx = batch.value_wait(ticket)
+            now = time.time() - t_start
+        for i in running:
+            runs[i].record(fx[i] + h.extra_Psi(None), now)                  # :466
+        wgt, csum, Lc = zip(*[run.weight() if active[i] else (0.0, 1.0, 1.0) for i, run in enumerate(runs)])   # :480
+        _, Zn = batch.avg_prox(Gavg, Gr, wgt, csum, Lc, eps_prox, active, out_avg=Gavg_next)     # :479, :481
+        Gavg, Gavg_next = Gavg_next, Gavg                   # (a stopped instance's row goes stale: it is not read again)
+        Xn = batch.axpby(one_m, X, theta, Zn, active)                       # :482
+        terms = batch.ls_terms(None, Xn, Y, Zn, Z, active)                  # :485-486
+        for i in running:
+            runs[i].divergences(terms[i, 1], terms[i, 2])                   # :491
+        X, Z = Xn, _finish_rows(batch, runs, running, active, result_x, None, Xn, X, Zn)    # :508
+        yield k
+    return _results(runs, result_x, X, as_numpy)
+
+
+def ABDA_batch(batch, h, L, x0, gamma, maxitrs, epsilon=1e-14, theta_eq=True, overlap=True):
+    """Drain ``ABDA_batch_steps``: list of (x, F, G, T), one per instance."""
+    return _drain(ABDA_batch_steps(batch, h, L, x0, gamma, maxitrs, epsilon, theta_eq, overlap))

@@ -11,8 +11,8 @@ extern "C" int accbpg_dopt_batch_destroy(accbpg_dopt_batch* b) {
     if (!b) return ACCBPG_OK;
     for (accbpg_dopt* h : b->inst) accbpg_dopt_destroy(h);
     acc_free(b->table); acc_free(b->chol_table[0]); acc_free(b->chol_table[1]); acc_free(b->ops_all); acc_free(b->red_all);
-    acc_free(b->dscal_all); acc_free(b->vflags); acc_free(b->vout); acc_free(b->vpart); acc_free(b->vws); acc_free(b->fw_table);
-    acc_free(b->fw_runs); acc_free(b->fw_div_table); acc_free(b->fw_div_runs);
+    acc_free(b->dscal_all); acc_free(b->vflags); acc_free(b->vout); acc_free(b->vpart); acc_free(b->vws); acc_free(b->vquot);
+    acc_free(b->fw_table); acc_free(b->fw_runs); acc_free(b->fw_div_table); acc_free(b->fw_div_runs);
     if (b->fw_bsteps_pin) hipHostFree(b->fw_bsteps_pin);
     if (b->fw_div_bsteps_pin) hipHostFree(b->fw_div_bsteps_pin);
     if (b->hpin) hipHostFree(b->hpin);

@@ -385,6 +385,7 @@ struct accbpg_dopt_batch {
     double* vout = nullptr;                 // K * 4 doubles: reduction results
     double* vpart = nullptr;                // K * 4 * 1024 doubles: reduction partials
     double* vws = nullptr;                  // workspace of the single-instance prox (long vectors, one instance at a time)
+    double* vquot = nullptr;                // gavg / csum of one instance (avg_prox on long vectors), n doubles
     double* vpin = nullptr;                 // pinned mirror (K * 8 doubles)
     accbpg::FwInst* fw_table = nullptr;     // device, K entries: Frank-Wolfe state of every instance (built by the first accbpg_dopt_batch_fw_init)
     accbpg::FwDivInst* fw_div_table = nullptr;  // device, K entries: their Bregman-step workspaces (built by the first accbpg_dopt_batch_fw_div_*)

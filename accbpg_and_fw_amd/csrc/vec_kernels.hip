@@ -45,14 +45,18 @@ __device__ __forceinline__ double block_min_bcast(double v, double* sh) {
 
 // Burg simplex prox, functions.py:336-356 (and :264-271 when y != NULL).
 // EPT > 0: gg lives in registers (n <= PB*EPT); EPT == 0: gg is kept in `ggbuf` and re-read.
-// ACC: the argument is xi + alpha*g, formed on load (one product, one sum) and stored to xi_out -- the
+// LOAD_ACC: the argument is xi + alpha*g, formed on load (one product, one sum) and stored to xi_out -- the
 // accumulated gradient of AIBM (algorithms.py:630-631); everything behind the load is the same code.
-template <int EPT, bool ACC = false>
+// LOAD_AVG: the argument is (xi + alpha*g) / csum, the sum stored to xi_out and then divided (one more rounding) -- the
+// weighted gradient average of ABDA and its quotient (algorithms.py:483-485).
+constexpr int LOAD_PLAIN = 0, LOAD_ACC = 1, LOAD_AVG = 2;
+template <int EPT, int LOAD = LOAD_PLAIN>
 __device__ __forceinline__ void burg_prox_body(const double* __restrict__ y, const double* __restrict__ g,
                                                double L, double eps, int64_t n, double* __restrict__ xout,
                                                double* __restrict__ ggbuf, int* __restrict__ info,
                                                int* __restrict__ flags, const double* __restrict__ xi = nullptr,
-                                               double alpha = 0.0, double* __restrict__ xi_out = nullptr) {
+                                               double alpha = 0.0, double* __restrict__ xi_out = nullptr,
+                                               double csum = 1.0) {
     __shared__ double sh[PB / 64];
     const int tid = threadIdx.x;
     constexpr int R = EPT > 0 ? EPT : 1;
@@ -63,11 +67,12 @@ __device__ __forceinline__ void burg_prox_body(const double* __restrict__ y, con
 
     auto make_gg = [&](int64_t i) -> double {
         double a = g[i];
-        if constexpr (ACC) {
-            const double t = alpha * a;       // alpha * grad_x     algorithms.py:630
+        if constexpr (LOAD != LOAD_PLAIN) {
+            const double t = alpha * a;       // alpha * grad_x     algorithms.py:630 (theta^(1-gamma) * g, :483)
             a = xi[i] + t;                    // xi_grad += ...
             xi_out[i] = a;
         }
+        if constexpr (LOAD == LOAD_AVG) a = a / csum;      // gavg / csum      algorithms.py:485
         if (y != nullptr) {
             const double yi = y[i];
             if (!(yi > 0.0)) bad = true;
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(PB) void burg_prox_acc_kernel(const double* __restr
                                                           const double* __restrict__ g, double L, double eps, int64_t n,
                                                           double* __restrict__ xi_out, double* __restrict__ xout,
                                                           int* __restrict__ info, int* __restrict__ flags) {
-    burg_prox_body<EPT, true>(nullptr, g, L, eps, n, xout, nullptr, info, flags, xi, alpha, xi_out);
+    burg_prox_body<EPT, LOAD_ACC>(nullptr, g, L, eps, n, xout, nullptr, info, flags, xi, alpha, xi_out);
 }
 // the prox of every active instance of a batch in one launch: a workgroup per instance (row `instance` of the K x n
 // arrays), its own constant L, its own status words
@@ -179,6 +184,19 @@ __global__ __launch_bounds__(PB) void burg_prox_batch_kernel(BatchAct act, const
     burg_prox_body<EPT>(ybase ? ybase + (int64_t)inst * ld : nullptr, gbase + (int64_t)inst * ld, Ls.v[inst], eps, n,
                         obase + (int64_t)inst * ld, ggbase ? ggbase + (int64_t)inst * n : nullptr, flags + 8 * inst + 4,
                         flags + 8 * inst);
+}
+// ABDA's step of every active instance in one launch: row i of avg_out = avg_i + wgt_i * g_i, row i of obase =
+// prox_map(avg_out_i / csum_i, Lc_i) (n <= PB*EPT)
+template <int EPT>
+__global__ __launch_bounds__(PB) void burg_avg_prox_batch_kernel(BatchAct act, const double* __restrict__ avgbase,
+                                                                const double* __restrict__ gbase, int64_t ld,
+                                                                BatchVals wgt, BatchVals csum, BatchVals Lc, double eps,
+                                                                int64_t n, double* __restrict__ avg_out,
+                                                                double* __restrict__ obase, int* __restrict__ flags) {
+    const int inst = act.idx[blockIdx.x];
+    const int64_t row = (int64_t)inst * ld;
+    burg_prox_body<EPT, LOAD_AVG>(nullptr, gbase + row, Lc.v[inst], eps, n, obase + row, nullptr, flags + 8 * inst + 4,
+                                  flags + 8 * inst, avgbase + row, wgt.v[inst], avg_out + row, csum.v[inst]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -966,6 +984,72 @@ extern "C" int accbpg_dopt_batch_burg_simplex_div_prox(accbpg_dopt_batch* b, con
         const int i = act.idx[a];
         if (pin_i[8 * i + FLAG_NONPOS]) status_host[i] = ACCBPG_ERR_ASSERT;     // y.min() > 0, functions.py:270
         if (info_host) { info_host[2 * i] = pin_i[8 * i + 4]; info_host[2 * i + 1] = pin_i[8 * i + 5]; }
+    }
+    return ACCBPG_OK;
+}
+
+/* ABDA's dual-averaging step for the active instances (algorithms.py:483-485): gavg_out[i] <- gavg[i] + wgt_host[i] * g[i],
+ * z_out[i] <- BurgEntropySimplex.prox_map(gavg_out[i] / csum_host[i], Lc_host[i]), one launch.  status_host[i]:
+ * ACCBPG_OK or ACCBPG_ERR_ASSERT (Lc <= 0; nothing is written for that instance).  info_host (optional, 2 ints per
+ * instance) receives {bisection steps, Newton steps}. */
+extern "C" int accbpg_dopt_batch_burg_simplex_avg_prox(accbpg_dopt_batch* b, const double* gavg_dev, const double* g_dev,
+                                                       int64_t ld, const double* wgt_host, const double* csum_host,
+                                                       const double* Lc_host, double eps, double* gavg_out_dev,
+                                                       double* z_out_dev, const int* active_host, int* status_host,
+                                                       int* info_host) {
+    if (!b || !gavg_dev || !g_dev || !wgt_host || !csum_host || !Lc_host || !gavg_out_dev || !z_out_dev || !status_host ||
+        b->K > BATCH_MAX)
+        return ACCBPG_ERR_ARG;
+    if (gavg_out_dev == gavg_dev || gavg_out_dev == g_dev || z_out_dev == gavg_out_dev || z_out_dev == gavg_dev ||
+        z_out_dev == g_dev)
+        return ACCBPG_ERR_ARG;
+    const int64_t n = b->inst[0]->n;
+    if (ld < n) return ACCBPG_ERR_ARG;
+    ACC_TRY(batch_vec_scratch(b));
+    BatchAct all = batch_active(b, active_host), act;
+    BatchVals wgt, csum, Lc;
+    for (int a = 0; a < all.n; ++a) {                           // functions.py:340: L > 0 is checked before anything runs
+        const int i = all.idx[a];
+        wgt.v[i] = wgt_host[i]; csum.v[i] = csum_host[i]; Lc.v[i] = Lc_host[i];
+        if (!(Lc_host[i] > 0.0)) status_host[i] = ACCBPG_ERR_ASSERT;
+        else { status_host[i] = ACCBPG_OK; act.idx[act.n++] = i; }
+    }
+    if (act.n == 0) return ACCBPG_OK;
+    hipStream_t s = b->stream;
+    if (n > (int64_t)PB * 32) {
+        // Long vectors: as in accbpg_dopt_batch_burg_simplex_div_prox, the multi-workgroup prox of the single instance
+        // has its own order of summation.  Run what the sequential solver runs, instance by instance: the sum, the
+        // quotient (into a scratch row), the prox.
+        if (!b->vws) ACC_HIP(acc_malloc(&b->vws, sizeof(double) * (size_t)vec_ws_doubles(n), "vws"));
+        if (!b->vquot) ACC_HIP(acc_malloc(&b->vquot, sizeof(double) * (size_t)n, "vquot"));
+        for (int a = 0; a < act.n; ++a) {
+            const int i = act.idx[a];
+            const size_t row = (size_t)i * ld;
+            int info[2] = {0, 0};
+            ACC_TRY(accbpg_vec_axpby(1.0, gavg_dev + row, wgt_host[i], g_dev + row, n, gavg_out_dev + row, s));
+            ACC_TRY(accbpg_vec_div_scalar(gavg_out_dev + row, csum_host[i], n, b->vquot, s));
+            ACC_TRY(accbpg_burg_simplex_div_prox(nullptr, b->vquot, Lc_host[i], eps, n, z_out_dev + row, b->vws, info, s));
+            if (info_host) { info_host[2 * i] = info[0]; info_host[2 * i + 1] = info[1]; }
+        }
+        return ACCBPG_OK;
+    }
+    if (n <= (int64_t)PB * 2)
+        burg_avg_prox_batch_kernel<2><<<act.n, PB, 0, s>>>(act, gavg_dev, g_dev, ld, wgt, csum, Lc, eps, n, gavg_out_dev,
+                                                           z_out_dev, b->vflags);
+    else if (n <= (int64_t)PB * 8)
+        burg_avg_prox_batch_kernel<8><<<act.n, PB, 0, s>>>(act, gavg_dev, g_dev, ld, wgt, csum, Lc, eps, n, gavg_out_dev,
+                                                           z_out_dev, b->vflags);
+    else                                                        // n <= PB * 32: longer rows returned above
+        burg_avg_prox_batch_kernel<32><<<act.n, PB, 0, s>>>(act, gavg_dev, g_dev, ld, wgt, csum, Lc, eps, n, gavg_out_dev,
+                                                            z_out_dev, b->vflags);
+    ACC_HIP(hipGetLastError());
+    if (!info_host) return ACCBPG_OK;                           // no y, so no flag can be raised: nothing to wait for
+    int* pin_i = reinterpret_cast<int*>(b->vpin);
+    ACC_HIP(hipMemcpyAsync(pin_i, b->vflags, sizeof(int) * 8 * (size_t)b->K, hipMemcpyDeviceToHost, s));
+    ACC_HIP(hipStreamSynchronize(s));
+    for (int a = 0; a < act.n; ++a) {
+        const int i = act.idx[a];
+        info_host[2 * i] = pin_i[8 * i + 4]; info_host[2 * i + 1] = pin_i[8 * i + 5];
     }
     return ACCBPG_OK;
 }

@@ -1,5 +1,5 @@
-"""The host decisions of BPG / ABPG / ABPG_gain (accbpg/algorithms.py:11-180, 295-420), one copy for the single solvers
-of ``algorithms.py`` and the lock-step batches of ``batched.py``, as ``_DivStepRun`` / ``_DescentRun`` are for the
+"""The host decisions of BPG / ABPG / ABPG_expo / ABPG_gain / ABDA (accbpg/algorithms.py:11-514), one copy for the single
+solvers of ``algorithms.py`` and the lock-step batches of ``batched.py``, as ``_DivStepRun`` / ``_DescentRun`` are for the
 Frank-Wolfe solvers.  A run object is one instance's scalars, result arrays and last iteration; it touches no device
 and no vector -- the caller does that work and hands over the numbers -- so the CPU tests drive it with NumPy
 (tests/test_solver_runs_cpu.py).  Every expression keeps the reference's operation order; the cited lines are its."""
@@ -196,3 +196,83 @@ class _GainRun(_Accelerated):
         self.sumlogG += np.log(self.G)
         self.Gavg[k] = np.exp(self.sumlogG / (self.gamma + k))
         return super().finish(dot)
+
+
+class _ExpoRun(_Accelerated):
+    """One instance of ABPG_expo (:183-292): the exponent and its lowering, theta, the restart state (:276-282), the
+    records and the stop test (:285).
+
+    Quirks kept: theta is that of the exponent the iteration starts from, for all of its trials (:238-241); a failed
+    test at gamma == 1 is accepted (:262-265); a comparison with a NaN is False, which accepts; the restart test has no
+    k > 0 guard, so rule 'f' at k = 0 compares with F[-1] (:276-279)."""
+    records = ("F", "Gamma", "G", "T")
+    restart_from = 0
+
+    def __init__(self, L, gamma0, maxitrs, epsilon, delta, theta_eq, checkdiv, Gmargin, restart, restart_rule):
+        super().__init__(L, gamma0, maxitrs, epsilon, theta_eq, restart, restart_rule)
+        self.delta, self.checkdiv, self.Gmargin = delta, checkdiv, Gmargin
+        self.Gamma = np.ones(maxitrs) * gamma0
+        self.lin, self.Gdr = None, 0.0
+
+    def begin(self, k):
+        """Iteration k: advances theta with the exponent it starts from and returns it."""
+        self.k = k
+        self.theta = next_theta(self.theta, self.kk, self.gamma, self.theta_eq)     # :238-241
+        return self.theta
+
+    def prox_coef(self):
+        return self.theta ** (self.gamma - 1) * self.L                      # :249
+
+    def divergences(self, lin, dxy, dzz):
+        """<g, x+ - y>, D(x+, y) and D(z+, z) of a trial.  NEEDS_VALUE: ``value`` decides; ACCEPT or RETRY: checkdiv
+        decided (:258)."""
+        self.lin, self.dzz = lin, dzz
+        self.Gdr = dxy / dzz / self.theta ** self.gamma                     # :255
+        if self.checkdiv:
+            return self._decided(dxy > self.Gmargin * (self.theta ** self.gamma) * dzz)
+        return NEEDS_VALUE
+
+    def value(self, fx, fy):
+        """ACCEPT or RETRY by the values at x+ and y (:260)."""
+        return self._decided(fx > fy + self.lin + self.theta ** self.gamma * self.L * self.dzz)
+
+    def _decided(self, failed):
+        if failed and self.gamma > 1:                                       # :262-265
+            self.gamma = max(self.gamma - self.delta, 1)
+            return RETRY
+        return ACCEPT
+
+    def finish(self, dot=None):
+        """Records Gdr and the exponent (:267-268), then the restart and the stop test."""
+        self.G[self.k] = self.Gdr
+        self.Gamma[self.k] = self.gamma
+        return super().finish(dot)
+
+
+class _ABDARun(_Accelerated):
+    """One instance of ABDA (:423-514): theta, the running sum of the weights, the records and the stop test (:508)."""
+    records = ("F", "G", "T")
+    restart_from = 0            # (never read: ABDA does not restart)
+
+    def __init__(self, L, gamma, maxitrs, epsilon, theta_eq):
+        super().__init__(L, gamma, maxitrs, epsilon, theta_eq, False, 'g')
+        self.csum = 0                                                       # the integer, as in the reference (:463)
+
+    def begin(self, k):
+        """Iteration k: advances theta and returns it."""
+        self.k = k
+        self.theta = next_theta(self.theta, self.kk, self.gamma, self.theta_eq)     # :472-475
+        return self.theta
+
+    def weight(self):
+        """(theta^(1-gamma), the sum of the weights with it, L over that sum): gavg += wgt * g (:483), csum += wgt
+        (:484), z = prox_map(gavg / csum, L / csum) (:485)."""
+        wgt = self.theta ** (1 - self.gamma)
+        self.csum = self.csum + wgt
+        return wgt, self.csum, self.L / self.csum
+
+    def divergences(self, dxy, dzz):
+        """D(x+, y) and D(z+, z) of the step: records and returns the triangle-scaling gain (:491)."""
+        self.dzz = dzz
+        self.G[self.k] = dxy / dzz / self.theta ** self.gamma
+        return self.G[self.k]

@@ -195,6 +195,18 @@ int accbpg_dopt_batch_burg_simplex_div_prox(accbpg_dopt_batch* b, const double* 
                                             const double* L_host, double eps, double* x_out_dev, const int* active_host,
                                             int* status_host, int* info_host);
 
+/* The dual-averaging step of ABDA (accbpg/algorithms.py:483-485) for the active instances, one launch:
+ *   gavg_out_i = gavg_i + wgt_host[i] * g_i,   z_out_i = BurgEntropySimplex.prox_map(gavg_out_i / csum_host[i], Lc_host[i])
+ * with one rounding per operation -- bit for bit accbpg_vec_axpby(1.0, gavg_i, wgt, g_i), accbpg_vec_div_scalar and
+ * accbpg_burg_simplex_div_prox(NULL, ...) in a row (which is what runs, instance by instance, for n > 32768).  Lc_host[i]
+ * is L / csum as the caller computed it.  gavg_out_dev must not be gavg_dev (ACCBPG_ERR_ARG).  status_host[i]:
+ * ACCBPG_ERR_ASSERT when Lc_host[i] is not positive, and nothing is written for that instance.  info_host (optional):
+ * {bisection steps, Newton steps} per instance. */
+int accbpg_dopt_batch_burg_simplex_avg_prox(accbpg_dopt_batch* b, const double* gavg_dev, const double* g_dev, int64_t ld,
+                                            const double* wgt_host, const double* csum_host, const double* Lc_host,
+                                            double eps, double* gavg_out_dev, double* z_out_dev, const int* active_host,
+                                            int* status_host, int* info_host);
+
 /* out_host[3i..3i+2] = { <g_i, x_i - y_i>, D_h(x_i, y_i), D_h(z_i, z1_i) } (accbpg/algorithms.py:153-154, 377-378, 387). */
 int accbpg_dopt_batch_ls_terms(accbpg_dopt_batch* b, const double* g_dev, const double* x_dev, const double* y_dev,
                                const double* z_dev, const double* z1_dev, int64_t ld, const int* active_host,

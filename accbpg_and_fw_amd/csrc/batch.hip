@@ -26,7 +26,8 @@ static int batch_init(accbpg_dopt_batch* b, const double* const* V_host, int K, 
     hipDeviceProp_t prop;
     ACC_HIP(hipGetDeviceProperties(&prop, b->device));
     ACC_HIP(acc_malloc(&b->dscal_all, sizeof(double) * 24 * (size_t)K, "dscal_all"));
-    ACC_HIP(hipMemset(b->dscal_all, 0, sizeof(double) * 24 * (size_t)K));
+    // (on the batch's stream, which every dopt_init below waits for before it returns)
+    ACC_HIP(hipMemsetAsync(b->dscal_all, 0, sizeof(double) * 24 * (size_t)K, b->stream));
     ACC_HIP(hipHostMalloc(&b->hpin, sizeof(double) * 24 * (size_t)K, hipHostMallocDefault));
     // instances that share a launch: as many as have their one-launch factorisations resident together.  The first
     // guess (T(T+1)/2 - (T-1) workgroups each, two per CU) sizes the per-instance Gram grids; it is replaced below by

@@ -58,14 +58,15 @@ int dopt_init(accbpg_dopt* h) {
     ACC_HIP(acc_malloc(&h->Lbuf, mm, "Lbuf"));
     ACC_HIP(acc_malloc(&h->Wbuf, mm, "Wbuf"));
     ACC_HIP(acc_malloc(&h->Tbuf, mm, "Tbuf"));
-    ACC_HIP(hipMemset(h->Lbuf, 0, mm));
-    ACC_HIP(hipMemset(h->Wbuf, 0, mm));     // the upper triangle of W must read as zero
-    ACC_HIP(hipMemset(h->Tbuf, 0, mm));
+    // every clear of create goes on the handle's stream; build_plans waits for that stream once before create returns
+    ACC_HIP(hipMemsetAsync(h->Lbuf, 0, mm, h->stream));
+    ACC_HIP(hipMemsetAsync(h->Wbuf, 0, mm, h->stream));     // the upper triangle of W must read as zero
+    ACC_HIP(hipMemsetAsync(h->Tbuf, 0, mm, h->stream));
     if (h->dscal_ext) {
         h->dscal = h->dscal_ext;                                // a slice of the batch's array (zeroed by the batch)
     } else {
         ACC_HIP(acc_malloc(&h->dscal, sizeof(double) * 24, "dscal"));     // 16 scalars, then the status flags: one readback
-        ACC_HIP(hipMemset(h->dscal, 0, sizeof(double) * 24));
+        ACC_HIP(hipMemsetAsync(h->dscal, 0, sizeof(double) * 24, h->stream));
     }
     h->dflag = reinterpret_cast<int*>(h->dscal + 16);
     ACC_HIP(hipHostMalloc(&h->hpin, sizeof(double) * 32, hipHostMallocDefault));
@@ -381,7 +382,7 @@ extern "C" int accbpg_dopt_burg_trial(accbpg_dopt* h, const double* x_prev_dev, 
     if (!h->trial_stat) {
         double* p = nullptr;
         ACC_HIP(acc_malloc(&p, sizeof(double) * TRIAL_DOUBLES, "trial_stat"));
-        if (hipMemset(p, 0, sizeof(double) * TRIAL_DOUBLES) != hipSuccess ||
+        if (hipMemsetAsync(p, 0, sizeof(double) * TRIAL_DOUBLES, s) != hipSuccess ||      // ahead of the launches below
             hipHostMalloc(&h->trial_pin, sizeof(double) * TRIAL_DOUBLES, hipHostMallocDefault) != hipSuccess) {
             acc_free(p);
             set_last_error("accbpg_dopt_burg_trial: could not allocate the status block");

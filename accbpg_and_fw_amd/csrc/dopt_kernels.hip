@@ -2599,13 +2599,16 @@ int build_plans(accbpg_dopt* h) {
             ACC_TRY(upload(jobs, &jobs_dev, "chol_jobs"));
             h->chol_jobs = jobs_dev;
             ACC_HIP(acc_malloc(&h->chol_ready, sizeof(int) * (size_t)(T * T + 5 * T), "chol_ready"));
-            ACC_HIP(hipMemset(h->chol_ready, 0, sizeof(int) * (size_t)(T * T + 5 * T)));
+            ACC_HIP(hipMemsetAsync(h->chol_ready, 0, sizeof(int) * (size_t)(T * T + 5 * T), h->stream));
             ACC_HIP(acc_malloc(&h->chol_hand, sizeof(double) * (size_t)T * NB * NB, "chol_hand"));
             ACC_HIP(acc_malloc(&h->chol_aux, sizeof(double) * (size_t)T * CT_AUX, "chol_aux"));
             ACC_HIP(acc_malloc(&h->Gbuf, sizeof(double) * (size_t)m * m, "Gbuf"));
-            ACC_HIP(hipMemset(h->Gbuf, 0, sizeof(double) * (size_t)m * m));
+            ACC_HIP(hipMemsetAsync(h->Gbuf, 0, sizeof(double) * (size_t)m * m, h->stream));
         }
     }
+    // the clears of dopt_init and the two above ran on the handle's stream: once they are done, the cleared state is
+    // valid for work on any stream, whichever one the caller sets next
+    ACC_HIP(hipStreamSynchronize(h->stream));
     return ACCBPG_OK;
 }
 

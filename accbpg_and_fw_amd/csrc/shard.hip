@@ -153,7 +153,8 @@ extern "C" int accbpg_dopt_shard_create(accbpg_dopt* local, int64_t n, int world
     auto fail = [&](int rc) { accbpg_dopt_shard_destroy(s); return rc; };
     if (acc_malloc(&s->gram, sizeof(double) * (size_t)m * m, "gram") != hipSuccess ||
         acc_malloc(&s->msg, sizeof(double) * (size_t)s->msg_len, "msg") != hipSuccess ||
-        hipMemset(s->msg, 0, sizeof(double) * (size_t)s->msg_len) != hipSuccess ||
+        hipMemsetAsync(s->msg, 0, sizeof(double) * (size_t)s->msg_len, local->stream) != hipSuccess ||
+        hipStreamSynchronize(local->stream) != hipSuccess ||                // cleared for work on any stream
         hipHostMalloc(reinterpret_cast<void**>(&s->hcount), sizeof(double)) != hipSuccess) {
         set_last_error("accbpg_dopt_shard_create: out of device memory");
         return fail(ACCBPG_ERR_HIP);

@@ -919,7 +919,7 @@ extern "C" int accbpg_burg_reg_div_prox(int kind, const double* y_dev, const dou
 static int batch_vec_scratch(accbpg_dopt_batch* b) {
     if (b->vflags) return ACCBPG_OK;
     ACC_HIP(acc_malloc(&b->vflags, sizeof(int) * 8 * (size_t)b->K, "vflags"));
-    ACC_HIP(hipMemset(b->vflags, 0, sizeof(int) * 8 * (size_t)b->K));
+    ACC_HIP(hipMemsetAsync(b->vflags, 0, sizeof(int) * 8 * (size_t)b->K, b->stream));   // the stream of the launches that follow
     ACC_HIP(acc_malloc(&b->vout, sizeof(double) * 4 * (size_t)b->K, "vout"));
     ACC_HIP(acc_malloc(&b->vpart, sizeof(double) * 4 * RMAXBLK * (size_t)b->K, "vpart"));
     ACC_HIP(hipHostMalloc(&b->vpin, sizeof(double) * 8 * (size_t)b->K, hipHostMallocDefault));

@@ -307,10 +307,6 @@ class DOptimalObj(RSmoothFunction):
                 self._side = torch.cuda.Stream(device=self._V.device)
                 rc = self._lib.accbpg_dopt_create(_ptr(self._V), self.m, self.n, self._V.stride(0),
                                                   C.c_void_p(self._side.cuda_stream), C.byref(h2), 1)
-                # create clears the handle's buffers (Gram target, factor, flags) with memsets on the null stream, which
-                # need not have run when it returns, and the side stream does not wait for the null stream: the first
-                # evaluation follows at once (value_async), so let them land first
-                torch.cuda.default_stream(self._V.device).synchronize()
             _lib.check(rc, "accbpg_dopt_create")
             self._h2 = h2
             # its evaluations run beside the gradient evaluation of the solver's own stream: a launch per block

@@ -1179,6 +1179,21 @@ def test_batched_instances_match_sequential(acc):
         np.testing.assert_array_equal(a[2], b[2])
 
 
+def test_batched_fresh_instances_match_sequential(acc):
+    """The same with objects the threads are the first to touch: the sequential leg runs on problems of its own from
+    the same seeds, so no handle of the parallel leg has been evaluated before -- its first evaluation, its first trial
+    (the lazily allocated status block) and its side handle all happen on the threads' non-blocking streams."""
+    from accbpg_and_fw_amd.batched import solve_batch
+    seq_probs = [acc.D_opt_design(96, 640, randseed=50 + j) for j in range(6)]
+    seq = [acc.ABPG_gain(f, h, L, x0, gamma=2, maxitrs=40, verbose=False) for f, h, L, x0 in seq_probs]
+    probs = [acc.D_opt_design(96, 640, randseed=50 + j) for j in range(6)]      # never evaluated
+    par = solve_batch(probs, acc.ABPG_gain, threads=6, gamma=2, maxitrs=40, verbose=False)
+    for a, b in zip(seq, par):
+        np.testing.assert_array_equal(a[0], b[0])
+        np.testing.assert_array_equal(a[1], b[1])
+        np.testing.assert_array_equal(a[2], b[2])
+
+
 # ------------------------------------------------------------------ SURVEY 8(f) rows 1-3
 import os as _os
 _DATA = _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "golden", "data")

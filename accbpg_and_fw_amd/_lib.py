@@ -180,6 +180,14 @@ _SIGS = {
     "accbpg_svm_set_stream": (C.c_int, [_P, _P]),
     "accbpg_svm_func_grad": (C.c_int, [_P, _P, C.c_double, C.c_int, C.POINTER(C.c_double), _P]),
     "accbpg_svm_get_ax": (C.c_int, [_P, _P]),
+    "accbpg_logistic_create": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, C.POINTER(_P)]),
+    "accbpg_logistic_destroy": (C.c_int, [_P]),
+    "accbpg_logistic_set_stream": (C.c_int, [_P, _P]),
+    "accbpg_logistic_func_grad": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_double), _P]),
+    "accbpg_logistic_get": (C.c_int, [_P, C.c_int, _P]),
+    "accbpg_l2l1linf_prox": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P]),
+    "accbpg_l1_norm": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), _P, _P]),
+    "accbpg_sq_ls_terms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), _P, _P]),
     "accbpg_shannon_div_prox": (C.c_int, [C.c_int, _P, _P, C.c_double, C.c_double, C.c_int64, _P, _P, _P]),
     "accbpg_shannon_ls_terms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double), _P, _P]),
     "accbpg_shannon_divergence": (C.c_int, [_P, _P, C.c_int64, C.c_double, C.POINTER(C.c_double), _P, _P]),

@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from .functions import (BurgEntropy, BurgEntropySimplex, DOptimalObj, PolyDiv, ShannonEntropy, SquaredL2Norm,
+from .functions import (BurgEntropy, BurgEntropySimplex, DOptimalObj, L2L1Linf, PolyDiv, ShannonEntropy, SquaredL2Norm,
                         SumOf2nd4thPowers,
                         combine_ls_terms, from_dev, ls_terms, shannon_ls_terms, to_dev, vec_axpby, vec_div_scalar,
                         vec_dot_diff)
@@ -35,7 +35,7 @@ def _divergences(h, g, x, y, z, z_prev):
         return ls_terms(g, x, y, z, z_prev)
     if isinstance(h, ShannonEntropy):
         return shannon_ls_terms(g, x, y, z, z_prev, h.delta)
-    if isinstance(h, (SumOf2nd4thPowers, PolyDiv)):
+    if isinstance(h, (SumOf2nd4thPowers, PolyDiv, L2L1Linf)):
         return h.ls_terms(g, x, y, z, z_prev)
     lin = vec_dot_diff(g, x, y) if g is not None else 0.0
     return lin, h.divergence(x, y), (h.divergence(z, z_prev) if z is not None else 0.0)

@@ -1,12 +1,12 @@
 """Problem factories (accbpg/applications.py): D-optimal design, Poisson and KL regression (on the orthant and on the
-simplex), symmetric NMF, and the soft-margin SVM on an l2 ball."""
+simplex), symmetric NMF, the soft-margin SVM on an l2 ball, and l1-regularised logistic regression in a box."""
 from __future__ import annotations
 
 import numpy as np
 
 from .functions import (BurgEntropyL1, BurgEntropyL2, BurgEntropySimplex, DOptimalObj, FrobeniusSymLoss,
-                        KLdivRegression, PoissonRegression, PolyDiv, ShannonEntropyL1, SquaredL2Norm, SumOf2nd4thPowers,
-                        SumOf2nd4thPowersPositiveOrthant, SVM_fun, vec_argminmax)
+                        KLdivRegression, L2L1Linf, LogisticRegression, PoissonRegression, PolyDiv, ShannonEntropyL1,
+                        SquaredL2Norm, SumOf2nd4thPowers, SumOf2nd4thPowersPositiveOrthant, SVM_fun, vec_argminmax)
 from .utils import (edge_point_on_simplex, generate_dataset_for_svm, load_libsvm_file, random_point_in_l2_ball,
                     random_point_on_simplex)
 
@@ -379,3 +379,24 @@ def svm_digits_ds_divs_ball(center=None, lamda=0.5, real_ds=False):
     radius, _, _, L, x0 = _svm_ball_numbers(X, Y, lamda, center)
     poly_h, sqL2_h = PolyDiv(X, lamda=lamda, radius=radius), SquaredL2Norm()
     return f, [poly_h, sqL2_h], L, x0, radius
+
+
+def Logistic_regr_L2L1Linf(m, n, lamda=None, B=1, randseed=-1, labels=None):
+    """l1-regularised logistic regression in the box ||x||_inf <= B (accbpg/ex_LR_L2L1Linf.py:57-70):
+        minimize_x  (1/m) * sum_i log(1 + exp(-b_i*(ai'*x))) + lamda*||x||_1   subject to ||x||_inf <= B.
+    The draws are the example's, in its order, from the legacy global generator: A = randn(m, n), then
+    b = sign(rand(m, 1)) -- all +1, kept so that a seeded script consumes the same stream.  ``labels`` (length m),
+    when given, replaces b after the draws; ``lamda`` defaults to 1.0/m.  Returns f, h = L2L1Linf(lamda, B),
+    L = 0.25, x0 = zeros(n)."""
+    if randseed > 0:
+        np.random.seed(randseed)
+    A = np.random.randn(m, n)
+    b = np.sign(np.random.rand(m, 1))
+    if labels is not None:
+        b = np.asarray(labels, dtype=np.float64)
+        assert b.size == m, "Logistic Regression: len(b) != m"
+    f = LogisticRegression(A, b.reshape(-1))
+    h = L2L1Linf(lamda=1.0 / m if lamda is None else lamda, B=B)
+    L = 0.25
+    x0 = np.zeros(n)
+    return f, h, L, x0

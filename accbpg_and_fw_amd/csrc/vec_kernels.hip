@@ -479,6 +479,59 @@ __global__ __launch_bounds__(RB) void dot_partial_kernel(const double* __restric
     block_reduce_store<RB, 1, false, 4>(v, part + blockIdx.x * 4);
 }
 
+// sum |x|  (np.sum(abs(x)) of L2L1Linf.extra_Psi, functions.py:801)
+__global__ __launch_bounds__(RB) void l1_partial_kernel(const double* __restrict__ x, int64_t n,
+                                                       double* __restrict__ part) {
+    double s = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * RB;
+    for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) s += fabs(x[i]);
+    double v[1] = {s};
+    block_reduce_store<RB, 1, false, 4>(v, part + blockIdx.x * 4);
+}
+
+// slots: 0 <g,x-y>, 1 sum (x-y)^2, 2 sum (z-z1)^2 -- the line-search terms of h = (1/2)||.||^2 (functions.py:809-815)
+__global__ __launch_bounds__(RB) void sq_ls_partial_kernel(const double* __restrict__ g, const double* __restrict__ x,
+                                                          const double* __restrict__ y, const double* __restrict__ z,
+                                                          const double* __restrict__ z1, int64_t n,
+                                                          double* __restrict__ part) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * RB;
+    for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
+        const double d = x[i] - y[i];
+        if (g != nullptr) s0 += g[i] * d;
+        s1 += d * d;
+        if (z != nullptr) {
+            const double dz = z[i] - z1[i];
+            s2 += dz * dz;
+        }
+    }
+    double v[3] = {s0, s1, s2};
+    block_reduce_store<RB, 3, false, 4>(v, part + blockIdx.x * 4);
+}
+
+// L2L1Linf.prox_map / div_prox_map (functions.py:817-835) in the reference's operation order:
+//   w = g - L*y (y given), v = -(invL*w), soft threshold at thr, clip to [-B, B] with a NaN kept as np.clip keeps it
+__global__ __launch_bounds__(RB) void l2l1linf_prox_kernel(const double* __restrict__ y, const double* __restrict__ g,
+                                                          double L, double invL, double thr, double B, int64_t n,
+                                                          double* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * RB;
+    for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
+        double w = g[i];
+        if (y != nullptr) {
+            const double ly = L * y[i];
+            w = w - ly;
+        }
+        const double p = invL * w;
+        double v = -p;
+        if (fabs(v) <= thr) v = 0.0;                  // x[abs(x) <= threshold] = 0
+        if (v > thr) v = v - thr;                     // x[x > threshold] -= threshold
+        if (v < -thr) v = v + thr;                    // x[x < -threshold] += threshold
+        v = (v < -B) ? -B : v;                        // np.clip: a NaN passes both comparisons
+        v = (v > B) ? B : v;
+        out[i] = v;
+    }
+}
+
 // Closed-form Burg-entropy prox maps on x > 0 with NumPy's operation order:
 //   gt = g - L*(-1/y)  when y != NULL (BurgEntropy.div_prox_map, functions.py:264-271), else gt = g
 //   kind 0: L / gt                                     (BurgEntropy.prox_map,   :255-262, needs gt > 0)
@@ -882,6 +935,49 @@ extern "C" int accbpg_vec_dot(const double* x_dev, const double* y_dev, int64_t 
     const double* o = finish4(part, nb, s);
     if (!o) return ACCBPG_ERR_HIP;
     out_host[0] = o[0];
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_l1_norm(const double* x_dev, int64_t n, double* out_host, double* ws_dev, void* stream) {
+    if (!x_dev || n <= 0 || !out_host || !ws_dev) return ACCBPG_ERR_ARG;
+    ACC_TRY(ensure_scratch());
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = red_blocks(n, RMAXBLK);
+    double* part = ws_dev + n;
+    l1_partial_kernel<<<nb, RB, 0, s>>>(x_dev, n, part);
+    const double* o = finish4(part, nb, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out_host[0] = o[0];
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_sq_ls_terms(const double* g_dev, const double* x_dev, const double* y_dev, const double* z_dev,
+                                  const double* z1_dev, int64_t n, double* out_host, double* ws_dev, void* stream) {
+    if (!x_dev || !y_dev || n <= 0 || !out_host || !ws_dev) return ACCBPG_ERR_ARG;
+    if ((z_dev == nullptr) != (z1_dev == nullptr)) return ACCBPG_ERR_ARG;
+    ACC_TRY(ensure_scratch());
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = red_blocks(n, RMAXBLK);
+    double* part = ws_dev + n;
+    sq_ls_partial_kernel<<<nb, RB, 0, s>>>(g_dev, x_dev, y_dev, z_dev, z1_dev, n, part);
+    const double* o = finish4(part, nb, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    out_host[0] = o[0];
+    out_host[1] = 0.5 * o[1];
+    out_host[2] = 0.5 * o[2];
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_l2l1linf_prox(const double* y_dev, const double* g_dev, double L, double lamda, double B,
+                                    int64_t n, double* out_dev, void* stream) {
+    if (!g_dev || !out_dev || n <= 0) return ACCBPG_ERR_ARG;
+    if (!(L > 0.0)) {                                           // functions.py:821, :834
+        set_last_error("L2L1Linf: L should be positive.");
+        return ACCBPG_ERR_ASSERT;
+    }
+    const double invL = 1.0 / L, thr = lamda / L;
+    l2l1linf_prox_kernel<<<ew_blocks(n), RB, 0, (hipStream_t)stream>>>(y_dev, g_dev, L, invL, thr, B, n, out_dev);
+    ACC_HIP(hipGetLastError());
     return ACCBPG_OK;
 }
 

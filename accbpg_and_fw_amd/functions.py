@@ -744,6 +744,102 @@ class SVM_fun(RSmoothFunction):
         return out.cpu().numpy()
 
 
+class LogisticRegression(RSmoothFunction):
+    """f(omega) = (1/m) sum_i log(1 + exp(-y_i (X omega)_i)), logistic regression (accbpg/functions.py:1068-1104,
+    accbpg/ex_LR_L2L1Linf.py:19-54).
+
+    ``X`` (m x n) and ``y`` (length m, any numeric type, usually +-1) may be NumPy arrays (copied to the GPU once) or
+    CUDA tensors (an fp64 ``X`` with unit column stride is borrowed with its row stride); ``self.X``, ``self.y`` and
+    ``self.alpha`` stay readable as in the reference.  Each func_grad is two passes over X: X omega with the logistic
+    terms t_i = max(-s_i, 0) + log1p(exp(-|s_i|)) and r_i = -y_i sigma(-s_i), s_i = y_i (X omega)_i, in its epilogue,
+    then X^T r / m (logistic_kernels.hip).  The value is formed on the host as sum_t / m."""
+
+    def __init__(self, X, y, alpha=0.01):
+        self.X = X
+        self.y = y
+        self.alpha = alpha
+        self.m = X.shape[0]
+        self.n = X.shape[1]
+        assert y.shape[0] == self.m, "Logistic Regression: len(b) != m"
+        if isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float64 and X.dim() == 2 \
+                and (X.stride(1) == 1 or self.n == 1) and X.stride(0) >= self.n:
+            self._A = X                                         # borrowed with its row stride
+        else:
+            self._A, _ = to_dev(X)
+        self._y, _ = to_dev(y)
+        self._y = self._y.to(self._A.device).reshape(-1)
+        assert self._y.numel() == self.m, "Logistic Regression: len(b) != m"
+        lib = _lib.load()
+        h = C.c_void_p()
+        with torch.cuda.device(self._A.device):
+            rc = lib.accbpg_logistic_create(_ptr(self._A), self.m, self.n, self._A.stride(0), _ptr(self._y), _stream(),
+                                            C.byref(h))
+        _lib.check(rc, "accbpg_logistic_create")
+        self._h = h
+        self._lib = lib
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self._lib.accbpg_logistic_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def _eval(self, omega, flag):
+        """The C entry at omega: (sum_t or None, gradient tensor or None, omega came from NumPy)."""
+        size = omega.numel() if isinstance(omega, torch.Tensor) else omega.size
+        assert size == self.n, "Logistic Regression: x.size not equal to n"
+        xd, was_np = to_dev(omega)
+        xd = xd.reshape(-1)
+        g = torch.empty(self.n, dtype=torch.float64, device=self._A.device) if flag != 0 else None
+        fval = (C.c_double * 1)(0.0)
+        with torch.cuda.device(self._A.device):
+            self._lib.accbpg_logistic_set_stream(self._h, _stream())
+            rc = self._lib.accbpg_logistic_func_grad(self._h, _ptr(xd), int(flag), fval, _ptr(g))
+        _lib.check(rc, "accbpg_logistic_func_grad")
+        return (np.float64(fval[0]) if flag != 1 else None), g, was_np
+
+    def f(self, omega):
+        return self.func_grad(omega, flag=0)
+
+    def __call__(self, omega):
+        return self.func_grad(omega, flag=0)
+
+    def gradient(self, omega):
+        return self.func_grad(omega, flag=1)
+
+    def func_grad(self, omega, flag=2):
+        """flag=0: function, flag=1: gradient, flag=2: function & gradient."""
+        assert flag in (0, 1, 2), "Logistic Regression: flag must be 0, 1 or 2."
+        sum_t, g, was_np = self._eval(omega, flag)
+        if flag == 0:
+            return sum_t / self.m
+        if flag == 1:
+            return from_dev(g, was_np)
+        return sum_t / self.m, from_dev(g, was_np)
+
+    def _get(self, which):
+        out = torch.empty(self.m, dtype=torch.float64, device=self._A.device)
+        with torch.cuda.device(self._A.device):
+            rc = self._lib.accbpg_logistic_get(self._h, which, _ptr(out))
+        _lib.check(rc, "accbpg_logistic_get")
+        return out.cpu().numpy()
+
+    def fitted(self):
+        """X omega of the last evaluation (length m) as a NumPy vector."""
+        return self._get(0)
+
+    def losses(self):
+        """The per-row losses log(1 + exp(-y_i (X omega)_i)) of the last evaluation as a NumPy vector."""
+        return self._get(1)
+
+    def weights(self):
+        """r_i = -y_i sigma(-y_i (X omega)_i) of the last evaluation as a NumPy vector: the gradient is X^T r / m."""
+        return self._get(2)
+
+
 class FrobeniusSymLoss(RSmoothFunction):
     """f(X) = 0.5*||M - X X^T||_F^2 for symmetric nonnegative matrix factorisation (accbpg/functions.py:908-976).
 
@@ -1169,6 +1265,58 @@ class SquaredL2Norm(LegendreFunction):
         return from_dev(vec_axpby(1.0, yd, -(1 / L), gd), was_np)
 
 
+class L2L1Linf(LegendreFunction):
+    """h(x) = (1/2)||x||_2^2 for problems  minimize f(x) + lamda*||x||_1  subject to ||x||_inf <= B
+    (accbpg/functions.py:782-835).  ``lamda`` and ``B`` are read at every call.  The prox maps are one elementwise
+    launch in the reference's operation order (soft threshold at lamda/L, then the clip to [-B, B]); the sums run on
+    the fixed tree of the vector kernels."""
+
+    def __init__(self, lamda=0, B=1):
+        self.lamda = lamda
+        self.B = B
+
+    def __call__(self, x):
+        xd, _ = to_dev(x)
+        return 0.5 * vec_dot(xd, xd)
+
+    def extra_Psi(self, x):
+        """lamda * ||x||_1"""
+        xd, _ = to_dev(x)
+        return self.lamda * l1_norm(xd)
+
+    def gradient(self, x):
+        return x
+
+    def divergence(self, x, y):
+        """D(x, y) = (1/2)||x - y||_2^2"""
+        assert x.shape == y.shape, "L2L1Linf: x and y not same shape."
+        xd, _ = to_dev(x)
+        yd, _ = to_dev(y)
+        return sq_ls_terms(None, xd, yd)[1]
+
+    def ls_terms(self, g, x, y, z=None, z1=None):
+        """(<g,x-y>, D(x,y), D(z,z1)) in one launch and one readback."""
+        return sq_ls_terms(g, x, y, z, z1)
+
+    def _prox(self, y, g, L):
+        gd, was_np = to_dev(g)
+        yd = to_dev(y)[0] if y is not None else None
+        out = torch.empty_like(gd)
+        _call("accbpg_l2l1linf_prox", gd, _ptr(yd), _ptr(gd), float(L), float(self.lamda), float(self.B), gd.numel(),
+              _ptr(out), assert_msg="L2L1Linf: L should be positive.")
+        return from_dev(out, was_np)
+
+    def prox_map(self, g, L):
+        """argmin_{||x||_inf <= B} { lamda*||x||_1 + <g, x> + L*h(x) }"""
+        assert L > 0, "L2L1Linf: L should be positive."
+        return self._prox(None, g, L)
+
+    def div_prox_map(self, y, g, L):
+        """argmin_{||x||_inf <= B} { lamda*||x||_1 + <g, x> + L*D(x, y) }"""
+        assert y.shape == g.shape and L > 0, "Vectors y and g not same shape."
+        return self._prox(y, g, L)
+
+
 def polydiv_prox_radius(L, lamda, ds_mean, ds_mean_quad, radius):
     """t* = min(radius, t^) with t^ >= 0 the root of L*phi'(t) = radius, phi'(t) = lamda^2 t^3 + 2 lamda ds_mean t^2 +
     ds_mean_quad t: the norm of the minimiser of L*phi(||x||) + <g', x> over ||x|| <= radius when ||g'|| = radius
@@ -1350,6 +1498,24 @@ def quartic_ls_terms(g, x, y, z=None, z1=None):
     out = (C.c_double * 7)()
     _call("accbpg_quartic_ls_terms", x, _ptr(g), _ptr(x), _ptr(y), _ptr(z), _ptr(z1), x.numel(), out, _WS)
     return tuple(out)
+
+
+def l1_norm(x):
+    """sum |x_i|  (np.sum(abs(x)) of L2L1Linf.extra_Psi, functions.py:801)."""
+    out = C.c_double(0.0)
+    _call("accbpg_l1_norm", x, _ptr(x), x.numel(), C.byref(out), _WS)
+    return np.float64(out.value)
+
+
+def sq_ls_terms(g, x, y, z=None, z1=None):
+    """(<g,x-y>, (1/2)||x-y||^2, (1/2)||z-z1||^2) in one streaming pass and one readback (g None, z None: 0)."""
+    xd, yd = to_dev(x)[0], to_dev(y)[0]
+    gd = to_dev(g)[0] if g is not None else None
+    zd = to_dev(z)[0] if z is not None else None
+    z1d = to_dev(z1)[0] if z is not None else None
+    out = (C.c_double * 3)(0.0, 0.0, 0.0)
+    _call("accbpg_sq_ls_terms", xd, _ptr(gd), _ptr(xd), _ptr(yd), _ptr(zd), _ptr(z1d), xd.numel(), out, _WS)
+    return np.float64(out[0]), np.float64(out[1]), np.float64(out[2])
 
 
 def vec_min_sum(x):

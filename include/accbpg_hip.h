@@ -677,6 +677,43 @@ int accbpg_svm_func_grad(accbpg_svm* h, const double* x_dev, double lamda, int f
 /* out_dev <- A x of the last evaluation (length m), the margins before the labels. */
 int accbpg_svm_get_ax(accbpg_svm* h, double* out_dev);
 
+/* ---- Logistic regression (accbpg/ex_LR_L2L1Linf.py:19-54, accbpg/functions.py:1068-1104) with L2L1Linf ----- */
+
+typedef struct accbpg_logistic accbpg_logistic;
+
+/* f(x) = (1/m) sum_i log(1 + exp(-y_i (A x)_i)).  Same layout and ownership rules as accbpg_svm_create: A row-major
+ * m x n with leading dimension lda >= n (any base alignment), y length m as doubles (+-1 or anything else); both owned
+ * by the caller.  A failed allocation leaves nothing of the handle behind. */
+int accbpg_logistic_create(const double* A_dev, int64_t m, int64_t n, int64_t lda, const double* y_dev, void* stream,
+                           accbpg_logistic** out);
+int accbpg_logistic_destroy(accbpg_logistic* h);
+int accbpg_logistic_set_stream(accbpg_logistic* h, void* stream);
+
+/* flag 0 -> f_host[0] = sum_i t_i, t_i = max(-s_i, 0) + log1p(exp(-|s_i|)) with s_i = y_i (Ax)_i, summed on the fixed
+ * tree; one pass over A, the caller forms f = f_host[0]/m.  flag 1 -> g_dev = A^T r / m with r_i = -(y_i q_i),
+ * q_i = sigma(-s_i) = (s_i >= 0) ? e/(1+e) : 1/(1+e), e = exp(-|s_i|); nothing waits for the device.  flag 2 -> both.
+ * A NaN s_i gives NaN t_i and r_i; s_i = +inf gives t_i = 0, q_i = 0; s_i = -inf gives t_i = +inf, q_i = 1.  Every row
+ * enters A^T r, so 0*NaN propagates.  g_dev must not be x_dev.  Synchronises the stream when a value is returned. */
+int accbpg_logistic_func_grad(accbpg_logistic* h, const double* x_dev, int flag, double* f_host, double* g_dev);
+
+/* out_dev <- a length-m vector of the last evaluation: which 0 -> A x, 1 -> t, 2 -> r. */
+int accbpg_logistic_get(accbpg_logistic* h, int which, double* out_dev);
+
+/* L2L1Linf.prox_map (y_dev NULL) and div_prox_map (accbpg/functions.py:817-835) in one elementwise launch and the
+ * reference's operation order: w = g - L*y, v = -((1/L)*w), thr = lamda/L; |v| <= thr -> +0.0, v > thr -> v - thr,
+ * v < -thr -> v + thr; clipped to [-B, B], a NaN kept.  L <= 0 returns ACCBPG_ERR_ASSERT. */
+int accbpg_l2l1linf_prox(const double* y_dev, const double* g_dev, double L, double lamda, double B, int64_t n,
+                         double* out_dev, void* stream);
+
+/* *out_host = sum_i |x_i| on the fixed tree with the block count of accbpg_vec_dot (L2L1Linf.extra_Psi, :801).
+ * ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_l1_norm(const double* x_dev, int64_t n, double* out_host, double* ws_dev, void* stream);
+
+/* One streaming pass, one readback: out_host[0..2] <- { <g, x-y>, (1/2)||x-y||^2, (1/2)||z-z1||^2 }, each a tree sum
+ * of its elementwise terms (g NULL: 0; z and z1 NULL together: 0).  ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_sq_ls_terms(const double* g_dev, const double* x_dev, const double* y_dev, const double* z_dev,
+                       const double* z1_dev, int64_t n, double* out_host, double* ws_dev, void* stream);
+
 /* Shannon-entropy prox maps.  kind 0: ShannonEntropy, y_dev == NULL -> exp(-g/L - 1) (accbpg/functions.py:423-429),
  * y_dev != NULL -> y*exp(-g/L) (:431-438, asserts y >= 0); kind 1: ShannonEntropyL1, the same with lamda + g
  * (:456-466); kind 2: ShannonEntropySimplex, the kind-0 result divided by its sum (:475-490, the div form asserts

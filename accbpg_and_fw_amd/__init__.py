@@ -15,8 +15,10 @@ from .functions import (RSmoothFunction, DOptimalObj, PoissonRegression, KLdivRe
                         SumOf2nd4thPowersPositiveOrthant, SquaredL2Norm, SVM_fun, PolyDiv, LogisticRegression,
                         L2L1Linf)
 from .algorithms import BPG, ABPG, ABPG_gain, ABPG_expo, ABDA, AIBM, AdaptFGM, UniversalGM, solve_theta
-from .algorithms_fw import FW_alg_div_step, FW_alg_descent_step
-from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball, lmo_l2_ball_positive_orthant
+from .algorithms_fw import (FW_alg_div_step, FW_alg_descent_step, FW_alg_L0_L1_shortest_step,
+                            FW_alg_L0_L1_shortest_step_steps, FW_l0l1_log_and_linear_step,
+                            FW_l0l1_log_and_linear_step_steps, FW_l0l1_log_only, FW_l0l1_log_only_steps)
+from .functions_lmo import lmo_simplex, lmo_l2_ball, lmo_linf_ball, lmo_l2_ball_positive_orthant, fw_direction
 from .D_opt_alg import (D_opt_FW, D_opt_FW_away, D_opt_FW_batch, D_opt_FW_away_batch, D_opt_FW_device,
                         D_opt_FW_away_device, D_opt_FW_batch_device, D_opt_FW_away_batch_device,
                         D_opt_FW_div_step, D_opt_FW_descent_step, D_opt_FW_div_step_batch,
@@ -25,7 +27,8 @@ from .D_opt_alg import (D_opt_FW, D_opt_FW_away, D_opt_FW_batch, D_opt_FW_away_b
 from .applications import (D_opt_design, D_opt_libsvm, D_opt_KYinit, D_opt_KYinit_device, D_opt_KYinit_batch,
                            Poisson_regrL1, Poisson_regrL2, KL_nonneg_regr, FrobeniusSymLossExL2Ball,
                            FrobeniusSymLossExLInfBall, FrobeniusSymLossResMeasEx, Poisson_regr_simplex,
-                           Poisson_regr_simplex_acc, svm_digits_ds_divs_ball, Logistic_regr_L2L1Linf)
+                           Poisson_regr_simplex_acc, svm_digits_ds_divs_ball, Logistic_regr_L2L1Linf, toeplitz_matrix,
+                           hard_FW_log_reg_jax, L0L1_FW_log_reg, load_a9a_data, L0L1_FW_log_reg_a9a)
 from .utils import (load_libsvm_file, random_point_on_simplex, edge_point_on_simplex, get_random_float,
                     get_random_vector, random_point_in_l2_ball, generate_dataset_for_svm)
 from .batched import (DOptimalBatch, BPG_batch, ABPG_batch, ABPG_gain_batch, ABPG_expo_batch, ABPG_expo_batch_steps,
@@ -48,5 +51,8 @@ __all__ = ["RSmoothFunction", "DOptimalObj", "PoissonRegression", "LegendreFunct
            "D_opt_FW_div_step_batch_device", "D_opt_FW_descent_step_batch_device", "SVM_fun",
            "PolyDiv", "svm_digits_ds_divs_ball", "random_point_in_l2_ball", "generate_dataset_for_svm",
            "ABPG_expo_batch", "ABPG_expo_batch_steps", "ABDA_batch", "ABDA_batch_steps",
-           "LogisticRegression", "L2L1Linf", "Logistic_regr_L2L1Linf"]
+           "LogisticRegression", "L2L1Linf", "Logistic_regr_L2L1Linf", "FW_alg_L0_L1_shortest_step",
+           "FW_alg_L0_L1_shortest_step_steps", "FW_l0l1_log_and_linear_step", "FW_l0l1_log_and_linear_step_steps",
+           "FW_l0l1_log_only", "FW_l0l1_log_only_steps", "fw_direction", "toeplitz_matrix", "hard_FW_log_reg_jax",
+           "L0L1_FW_log_reg", "load_a9a_data", "L0L1_FW_log_reg_a9a"]
 __version__ = "0.1.0"

@@ -185,6 +185,12 @@ _SIGS = {
     "accbpg_logistic_set_stream": (C.c_int, [_P, _P]),
     "accbpg_logistic_func_grad": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_double), _P]),
     "accbpg_logistic_get": (C.c_int, [_P, C.c_int, _P]),
+    "accbpg_logistic_line_begin": (C.c_int, [_P, _P]),
+    "accbpg_logistic_line_value": (C.c_int, [_P, C.c_double, C.POINTER(C.c_double)]),
+    "accbpg_logistic_line_accept": (C.c_int, [_P, C.c_double]),
+    "accbpg_logistic_func_grad_carried": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), _P]),
+    "accbpg_fw_direction": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_double, C.c_double, C.c_int64, _P, _P,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_int64), _P, _P]),
     "accbpg_l2l1linf_prox": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P]),
     "accbpg_l1_norm": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_double), _P, _P]),
     "accbpg_sq_ls_terms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), _P, _P]),

@@ -400,3 +400,126 @@ def Logistic_regr_L2L1Linf(m, n, lamda=None, B=1, randseed=-1, labels=None):
     L = 0.25
     x0 = np.zeros(n)
     return f, h, L, x0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Logistic regression instances for the (L0, L1) Frank-Wolfe solvers (accbpg/applications.py:432-701).  The reference
+# draws with jax.random; this package draws with NumPy, so the construction is the reference's and the numbers are
+# not: ``key`` is an int seed or a np.random.RandomState, used for every draw in the order of the reference's code.
+# ---------------------------------------------------------------------------------------------------------------
+def toeplitz_matrix(n_features, rho):
+    """The n x n matrix rho^|i-j| (accbpg/applications.py:432-434)."""
+    idx = np.arange(n_features)
+    return rho ** np.abs(idx[:, None] - idx[None, :])
+
+
+def _rng_of(key):
+    return key if isinstance(key, np.random.RandomState) else np.random.RandomState(int(key))
+
+
+def _correlated_rows(rng, n_samples, n_features, rho):
+    """Z L^T with Z ~ N(0, I) and L the lower Cholesky factor of toeplitz_matrix(n_features, rho)."""
+    chol = np.linalg.cholesky(toeplitz_matrix(n_features, rho))
+    return rng.standard_normal((n_samples, n_features)) @ chol.T
+
+
+def _row_norm_constants(X):
+    """(L, L1) = (max row norm squared, max row norm)"""
+    L1 = np.max(np.linalg.norm(X, axis=1))
+    return L1 ** 2, L1
+
+
+def L0L1_FW_log_reg(key, n_samples, n_features, ball_constrnt_radius, solution_spread_radius_btm=0.91,
+                    solution_spread_radius_up=0.96, noise=0.0, rho=0.98):
+    """The older generator (accbpg/applications.py:437-499): Toeplitz-correlated Gaussian rows, column j scaled by
+    3^j, labels sign(X w + noise * N(0, 1)) (0 counted as +1) for a w at 0.91 to 0.96 of the radius from the origin,
+    x0 = 1e-6 in every entry.  Returns f, h = SquaredL2Norm(), L, L0 = 1e-9, L1, x0 with L1 the largest row norm and
+    L = L1^2.  ``key`` is an int seed or a RandomState and the draws are NumPy's (rows, direction, radius, noise), so
+    the construction is the reference's and the numbers are not."""
+    rng = _rng_of(key)
+    x0 = np.zeros(n_features) + 1e-6
+    assert np.linalg.norm(x0, 2) <= ball_constrnt_radius
+    assert np.linalg.norm(x0, np.inf) <= ball_constrnt_radius
+    X = _correlated_rows(rng, n_samples, n_features, rho)
+    X = X * (3.0 ** np.arange(n_features))[None, :]
+    direction = rng.standard_normal(n_features)
+    direction /= np.linalg.norm(direction)
+    true_omega = rng.uniform(ball_constrnt_radius * solution_spread_radius_btm,
+                             ball_constrnt_radius * solution_spread_radius_up) * direction
+    print("radius is", ball_constrnt_radius)
+    print("true omega radius is", float(np.linalg.norm(true_omega, 2)))
+    assert np.linalg.norm(true_omega, 2) <= ball_constrnt_radius
+    assert np.linalg.norm(true_omega, np.inf) <= ball_constrnt_radius
+    y = np.sign(X @ true_omega + noise * rng.standard_normal(n_samples))
+    y = np.where(y == 0, 1.0, y)
+    print("ratio positive labels:", float(np.sum(y == 1) / y.shape[0]))
+    L, L1 = _row_norm_constants(X)
+    return LogisticRegression(X, y), SquaredL2Norm(), L, 1e-9, L1, x0
+
+
+def hard_FW_log_reg_jax(key, n_samples, n_features, radius=1.0, domain="l1", k_sparse=5, rho=0.95, col_scale=10.0,
+                        flip_y=0.0, margin=0.5, class_bias=0.0, x0_mode="center", noise=0.01):
+    """An ill-conditioned logistic regression instance on a norm ball or the simplex (accbpg/applications.py:502-658):
+    Toeplitz-correlated Gaussian rows, columns scaled by col_scale^linspace(0, 1, n), a planted vector in the domain
+    (``domain`` "l1" or "simplex": k_sparse positive entries of sum radius; "linf": +-radius; anything else, "l2": on
+    the sphere), labels sign(margin * X w + class_bias + noise * N(0, 1)) with a fraction flip_y flipped and 0 counted
+    as +1, x0 the origin or (x0_mode other than "center", "l1" / "simplex" only) a vertex.  Returns f, h, L, L0 = 1e-12,
+    L1, x0, X, y with L1 the largest row norm and L = L1^2.  ``key`` is an int seed or a RandomState and the draws are
+    NumPy's, in the order of the reference's code, so the construction is the reference's and the numbers are not."""
+    rng = _rng_of(key)
+    X = _correlated_rows(rng, n_samples, n_features, rho)
+    X = X * (col_scale ** np.linspace(0, 1, n_features))[None, :]
+    if domain in ("l1", "simplex"):
+        true_omega = np.zeros(n_features)
+        supp = rng.choice(n_features, size=min(k_sparse, n_features), replace=False)
+        vals = rng.uniform(0.5, 1.0, size=supp.shape[0])
+        true_omega[supp] = vals / np.sum(np.abs(vals)) * radius
+        if domain == "simplex":
+            true_omega = np.abs(true_omega)
+            true_omega = true_omega / np.sum(true_omega) * radius
+    elif domain == "linf":
+        true_omega = rng.choice(np.array([-1.0, 1.0]), size=n_features) * radius
+    else:
+        v = rng.standard_normal(n_features)
+        true_omega = radius * (v / (np.linalg.norm(v, 2) + 1e-12))
+    logits = margin * (X @ true_omega) + class_bias
+    y = np.sign(logits + noise * rng.standard_normal(n_samples))
+    if flip_y > 0:
+        y = np.where(rng.uniform(size=n_samples) < flip_y, -y, y)
+    y = np.where(y == 0, 1.0, y)
+    x0 = np.zeros(n_features)
+    if domain in ("l1", "simplex") and x0_mode != "center":
+        x0[rng.randint(0, n_features)] = radius
+    L, L1 = _row_norm_constants(X)
+    return LogisticRegression(X, y), SquaredL2Norm(), L, 1e-12, L1, x0, X, y
+
+
+def load_a9a_data(path, bias=True):
+    """(X, y) of a LIBSVM file such as a9a (accbpg/applications.py:661-672) through this package's load_libsvm_file:
+    the dense feature matrix, a column of ones appended when ``bias``, and the labels mapped to -1 (label <= 0) / +1."""
+    X_sparse, y = load_libsvm_file(path)
+    X = X_sparse.toarray()
+    if bias:
+        X = np.hstack([X, np.ones((X.shape[0], 1))])
+    return X, np.where(y <= 0, -1, 1)
+
+
+def L0L1_FW_log_reg_a9a(ball_constrnt_radius, path):
+    """Logistic regression on a LIBSVM file for the (L0, L1) Frank-Wolfe solvers (accbpg/applications.py:675-701): the
+    columns of load_a9a_data(path) are standardised in place with their mean and population standard deviation -- a
+    column of zero variance, the bias among them, keeps the scale 1 and becomes 0 --, x0 is drawn from
+    np.random.uniform(-0.5, 0.5, n) (the global generator, as in the reference) and scaled into the l2 and the
+    l-infinity ball of the given radius.  Returns f, h = SquaredL2Norm(), L, L0 = 1e-9, L1, x0."""
+    X, y = load_a9a_data(path=path)
+    X = X.astype(np.float64, copy=False)
+    mean, std = X.mean(axis=0), X.std(axis=0)
+    std[std == 0.0] = 1.0
+    X -= mean
+    X /= std
+    n_features = X.shape[1]
+    x0 = np.random.uniform(low=-0.5, high=0.5, size=n_features)
+    x0 = x0 / max(np.linalg.norm(x0, 2) / ball_constrnt_radius, np.linalg.norm(x0, np.inf) / ball_constrnt_radius, 1.0)
+    assert np.linalg.norm(x0, 2) <= ball_constrnt_radius
+    assert np.linalg.norm(x0, np.inf) <= ball_constrnt_radius
+    L, L1 = _row_norm_constants(X)
+    return LogisticRegression(X, y), SquaredL2Norm(), L, 1e-9, L1, x0

@@ -8,6 +8,7 @@
 // expressions with separate NumPy ufuncs (one rounding per operation), so no multiply-add here
 // may be fused.  Replaces accbpg/functions.py:246-271 and 336-356.
 #include <atomic>
+#include <cstring>
 #include <mutex>
 
 #include "internal.h"
@@ -584,6 +585,101 @@ __global__ __launch_bounds__(RB) void minmax_final_kernel(const MinMaxRec* __res
 }
 
 // -----------------------------------------------------------------------------------------
+// The Frank-Wolfe direction of a gradient g at x in two phases (accbpg_fw_direction): what lmo(g), s - x, <g, g>,
+// <g, s - x> and <s - x, s - x> compute in five launches with a read-back each.
+//   phase 1  sum g^2 (the terms and the tree of dot_partial_kernel) and the first-index argmin of g; the final stage
+//            leaves {sum g^2, min g, argmin as int64 bits, 1.0 when sqrt(sum g^2) < 1e-10} in four device doubles
+//   phase 2  s from those scalars, d = s - x, and the sums <g, d>, sum d^2, sum (s - c)^2
+// Every elementwise operation is the one of the kernel it replaces: lmo_l2_kernel / lmo_linf_kernel
+// (quartic_kernels.hip), vertex_kernel, axpby_kernel with a = 1, b = -1 (1*s and -1*x are exact, so p + q is s - x).
+constexpr int FWD_L2 = 0, FWD_LINF = 1, FWD_SIMPLEX = 2;
+constexpr double FWD_FILL = 1e-15;         // the simplex vertex's other entries (functions_lmo.py:152)
+constexpr double FWD_TINY = 1e-10;         // ||g|| below this: the l2 ball's centre (functions_lmo.py:37)
+
+// part: nb block sums of g^2, then (from part + RMAXBLK) nb pairs {min g, argmin bits}
+__global__ __launch_bounds__(RB) void fw_dir_scan_kernel(const double* __restrict__ g, int64_t n,
+                                                        double* __restrict__ part) {
+    __shared__ MinMaxRec sh[RB / 64];
+    const double inf = __builtin_inf();
+    MinMaxRec a{inf, -inf, INT64_MAX, INT64_MAX};
+    double s = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * RB;
+    for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
+        const double v = g[i];
+        s += v * v;
+        a = mm_merge(a, MinMaxRec{v, v, i, i});
+    }
+    a = mm_block(a, sh);
+    double v[1] = {s};
+    block_reduce_store<RB, 1, false>(v, part + blockIdx.x);
+    if (threadIdx.x == 0) {
+        part[RMAXBLK + 2 * blockIdx.x] = a.vmin;
+        part[RMAXBLK + 2 * blockIdx.x + 1] = __longlong_as_double((long long)a.imin);
+    }
+}
+__global__ __launch_bounds__(RB) void fw_dir_scan_final_kernel(const double* __restrict__ part, int nb,
+                                                              double* __restrict__ scal) {
+    __shared__ MinMaxRec sh[RB / 64];
+    const double inf = __builtin_inf();
+    MinMaxRec a{inf, -inf, INT64_MAX, INT64_MAX};
+    for (int b = threadIdx.x; b < nb; b += RB) {
+        const double v = part[RMAXBLK + 2 * b];
+        const int64_t i = (int64_t)__double_as_longlong(part[RMAXBLK + 2 * b + 1]);
+        a = mm_merge(a, MinMaxRec{v, v, i, i});
+    }
+    a = mm_block(a, sh);
+    __shared__ double tot[1];
+    reduce_final_body<RB, 1, false>(part, nb, tot);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        scal[0] = tot[0];
+        scal[1] = a.vmin;
+        scal[2] = __longlong_as_double((long long)a.imin);
+        scal[3] = (sqrt(tot[0]) < FWD_TINY) ? 1.0 : 0.0;     // a NaN norm is not small: NaN goes through, as on the host
+    }
+}
+// slots: 0 <g, d>, 1 sum d^2, 2 sum (s - c)^2 (l2 ball away from the centre, else 0)
+__global__ __launch_bounds__(RB) void fw_dir_form_kernel(int lmo, const double* __restrict__ g,
+                                                        const double* __restrict__ x, int kind,
+                                                        const double* __restrict__ c, double cval, double radius,
+                                                        const double* __restrict__ scal, int64_t n,
+                                                        double* __restrict__ s_out, double* __restrict__ d_out,
+                                                        double* __restrict__ part) {
+    const double gnorm = sqrt(scal[0]);
+    const int64_t imin = (int64_t)__double_as_longlong(scal[2]);
+    const bool centre = scal[3] != 0.0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * RB;
+    for (int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x; i < n; i += stride) {
+        const double gi = g[i];
+        double si;
+        if (lmo == FWD_SIMPLEX) {
+            si = (i == imin) ? radius : FWD_FILL;
+        } else {
+            const double ci = kind == 1 ? c[i] : cval;
+            if (lmo == FWD_LINF) {
+                const double sg = gi > 0.0 ? 1.0 : (gi < 0.0 ? -1.0 : gi);
+                si = ci - radius * sg;
+            } else if (centre) {
+                si = ci;
+            } else {
+                const double t = (radius * gi) / gnorm;
+                si = ci - t;
+                const double e = si - ci;
+                s2 += e * e;
+            }
+        }
+        const double di = si - x[i];
+        s_out[i] = si;
+        d_out[i] = di;
+        s0 += gi * di;
+        s1 += di * di;
+    }
+    double v[3] = {s0, s1, s2};
+    block_reduce_store<RB, 3, false, 4>(v, part + blockIdx.x * 4);
+}
+
+// -----------------------------------------------------------------------------------------
 // Scratch of the handle-free entry points: one block per (host thread, device) -- instances of a batch are
 // driven from separate threads on separate streams, and one thread may drive several GPUs.  A block goes back
 // to a per-device pool when its thread ends and is handed to the next thread that asks, so generations of
@@ -921,6 +1017,43 @@ extern "C" int accbpg_vec_argminmax(const double* x_dev, int64_t n, int64_t* idx
     idx_host[0] = r->imin;
     idx_host[1] = r->imax;
     if (val_host) { val_host[0] = r->vmin; val_host[1] = r->vmax; }
+    return ACCBPG_OK;
+}
+
+extern "C" int accbpg_fw_direction(const double* g_dev, const double* x_dev, int lmo_kind, int center_kind,
+                                   const double* center_dev, double center_val, double radius, int64_t n,
+                                   double* s_out_dev, double* d_out_dev, double* out5_host, int64_t* idx_host,
+                                   double* ws_dev, void* stream) {
+    if (!g_dev || !x_dev || !s_out_dev || !d_out_dev || !out5_host || !idx_host || !ws_dev || n <= 0) return ACCBPG_ERR_ARG;
+    if (lmo_kind < FWD_L2 || lmo_kind > FWD_SIMPLEX || center_kind < 0 || center_kind > 1) return ACCBPG_ERR_ARG;
+    if (lmo_kind != FWD_SIMPLEX && center_kind == 1 && !center_dev) return ACCBPG_ERR_ARG;
+    if (s_out_dev == d_out_dev || s_out_dev == g_dev || s_out_dev == x_dev || d_out_dev == g_dev || d_out_dev == x_dev)
+        return ACCBPG_ERR_ARG;
+    ACC_TRY(ensure_scratch());
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = red_blocks(n, RMAXBLK);
+    double* part = ws_dev + n;                                  // 3 * RMAXBLK doubles of phase 1, then 4 * nb of phase 2
+    double* scal = g_out + 4;
+    fw_dir_scan_kernel<<<nb, RB, 0, s>>>(g_dev, n, part);
+    fw_dir_scan_final_kernel<<<1, RB, 0, s>>>(part, nb, scal);
+    fw_dir_form_kernel<<<nb, RB, 0, s>>>(lmo_kind, g_dev, x_dev, center_kind, center_dev, center_val, radius, scal, n,
+                                         s_out_dev, d_out_dev, part);
+    // one final stage, one copy of {<g,d>, sum d^2, sum (s-c)^2, -, sum g^2, min g, argmin, centre} and one wait
+    const double* o = reduce_finish(ls_terms_final_kernel, part, nb, g_out, g_out, 8, g_pin, s);
+    if (!o) return ACCBPG_ERR_HIP;
+    const bool centre = o[7] != 0.0;
+    out5_host[0] = o[4];
+    out5_host[1] = o[0];
+    out5_host[2] = o[1];
+    out5_host[3] = (lmo_kind == FWD_L2 && !centre) ? sqrt(o[2]) : 0.0;
+    out5_host[4] = centre ? 1.0 : 0.0;
+    int64_t imin;
+    memcpy(&imin, &o[6], sizeof(imin));
+    idx_host[0] = imin;
+    if (lmo_kind == FWD_L2 && !centre && !(fabs(out5_host[3] - radius) <= 1e-10)) {    // functions_lmo.py:45-46
+        set_last_error("Solution does not lie on ball boundary");
+        return ACCBPG_ERR_ASSERT;
+    }
     return ACCBPG_OK;
 }
 

@@ -820,6 +820,45 @@ class LogisticRegression(RSmoothFunction):
             return from_dev(g, was_np)
         return sum_t / self.m, from_dev(g, was_np)
 
+    # Margins along a segment.  After func_grad(x) the handle holds X x with its losses and weights; X (x + a d) is
+    # X x + a (X d), so after one pass for X d every value on the segment, and the accepted point's rows, cost O(m).
+    # A func_grad rebases the margins to its argument; the calls below raise ValueError on a handle that has none.
+    def _line(self, name, *args):
+        with torch.cuda.device(self._A.device):
+            self._lib.accbpg_logistic_set_stream(self._h, _stream())
+            rc = getattr(self._lib, name)(self._h, *args)
+        _lib.check(rc, name)
+
+    def line_begin(self, d):
+        """Starts the segment x + a d from the point of the last func_grad (or line_accept): one pass for X d."""
+        size = d.numel() if isinstance(d, torch.Tensor) else d.size
+        assert size == self.n, "Logistic Regression: d.size not equal to n"
+        dd, _ = to_dev(d)
+        self._line("accbpg_logistic_line_begin", _ptr(dd.reshape(-1)))
+
+    def line_value(self, a):
+        """f(x + a d) from the carried margins fma(a, (X d)_i, (X x)_i); fitted(), losses() and weights() stay."""
+        fval = (C.c_double * 1)(0.0)
+        self._line("accbpg_logistic_line_value", float(a), fval)
+        return np.float64(fval[0]) / self.m
+
+    def line_accept(self, a):
+        """Moves the handle's margins, losses and weights to x + a d; the next segment needs a new line_begin."""
+        self._line("accbpg_logistic_line_accept", float(a))
+
+    def func_grad_carried(self, flag=2, as_numpy=False):
+        """func_grad at the point the handle's margins stand for, without the pass for X x: the value is the sum of
+        the carried losses, the gradient X^T r / m.  The gradient is a CUDA tensor unless ``as_numpy``."""
+        assert flag in (0, 1, 2), "Logistic Regression: flag must be 0, 1 or 2."
+        g = torch.empty(self.n, dtype=torch.float64, device=self._A.device) if flag != 0 else None
+        fval = (C.c_double * 1)(0.0)
+        self._line("accbpg_logistic_func_grad_carried", int(flag), fval, _ptr(g))
+        if flag == 0:
+            return np.float64(fval[0]) / self.m
+        if flag == 1:
+            return from_dev(g, as_numpy)
+        return np.float64(fval[0]) / self.m, from_dev(g, as_numpy)
+
     def _get(self, which):
         out = torch.empty(self.m, dtype=torch.float64, device=self._A.device)
         with torch.cuda.device(self._A.device):

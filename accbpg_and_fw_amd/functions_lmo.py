@@ -13,6 +13,42 @@ from . import _lib
 from .functions import _Workspace, _ptr, _stream, from_dev, to_dev, vec_argminmax, vec_dot, vec_vertex
 
 
+LMO_L2, LMO_LINF, LMO_SIMPLEX = 0, 1, 2      # the lmo_kind of accbpg_fw_direction
+
+
+class _Lmo:
+    """An oracle of this module: the callable g -> s it has always been, which also says what it is -- ``kind`` (one of
+    LMO_L2, LMO_LINF, LMO_SIMPLEX), ``radius`` and ``center`` (a _Center, None for the simplex) -- so that a solver can
+    hand the whole direction step to ``fw_direction``."""
+
+    def __init__(self, call, kind, radius, center):
+        self._call, self.kind, self.radius, self.center = call, kind, radius, center
+
+    def __call__(self, g):
+        return self._call(g)
+
+
+def fw_direction(lmo, g, x):
+    """(s, d, gg, slope, dd, index, dist) for an oracle of this module: s = lmo(g), d = s - x, gg = sum g^2,
+    slope = <g, d>, dd = sum d^2, the simplex vertex's index and the l2 ball's ||s - c|| (0.0 for the other oracles and
+    for the ball's centre), in one call with one read-back (accbpg_fw_direction).  g and x are CUDA tensors of the same
+    shape; s and d have that shape.  Entry by entry and sum by sum the result has the bits of lmo(g),
+    vec_axpby(1, s, -1, x) and vec_dot on them."""
+    assert isinstance(lmo, _Lmo), "fw_direction: not an oracle of functions_lmo"
+    gd, xd = g.contiguous(), x.contiguous()
+    assert gd.shape == xd.shape, "fw_direction: g and x not same shape."
+    kind, cd, val = (0, None, 0.0) if lmo.center is None else lmo.center.args(gd)
+    n = gd.numel()
+    s, d = torch.empty_like(gd), torch.empty_like(gd)
+    out, idx = (C.c_double * 5)(), (C.c_int64 * 1)()
+    with torch.cuda.device(gd.device):
+        ws = _Workspace.get(n, gd.device)
+        rc = _lib.load().accbpg_fw_direction(_ptr(gd), _ptr(xd), lmo.kind, kind, _ptr(cd), val, float(lmo.radius), n,
+                                             _ptr(s), _ptr(d), out, idx, _ptr(ws), _stream())
+    _lib.check(rc, "accbpg_fw_direction", "Solution does not lie on ball boundary")
+    return s, d, np.float64(out[0]), np.float64(out[1]), np.float64(out[2]), int(idx[0]), out[3]
+
+
 def lmo_simplex(radius=1):
     """Returns g -> s with s[i] = 1e-15 and s[first argmin g] = radius (NumPy in, NumPy out; CUDA
     tensor in, CUDA tensor out: first-index argmin and the fill run on the device)."""
@@ -20,7 +56,7 @@ def lmo_simplex(radius=1):
         gd, was_np = to_dev(g)
         imin, _, _, _ = vec_argminmax(gd)
         return from_dev(vec_vertex(imin, radius, 1e-15, gd.numel(), gd.device), was_np)
-    return vertex
+    return _Lmo(vertex, LMO_SIMPLEX, radius, None)
 
 
 class _Center:
@@ -72,7 +108,7 @@ def lmo_l2_ball(radius, center=None):
         _lib.check(rc, "accbpg_lmo_l2_ball", "Solution does not lie on ball boundary")
         return from_dev(out, was_np)
 
-    return lambda g: f(g)
+    return _Lmo(f, LMO_L2, radius, cen)
 
 
 def lmo_linf_ball(radius, center=None):
@@ -90,7 +126,7 @@ def lmo_linf_ball(radius, center=None):
         _lib.check(rc, "accbpg_lmo_linf_ball")
         return from_dev(out, was_np)
 
-    return lambda g: f(g)
+    return _Lmo(f, LMO_LINF, radius, cen)
 
 
 def lmo_l2_ball_positive_orthant(radius, center=None, epsilon=0.0):

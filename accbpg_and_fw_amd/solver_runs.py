@@ -3,6 +3,8 @@ solvers of ``algorithms.py`` and the lock-step batches of ``batched.py``, as ``_
 Frank-Wolfe solvers.  A run object is one instance's scalars, result arrays and last iteration; it touches no device
 and no vector -- the caller does that work and hands over the numbers -- so the CPU tests drive it with NumPy
 (tests/test_solver_runs_cpu.py).  Every expression keeps the reference's operation order; the cited lines are its."""
+import math
+
 import numpy as np
 
 
@@ -276,3 +278,207 @@ class _ABDARun(_Accelerated):
         self.dzz = dzz
         self.G[self.k] = dxy / dzz / self.theta ** self.gamma
         return self.G[self.k]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The (L0, L1) Frank-Wolfe family (accbpg/algorithms_fw.py:78-207, :250-349, :352-453).  A run object takes the
+# scalars of an iteration -- f(x), ||g||, <g, d>, and D(s, x) or ||d|| -- and decides: the division of L0 and L1 in
+# front of a search, the step, the acceptance test, which constant grows when it fails, their caps, the records and the
+# stop test.  The traces are lists, as in the reference: LOG_STEPS gains an entry per trial.  ``lhs`` and ``rhs`` are
+# the two sides of the last acceptance test.  Arguments are taken as NumPy scalars and math / NumPy routines are the
+# reference's, so that the bits are.
+# ---------------------------------------------------------------------------------------------------------------
+_L0L1_BAND = 1e-8           # the slopes in (0, band] counted as 0, and the stand-in for a vanishing divergence
+
+
+class _L0L1Run:
+    lo_message = "Initial L0 and L1 must be positive"
+    slope_message = "grad_d_prod must be non-positive (we minimize)"
+
+    def __init__(self, L0, L1, epsilon, linesearch, ls_ratio):
+        for bad, message in ((ls_ratio < 1, "ls_ratio must be >= 1"),
+                             (self.bad_start(L0, L1), self.lo_message),
+                             (epsilon <= 0, "epsilon must be positive")):
+            if bad:
+                raise ValueError(message)
+        self.L0, self.L1, self.epsilon, self.linesearch, self.ls_ratio = L0, L1, epsilon, linesearch, ls_ratio
+        self.F, self.Ls, self.T = [], [], []
+        self.k, self.toggle = -1, 0
+        self.lhs = self.rhs = None
+
+    @staticmethod
+    def bad_start(L0, L1):
+        return L0 <= 0 or L1 <= 0
+
+    def begin(self, k, fx, Fk, now):
+        """Iteration k with f(x) = fx and F(x) = Fk known at time ``now``."""
+        self.k, self.fx = k, fx
+        self.F.append(Fk)
+        self.T.append(now)
+
+    def banded(self, slope):
+        """<g, d> with the band (0, 1e-8] set to the integer 0; a larger one is the oracle's fault."""
+        if 0 < slope <= _L0L1_BAND:
+            slope = 0
+        if slope > 0:
+            raise ValueError(self.slope_message)
+        return slope
+
+    def decide(self, ft, rhs):
+        self.lhs, self.rhs = ft, rhs
+        return ft <= rhs
+
+    def finish(self):
+        """Records a_k; True when the stop test holds."""
+        self.Ls.append(self.a_k)
+        return self.k > 0 and bool(abs(self.F[self.k] - self.F[self.k - 1]) < self.epsilon)
+
+    def result(self, x):
+        return x, np.array(self.F), np.array(self.Ls), np.array(self.T)
+
+
+class _ShortestStepRun(_L0L1Run):
+    """One instance of FW_alg_L0_L1_shortest_step (:78-207).
+
+    Quirks kept: ``L0 /= ls_ratio + L0 / a_k`` divides by the whole sum (:175-176) and ``L0 *= ls_ratio - L0 / a_k``
+    multiplies by the whole difference (:192, :195); the toggle that picks the constant to grow lives across
+    iterations (:153); a divergence of exactly 0 becomes 1e-8 (:162-163); zero constants are allowed and the message
+    for negative ones says "positive" (:138-139)."""
+    lo_message = "Initial L must be positive"
+    slope_message = "⟨∇f(x), d⟩ must be nonpositive (LMO issue)."
+
+    def __init__(self, L0, L1, gamma, epsilon, linesearch, ls_ratio):
+        super().__init__(L0, L1, epsilon, linesearch, ls_ratio)
+        self.gamma = gamma
+
+    @staticmethod
+    def bad_start(L0, L1):
+        return L0 < 0 or L1 < 0
+
+    def direction(self, gnorm, slope, div):
+        """||g||, <g, d> and D(s, x) of the iteration; divides L0 and L1 in front of a search (:174-176)."""
+        if div == 0:
+            div = _L0L1_BAND
+        self.gnorm, self.div, self.slope = gnorm, div, self.banded(slope)
+        a_k = self.L0 + self.L1 * gnorm
+        if self.linesearch:
+            self.L0 /= self.ls_ratio + self.L0 / a_k
+            self.L1 /= self.ls_ratio + (self.L1 * gnorm) / a_k
+        return True
+
+    def step(self):
+        """The step of a trial with the current constants (:179-182)."""
+        self.a_k = self.L0 + self.L1 * self.gnorm
+        self.alpha = min((-self.slope / (self.a_k * self.div * np.e)) ** (1 / (self.gamma - 1)), 1)
+        return self.alpha
+
+    def accepts(self, ft):
+        """The test of the trial's value ft (:188); the constant the toggle names grows when it fails (:191-196)."""
+        a, a_k = self.alpha, self.a_k
+        if self.decide(ft, self.fx + a * self.slope + a ** self.gamma * (a_k / 2) * np.e * self.div):
+            return True
+        if self.toggle == 0:
+            self.L0 *= self.ls_ratio - self.L0 / a_k
+            self.toggle = 1
+        else:
+            self.L1 *= self.ls_ratio - (self.L1 * self.gnorm) / a_k
+            self.toggle = 0
+        return False
+
+
+class _LogStepRun(_L0L1Run):
+    """What FW_l0l1_log_and_linear_step and FW_l0l1_log_only share: LOG_STEPS, which starts with a 0 and gains an entry
+    per trial (:304-305, :314, :317), the caps, which are tested for truth so that a cap of 0 is no cap (:336-337), the
+    model exp(z) - 1 - z of the acceptance test with 0.5 z^2 in its place from z = 50 on (:326-332), and the ending at
+    d = 0: the reference divides by ||d|| = 0 there and goes on with NaN; ``direction`` returns False and the run ends
+    with what has been recorded -- F and T have that iteration's entry, Ls has not."""
+
+    def __init__(self, L0, L1, ls_ratio, epsilon, L0_max, L1_max, linesearch):
+        super().__init__(L0, L1, epsilon, linesearch, ls_ratio)
+        self.L0_max, self.L1_max = L0_max, L1_max
+        self.LOG_STEPS = []
+
+    def direction(self, gnorm, slope, dnorm):
+        """||g||, <g, d> and ||d|| of the iteration; False at d = 0.  Divides L0 and L1 in front of a search."""
+        self.gnorm, self.dnorm, self.slope = gnorm, dnorm, self.banded(slope)
+        if self.k == 0:
+            self.LOG_STEPS.append(0)
+        if dnorm == 0:
+            return False
+        if self.linesearch:
+            self.L0 /= self.ls_ratio
+            self.L1 /= self.ls_ratio
+        self.floor_L1()
+        return True
+
+    def floor_L1(self):
+        pass
+
+    def grown(self, L, cap):
+        return min(L * self.ls_ratio, cap) if cap else L * self.ls_ratio
+
+    def accepts(self, ft):
+        """The test of the trial's value ft (:326-333); ``grow`` when it fails."""
+        z = self.L1 * self.alpha * self.dnorm
+        if z < 50:
+            exp_term = np.expm1(z) - z
+        else:
+            exp_term = 0.5 * z**2
+        if self.decide(ft, self.fx + self.alpha * self.slope + (self.a_k / self.L1**2) * exp_term):
+            return True
+        self.grow()
+        self.a_k = self.L0 + self.L1 * self.gnorm
+        return False
+
+    def result(self, x):
+        return x, np.array(self.F), np.array(self.Ls), np.array(self.LOG_STEPS), np.array(self.T)
+
+
+class _LogLinearRun(_LogStepRun):
+    """One instance of FW_l0l1_log_and_linear_step (:250-349): the logarithmic step when L1 ||d|| >= log 2 (np.log),
+    the linear one below; both constants grow on a failed test."""
+
+    def step(self):
+        assert self.L0 >= 0 and self.L1 >= 0, "Smoothness parameters must stay positive"
+        L1, d_norm, slope = self.L1, self.dnorm, self.slope
+        self.a_k = a_k = self.L0 + L1 * self.gnorm
+        if L1 * d_norm >= np.log(2):
+            self.alpha = (1 / (L1 * d_norm)) * np.log(1 - (L1 * slope) / (a_k * d_norm))
+            self.LOG_STEPS.append(self.LOG_STEPS[-1] + 1)
+        else:
+            self.alpha = L1 * (-slope) / (a_k * d_norm)
+            self.LOG_STEPS.append(self.LOG_STEPS[-1])
+        return self.alpha
+
+    def grow(self):
+        self.L0 = self.grown(self.L0, self.L0_max)
+        self.L1 = self.grown(self.L1, self.L1_max)
+
+
+class _LogOnlyRun(_LogStepRun):
+    """One instance of FW_l0l1_log_only (:352-453): L1 is lifted to log 2 / ||d|| after the division (:402), so every
+    step is the logarithmic one (math.log); a failed test grows L0 and L1 in turn, the toggle living across
+    iterations (:378)."""
+
+    def floor_L1(self):
+        self.L1 = max(math.log(2) / self.dnorm, self.L1)
+
+    def step(self):
+        assert self.L0 >= 0 and self.L1 >= 0, "Smoothness parameters must stay positive"
+        L1, d_norm, slope = self.L1, self.dnorm, self.slope
+        self.a_k = a_k = self.L0 + L1 * self.gnorm
+        z = L1 * d_norm
+        if z >= math.log(2) - 1e-5:
+            self.alpha = (1 / (L1 * d_norm)) * math.log(1 - (L1 * slope) / (a_k * d_norm))
+            self.LOG_STEPS.append(self.LOG_STEPS[-1] + 1)
+        else:
+            assert False, "No use for the second step!"
+        return self.alpha
+
+    def grow(self):
+        if self.toggle == 0:
+            self.L0 = self.grown(self.L0, self.L0_max)
+            self.toggle = 1
+        else:
+            self.L1 = self.grown(self.L1, self.L1_max)
+            self.toggle = 0

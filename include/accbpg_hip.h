@@ -699,6 +699,31 @@ int accbpg_logistic_func_grad(accbpg_logistic* h, const double* x_dev, int flag,
 /* out_dev <- a length-m vector of the last evaluation: which 0 -> A x, 1 -> t, 2 -> r. */
 int accbpg_logistic_get(accbpg_logistic* h, int which, double* out_dev);
 
+/* Margins along a segment x + a d.  After a func_grad at x the handle holds z = A x with its t and r.
+ * line_begin: w <- A d in one pass over A (the A x kernel of func_grad with a plain store).
+ * line_value: f_host[0] <- sum_i t(fma(a, w_i, z_i)) on the fixed tree, O(m); z, t and r stay as they are.
+ * line_accept: z_i <- fma(a, w_i, z_i) with its t_i and r_i, O(m); w is spent, the next line begins anew.
+ * func_grad_carried: flag as in func_grad, from the handle's current z, t and r: the sum of t, and A^T r / m.
+ * A func_grad rebases the margins to its x and spends w.  ACCBPG_ERR_ARG on a handle whose margins (or whose w, for
+ * line_value and line_accept) are not current. */
+int accbpg_logistic_line_begin(accbpg_logistic* h, const double* d_dev);
+int accbpg_logistic_line_value(accbpg_logistic* h, double a, double* f_host);
+int accbpg_logistic_line_accept(accbpg_logistic* h, double a);
+int accbpg_logistic_func_grad_carried(accbpg_logistic* h, int flag, double* f_host, double* g_dev);
+
+/* The Frank-Wolfe direction at x for the gradient g (length n, an n x r iterate flat): s_out_dev <- lmo(g),
+ * d_out_dev <- s - x, out5_host <- {sum g^2, <g, d>, sum d^2, ||s - c|| (l2 ball away from its centre, else 0),
+ * 1.0 when the l2 ball returned its centre}, idx_host[0] <- the first argmin of g (the simplex vertex), with one
+ * synchronisation.  lmo_kind 0: the l2 ball, s = c - (radius*g)/||g||, the centre itself when ||g|| < 1e-10, decided
+ * on the device; 1: the l-infinity ball, s = c - radius*sign(g); 2: the simplex, s = 1e-15 with s[argmin] = radius.
+ * The centre as in accbpg_lmo_l2_ball (ignored by the simplex).  Entry by entry s and d have the bits of
+ * accbpg_lmo_* / accbpg_vec_vertex followed by accbpg_vec_axpby(1, s, -1, x), and the three sums those of
+ * accbpg_vec_dot on them.  Returns ACCBPG_ERR_ASSERT when | ||s - c|| - radius | > 1e-10 on the l2 ball.  The outputs
+ * must not alias each other or the inputs.  ws_dev: accbpg_vec_workspace_doubles(n) doubles. */
+int accbpg_fw_direction(const double* g_dev, const double* x_dev, int lmo_kind, int center_kind,
+                        const double* center_dev, double center_val, double radius, int64_t n, double* s_out_dev,
+                        double* d_out_dev, double* out5_host, int64_t* idx_host, double* ws_dev, void* stream);
+
 /* L2L1Linf.prox_map (y_dev NULL) and div_prox_map (accbpg/functions.py:817-835) in one elementwise launch and the
  * reference's operation order: w = g - L*y, v = -((1/L)*w), thr = lamda/L; |v| <= thr -> +0.0, v > thr -> v - thr,
  * v < -thr -> v + thr; clipped to [-B, B], a NaN kept.  L <= 0 returns ACCBPG_ERR_ASSERT. */

@@ -148,6 +148,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void gram_streamk_kernel(
 // counted vmcnt + raw barrier, x applied to the A fragments after the LDS read.
 // GV (timing ablations only): bit 0 = no loads inside the k-loop, bit 1 = no wait + barrier,
 // bit 2 = no fragment reads, bit 3 = barrier without the vmcnt wait, bit 4 = half of the fragment reads.
+// GV (schedules): 32 = dealt out between the MFMA pairs, 64 = placement B, 128 / 256 = loads two / four to an M0 write,
+// 512 = the stage of every k-step a compile-time constant (with 32 | 64 | 128; takes the ablation bits 0..2).
 template <class T, int GV = 0>
 __device__ __forceinline__ void gram_streamk_glds_body(
     const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n, const double* __restrict__ x,
@@ -233,8 +235,20 @@ __device__ __forceinline__ void gram_streamk_glds_body(
             t.glds_x(x, ks * BK, st);
         };
         __builtin_amdgcn_s_barrier();                           // previous segment's readers are done
-        issue(kb, 0);
-        issue(min(kb + 1, klast), 1);
+        if constexpr (GV & 512) {
+            // (the x pieces through the statement the loop uses: no LDS-DMA load of the compiler's in this path)
+            const int64_t k1 = min(kb + 1, klast);
+            t.frag_setup(lds);
+            t.glds_src(x, (int)kb);
+            t.template glds_issue<PAIR>(kb * BK, kb * BK, lds);
+            t.template glds_x_c<0>();
+            t.glds_src(x, (int)k1);
+            t.template glds_issue<PAIR>(k1 * BK, k1 * BK, lds + T::G_STAGE);
+            t.template glds_x_c<1>();
+        } else {
+            issue(kb, 0);
+            issue(min(kb + 1, klast), 1);
+        }
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");   // stage 0 landed (this wave's share)
         __builtin_amdgcn_s_barrier();
         int cur = 0;
@@ -248,7 +262,103 @@ __device__ __forceinline__ void gram_streamk_glds_body(
         static_assert(T::MI == 4, "group 0 is dealt out over four fragment rows");
         constexpr int NP = T::G_NA + T::G_NB;
         constexpr int P1 = (NP + 2) / 3, P2 = 2 * P1 < NP ? 2 * P1 : NP;
-        if constexpr (GV & 32) {
+        if constexpr (GV & 512) {
+            // The dealt-out schedule below (placement B, loads two to an M0 write) with the stage as a compile-time
+            // constant.  Every segment starts its pipeline at stage 0, so the k-loop runs as trips of three k-steps on
+            // stages 0, 1, 2 and a tail of one to four steps whose stages are known as well.  Rolled over a runtime
+            // stage index, a k-step rebuilt the three stage bases, every fragment address, the M0 bases and the three
+            // global sources from scratch (about 65 scalar and vector instructions between its 128 MFMAs, with the
+            // wait states behind the multiplies); here the addresses come from frag_setup, the stage is an immediate,
+            // the sources advance by one scalar add each, and the multiply that scales a fragment row stands in
+            // front of the pair BEFORE the row's first one, so that its result is two MFMAs old when it is read.
+            // Same MFMAs on the same operands in the same order, same counted waits: the same bits.
+            // The loads of a step fetch step min(ks + 2, klast): the first L - 2 steps of a segment of L advance, the
+            // last two load stage klast again (every wave retires the same number of loads).  The trips hold
+            // advancing steps only; the tail sets its sources step by step.
+            static_assert((GV & 32) && (GV & 64) && PAIR == 2, "the constant-stage loop is the production schedule");
+            constexpr int QBAR = 4;
+            const int L = (int)(ke - kb);
+            int trips = (L > 2 ? L - 2 : 0) / 3;
+            asm volatile("" : "+s"(trips));                      // (a scalar register: the trip count is counted on the scalar ALU)
+            auto step = [&](auto ctag, auto atag) {
+                constexpr int CUR = decltype(ctag)::value, NX1 = (CUR + 1) % 3, NX2 = (CUR + 2) % 3;
+                constexpr bool ADV = decltype(atag)::value;
+                static_for<0, 4>([&](auto gtag) {
+                    constexpr int g = decltype(gtag)::value;
+                    constexpr int S = g & 1, NS = S ^ 1;
+                    static_for<0, 16>([&](auto qtag) {
+                        constexpr int q = decltype(qtag)::value;
+                        constexpr int I = q >> 2, P = q & 3;
+                        if constexpr (P == 3 && I < 3) t.template scale_row<S, I + 1>();
+                        if constexpr (P == 3 && I == 3) {
+                            // row 0 of the next group.  Its fragments were asked for eight pairs ago or more; ONE
+                            // lgkmcnt(0) here (vmcnt and expcnt left alone) stands for the counted wait the compiler
+                            // would otherwise put in front of the first use of every part.
+                            __builtin_amdgcn_s_waitcnt(0xC07F);
+                            __builtin_amdgcn_sched_barrier(0);
+                            t.template scale_row<NS, 0>();
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (g == 3 && q == QBAR && !(GV & 2)) {
+                            asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(NLD) : "memory");
+                            __builtin_amdgcn_s_barrier();
+                        }
+                        t.template mma_pair<S, I, P>();
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (g < 3) {
+                            constexpr int rp = q - 1;                 // read part behind this pair
+                            if constexpr (rp >= 0 && rp < 7 && !(GV & 4)) t.template read_part_c<NS, rp, CUR, g + 1>();
+                            constexpr int p0 = 2 * (q - 8);           // load run behind this pair
+                            if constexpr (g == 0 && p0 >= 0 && !(GV & 1)) {
+                                if constexpr (p0 < NP) t.template glds_pair_c<NX2, p0>();
+                                if constexpr (p0 == NP) {
+                                    t.template glds_x_c<NX2>();
+                                    if constexpr (ADV) t.glds_src_advance();
+                                }
+                            }
+                        } else {
+                            // (after the last step this reads the redundant, already landed copy of stage klast)
+                            constexpr int rp = q - QBAR - 1;
+                            if constexpr (rp >= 0 && rp < 7 && !(GV & 4)) t.template read_part_c<NS, rp, NX1, 0>();
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                });
+            };
+            constexpr std::integral_constant<int, 0> s0{};
+            constexpr std::integral_constant<int, 1> s1{};
+            constexpr std::integral_constant<int, 2> s2{};
+            t.template scale_row<0, 0>();
+            t.glds_src(x, (int)kb + 2);
+#pragma unroll 1
+            for (int tr = 0; tr < trips; ++tr) {
+                t.pin_acc();
+                step(s0, std::true_type{});
+                step(s1, std::true_type{});
+                step(s2, std::true_type{});
+            }
+            t.pin_acc();                                         // (between the loop and every step of the tail: mfma_tile.hpp)
+            const int rest = L - 3 * trips;                      // 1 .. 4 steps, the first of them on stage 0
+            const int kt = (int)kb + 3 * trips + 2, kl = (int)klast;
+            t.glds_src(x, min(kt, kl));
+            step(s0, std::false_type{});
+            t.pin_acc();
+            if (rest >= 2) {
+                t.glds_src(x, min(kt + 1, kl));
+                step(s1, std::false_type{});
+                t.pin_acc();
+                if (rest >= 3) {
+                    t.glds_src(x, min(kt + 2, kl));
+                    step(s2, std::false_type{});
+                    t.pin_acc();
+                    if (rest >= 4) {
+                        t.glds_src(x, min(kt + 3, kl));
+                        step(s0, std::false_type{});
+                        t.pin_acc();
+                    }
+                }
+            }
+        } else if constexpr (GV & 32) {
             // Dealt-out schedule: nothing is issued as a block at a group boundary.  A fragment group is sixteen pairs
             // of MFMAs; behind every pair goes ONE small thing -- a part of the next group's LDS reads, two of the
             // loads of stage ks+2, the multiply that scales the next fragment row -- so that each of them issues in
@@ -376,7 +486,10 @@ __device__ __forceinline__ void gram_streamk_glds_body(
     }
 }
 
-constexpr int GRAM_GV = 224;    // schedule of the production Gram kernel: dealt out (32), placement B (64), loads two to an M0 write (128)
+// schedule of the production Gram kernel: dealt out (32), placement B (64), loads two to an M0 write (128), the stage of
+// every k-step a compile-time constant (512)
+constexpr int GRAM_GV = 224 | 512;
+constexpr int GRAM_GV_ROLLED = 224;     // the same schedule rolled over a runtime stage index (production before; A/B)
 template <class T, int GV = 0>
 __global__ __launch_bounds__(NTHREADS, 1) void gram_streamk_glds_kernel(
     const double* __restrict__ V, int64_t ldv, int64_t m, int64_t n, const double* __restrict__ x,
@@ -2616,9 +2729,11 @@ template <class T>
 static int gram_launch_t(accbpg_dopt* h, const double* x, double* gram) {
     if constexpr (!T::EDGE && T::BM == 256) {
         if (h->use_glds || h->has_duals) {
-            // production: the dealt-out schedule, placement B, loads two to an M0 write (GRAM_GV); the development switch
-            // selects one load per M0 write through the builtin (1: round 3's first form), four to an M0 write (2), or
-            // the block schedule of round 2 (3) -- all give bit-identical results.
+            // production: the dealt-out schedule, placement B, loads two to an M0 write, the stage of every k-step a
+            // compile-time constant (GRAM_GV); the development switch selects one load per M0 write through the builtin
+            // (1: round 3's first form), four to an M0 write (2), or the block schedule of round 2 (3), all three on the
+            // loop rolled over a runtime stage index; gram_rolled runs production's schedule on that loop -- all give
+            // bit-identical results.
             // Long rows (gram_chunks > 1): one launch per column block of V, each adding its Gram matrix to G.
             const int64_t nc = h->gram_chunks > 1 ? h->gram_nc : h->n;
             for (int c = 0; c < h->gram_chunks; ++c) {
@@ -2629,12 +2744,14 @@ static int gram_launch_t(accbpg_dopt* h, const double* x, double* gram) {
                 const int all_slabs = h->gram_chunks > 1 ? 1 : 0;   // (the plan of a chunked handle lists every segment)
                 prof_begin(h, PROF_GRAM);
 #define ACC_GRAM_ARGS Vc, ldc, h->m, nc, xc, h->tiles, h->wg_ranges, h->kiters, h->gram_nslot, h->slabs, gram, h->m, all_slabs
-                if (h->kern_variant == 1)
-                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GRAM_GV ^ 128>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                if (h->gram_rolled && h->kern_variant == 0)
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GRAM_GV_ROLLED>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                else if (h->kern_variant == 1)
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GRAM_GV_ROLLED ^ 128>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
                 else if (h->kern_variant == 3)
                     ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, 0>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
                 else if (h->kern_variant == 2)
-                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, (GRAM_GV ^ 128) | 256>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
+                    ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, (GRAM_GV_ROLLED ^ 128) | 256>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
                 else
                     ACC_LAUNCH_LDS(h->device, (gram_streamk_glds_kernel<T, GRAM_GV>), h->gram_grid, NTHREADS, T::G_LDS_BYTES, h->stream, ACC_GRAM_ARGS);
 #undef ACC_GRAM_ARGS
@@ -2721,6 +2838,13 @@ int debug_gram_variant(accbpg_dopt* h, const double* x, int var, int iters, doub
             case 27: ACC_LAUNCH_G(99); break;     /* dealt-out, reads only (no loads, no barrier) */
             case 28: ACC_LAUNCH_G(224); break;    /* dealt-out, loads two to an M0 write */
             case 29: ACC_LAUNCH_G(352); break;    /* dealt-out, loads four to an M0 write */
+            case 30: ACC_LAUNCH_G(736); break;    /* 28 with the stage a compile-time constant (production) */
+            case 31: ACC_LAUNCH_G(742); break;    /* 30, loads only (no barrier, no reads) */
+            case 32: ACC_LAUNCH_G(739); break;    /* 30, reads only (no loads, no barrier) */
+            case 33: ACC_LAUNCH_G(743); break;    /* 30, MFMA only */
+            case 34: ACC_LAUNCH_G(230); break;    /* 28, loads only */
+            case 35: ACC_LAUNCH_G(227); break;    /* 28, reads only */
+            case 36: ACC_LAUNCH_G(231); break;    /* 28, MFMA only */
             case 0: ACC_LAUNCH_VAR(0); break;
             case 1: ACC_LAUNCH_VAR(1); break;
             case 2: ACC_LAUNCH_VAR(2); break;

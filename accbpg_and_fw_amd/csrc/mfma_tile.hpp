@@ -511,6 +511,102 @@ struct Tile {
         }
     }
 
+    // ---- the Gram k-loop with the stage as a compile-time constant (gram_streamk_glds_body, GV & 512) -------------
+    // What a k-step needs of addresses that does not change from step to step is worked out once per segment and kept
+    // in registers: the LDS byte address of fragment group kk of stage s for this lane (A and B image; the swizzle makes
+    // it a function of kk, not an offset), of its x values, the LDS addresses of the wave's first piece of stage 0 (the
+    // stage goes into the immediate of the M0 write), and the lane offset of the x load.  The empty asm statements
+    // make the values opaque: the compiler can neither rebuild them from lane constants inside the loop nor fold the
+    // three stages of one group into one register plus an add per use.
+    typedef const __attribute__((address_space(3))) double* lptr;
+    uint32_t fra[3][4], frb[3][4], frx[3];
+    uint32_t gla, glb, glx, gxo;
+    const char* gpa;                                            // sources of the k-step the next loads of the loop fetch
+    const char* gpb;
+    const char* gpx;
+    __device__ __forceinline__ void frag_setup(const double* __restrict__ lds) {
+        static_assert(!BKM, "k-contiguous B image");
+        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+        const int lr = lane & 15, lq = lane >> 4;
+        const int sw = (lr >> 1) & 7;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const double* stage = lds + s * G_STAGE;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int koff = 2 * ((2 * kk + (lq >> 1)) ^ sw) + (lq & 1);      // as read_part_g
+                fra[s][kk] = lds_addr(stage + (16 * wm + lr) * BK + koff);
+                frb[s][kk] = lds_addr(stage + G_A + (wn * WN + lr) * BK + koff);
+                asm volatile("" : "+v"(fra[s][kk]));
+                asm volatile("" : "+v"(frb[s][kk]));
+            }
+            frx[s] = lds_addr(stage + G_A + G_B + lq);
+            asm volatile("" : "+v"(frx[s]));
+        }
+        gla = lds_addr(lds + wave * G_NA * 128);                // as glds_issue_range: runs of consecutive pieces
+        glb = lds_addr(lds + G_A + wave * G_NB * 128);
+        glx = lds_addr(lds + G_A + G_B);
+        gxo = (uint32_t)(lane & 31) * 4;                         // as glds_x
+        asm volatile("" : "+s"(gla));
+        asm volatile("" : "+s"(glb));
+        asm volatile("" : "+s"(glx));
+        asm volatile("" : "+v"(gxo));
+    }
+    // the loads that follow fetch k-step k (after glds_setup_A / _B_kc of the segment)
+    __device__ __forceinline__ void glds_src(const double* __restrict__ x, int k) {
+        gpa = gbase_a + (int64_t)k * (BK * 8);
+        gpb = gbase_b + (int64_t)k * (BK * 8);
+        gpx = reinterpret_cast<const char*>(x) + (int64_t)k * (BK * 8);
+        asm volatile("" : "+s"(gpa));
+        asm volatile("" : "+s"(gpb));
+        asm volatile("" : "+s"(gpx));
+    }
+    // ... and then the k-step behind it: one scalar add per source
+    __device__ __forceinline__ void glds_src_advance() {
+        gpa += BK * 8;
+        gpb += BK * 8;
+        gpx += BK * 8;
+        asm volatile("" : "+s"(gpa));
+        asm volatile("" : "+s"(gpb));
+        asm volatile("" : "+s"(gpx));
+    }
+    // pieces P0, P0 + 1 of the combined list (glds_issue_range<2>) into stage STG
+    template <int STG, int P0>
+    __device__ __forceinline__ void glds_pair_c() const {
+        static_assert(G_NA % 2 == 0 && G_NB % 2 == 0 && P0 % 2 == 0 && P0 < G_NA + G_NB, "whole runs of two");
+        if constexpr (P0 < G_NA) glds16_run2<STG * G_STAGE * 8 + P0 * 1024>(gpa, goa[P0], goa[P0 + 1], gla);
+        else glds16_run2<STG * G_STAGE * 8 + (P0 - G_NA) * 1024>(gpb, gob[P0 - G_NA], gob[P0 - G_NA + 1], glb);
+    }
+    // glds_x into stage STG, as a statement of the same kind as the runs (no lane address arithmetic: scalar base +
+    // lane offset).  The "m0" clobber is required here as it is there.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+    template <int STG>
+    __device__ __forceinline__ void glds_x_c() const {
+        asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
+                     :: "v"(gxo), "s"(gpx), "s"(glx), "i"(STG * G_STAGE * 8) : "memory", "scc", "m0");
+    }
+#pragma clang diagnostic pop
+    // read_part_g<SET, true, PART>(stage STG, KK) from the addresses of frag_setup
+    template <int SET, int PART, int STG, int KK>
+    __device__ __forceinline__ void read_part_c() {
+        static_assert(MI == 4 && NI == 8, "parts are laid out for the 64 x 128 wave tile");
+        if constexpr (PART == 0) {
+            fx[SET] = reinterpret_cast<lptr>(frx[STG])[4 * KK];
+        } else if constexpr (PART == 1 || PART == 6) {
+            lptr as = reinterpret_cast<lptr>(fra[STG][KK]);
+            constexpr int i0 = (PART == 1) ? 0 : 2;
+            fa[SET][i0] = as[i0 * 16 * WAVES_M * BK];
+            fa[SET][i0 + 1] = as[(i0 + 1) * 16 * WAVES_M * BK];
+        } else {
+            lptr bs = reinterpret_cast<lptr>(frb[STG][KK]);
+            constexpr int j0 = 2 * (PART - 2);
+            fb[SET][j0] = bs[j0 * 16 * BK];
+            fb[SET][j0 + 1] = bs[(j0 + 1) * 16 * BK];
+        }
+    }
+
     // ---- gradient product: k-steps with the triangular skip resolved at compile time -------------
     // ILO = first fragment row of the step that can be non-zero.  Rows below it do not exist in the step (no MFMAs, no
     // A-fragment reads), rows above it are live for every wave, and row ILO itself is live for the waves that say so

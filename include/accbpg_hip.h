@@ -874,7 +874,10 @@ int accbpg_test_gemm(const double* A_dev, int64_t lda, const double* B_dev, int6
 
 /* Timing ablations of the Gram kernel (development aid; variant 0 is the product kernel, the
  * others drop global loads / LDS staging / the barrier / fragment reads and produce wrong data
- * into scratch).  Average milliseconds per launch over `iters` launches. */
+ * into scratch).  Average milliseconds per launch over `iters` launches.  Codes 10..29: the direct-to-LDS kernel's
+ * schedules and their ablations (tools/ablate_gram.py names them); 28 = the production schedule with its k-loop rolled
+ * over a runtime stage index, 30 = with the stage a compile-time constant (production), 34..36 / 31..33 = "loads only",
+ * "reads only", "MFMA only" of 28 / 30. */
 int accbpg_debug_gram_variant(accbpg_dopt* h, const double* x_dev, int variant, int iters, double* ms_host);
 /* The same for the direct-to-LDS gradient kernel, on the inverse factor the handle holds from its last gradient
  * evaluation: variant 0 = the product kernel, 3 = its schedule before the k loop was split into phases, 10..13 = that
@@ -932,7 +935,10 @@ int accbpg_debug_prox_state(int* out3_host);
  * 1 skip the diagonal-block factorisation, 2 skip the panel solve, 4 skip the MFMA products; 8, 16, 32 switch
  * off the row solves / MFMA updates / 16x16 factor inside the 64x64 factorisation.  256 / 512 select the
  * register-staged / direct-to-LDS Gram and gradient kernels; bits 30..31 select the schedule of the direct-to-LDS
- * kernels (0 product, 1 / 2 development variants; bit-identical results).  2048 sets the scheme of the factorisation
+ * kernels (0 product, 1 / 2 development variants; bit-identical results); 1024 runs schedule 0 of the Gram kernel with
+ * its k-loop rolled over a runtime stage index, as before the stage became a compile-time constant (the loop of timing
+ * code 28 of accbpg_debug_gram_variant; without the bit, schedule 0 is the loop of code 30; bit-identical results).
+ * 2048 sets the scheme of the factorisation
  * (results agree to rounding): bits 12..23 = number of 64-wide block columns from which the two-level scheme
  * runs (default 64), bits 24..29 = block columns per outer panel (default 8; 0 leaves it). */
 int accbpg_debug_chol_variant(accbpg_dopt* h, int bits);

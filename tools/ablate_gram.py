@@ -1,5 +1,8 @@
 """What a launch of the Gram kernel is made of (development aid): timing ablations of the production loop and of the
-dealt-out schedule through accbpg_debug_gram_variant (wrong results except the first two), interleaved rounds."""
+dealt-out schedule through accbpg_debug_gram_variant (wrong results except the first two and codes 28, 30), interleaved
+rounds.  Codes 28 and 30 are the production schedule (placement B, loads two to an M0 write) rolled over a runtime stage
+index and with the stage a compile-time constant; 34..36 and 31..33 their "loads only", "reads only" and "MFMA only" forms,
+which bound what the instructions between the MFMAs of each loop cost."""
 import ctypes as C
 import json
 import os
@@ -10,7 +13,10 @@ sys.path.insert(0, ROOT)
 
 CODES = {10: "block schedule (production in round 2)", 19: "dealt-out schedule B", 20: "B, no loads in the loop",
          21: "B, no wait + barrier", 22: "B, no fragment reads", 23: "B, barrier without the vmcnt wait",
-         24: "B, MFMA only", 25: "B, loads only", 26: "B, barrier only", 27: "B, reads only"}
+         24: "B, MFMA only", 25: "B, loads only", 26: "B, barrier only", 27: "B, reads only",
+         28: "rolled loop (production before)", 34: "rolled, loads only", 35: "rolled, reads only", 36: "rolled, MFMA only",
+         30: "constant-stage loop (production)", 31: "constant stage, loads only", 32: "constant stage, reads only",
+         33: "constant stage, MFMA only"}
 
 
 def main():
@@ -31,6 +37,7 @@ def main():
             _lib.check(lib.accbpg_debug_gram_variant(f._h, _ptr(x), c, 20, C.byref(ms)), "variant %d" % c)
             out[c].append(ms.value)
     res = {CODES[c]: min(v) for c, v in out.items()}
+    res["all rounds"] = {CODES[c]: v for c, v in out.items()}
     print(json.dumps(res, indent=1))
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as fh:
